@@ -5,7 +5,7 @@ A "step" (the headline `value`) is one pass of the hot path on every rank: numer
 HBM) followed by one solve (rhs resident in HBM, default iterative refinement) of the general-storage matrix -- the call the
 reference's Radau5 / Newton callers repeat, and the one the north_star compares with UMFPACK.  Prints ONE JSON line (rank 0).
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Beside the headline the same line carries (all measured in this run, outside the K timed steps):
@@ -46,6 +46,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
 FP64_PEAK_TFLOPS = 78.6    # MI355X FP64 (vector = matrix) peak, datasheet
 NRHS_TOTAL = 256           # BASELINE config 4 / north_star: 256 right-hand sides over the GPUs of the node
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SEED = 20261015
 
 
 def sptrsv_bytes(st, n, k=1):
@@ -75,6 +77,23 @@ def measured_traffic(grid, st):
             return None, "profiles/%s was taken on another build (stamp %r, this run %r): refused" % (name, stamp, want)
         return t["traffic_bytes_per_pass"], "profiles/%s: %s" % (name, t["source"])
     return None, None
+
+
+def dump_outputs(out_dir, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """Writes every array as out_dir/<name>.npy in float64.  An array above its share of the budget is cut down to a fixed
+    seeded sample of its entries (the same whatever the build), written beside it as <name>_index.npy (float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget_bytes // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        index_file = os.path.join(out_dir, name + "_index.npy")
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share // 16, replace=False))
+            np.save(index_file, idx.astype(np.float64))
+            a = a[idx]
+        elif os.path.exists(index_file):
+            os.remove(index_file)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def lower_triangle(n, rp, ci, v):
@@ -460,7 +479,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
     ap.add_argument("--no-configs", action="store_true", help="skip the config3 / config4 / config5 sections")
     ap.add_argument("--grid3d", type=int, default=100, help="edge of the 3D 7-point Poisson problem of the `poisson3d` extra (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution x of the last timed step (rank 0) as DIR/x.npy (float64; above "
+                         "64 MB a fixed seeded sample, its positions in DIR/x_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -528,6 +552,8 @@ def main():
     st = s.stats()
     x = np.zeros(n)
     s.d2h(x, d_x)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x})
     rel_err = residual_metric(n, rp, ci, v, x, b)
     perm = s.permutation() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
 

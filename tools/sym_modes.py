@@ -1,5 +1,6 @@
 import sys, os, time, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from russell_amd import problems as P
 from russell_amd.backend import Hipmf
 import scipy.sparse as sp
