@@ -137,6 +137,26 @@ int32_t solver_hipmf_prepare_solve_many(struct InterfaceHIPMF *solver, int32_t n
 int32_t solver_hipmf_factorize_device(struct InterfaceHIPMF *solver, const double *d_values);
 int32_t solver_hipmf_solve_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 
+/* Transposed solves A^T x = b with the factor of A: no second analysis or factorisation (UMFPACK's UMFPACK_At system of umfpack_di_solve,
+ * which interface_umfpack.c:229 calls with UMFPACK_A; MUMPS's ICNTL(9) in the job-3 call of interface_mumps.c:243-277).  Refined by the rule
+ * of solver_hipmf_solve (residual of A^T), Krylov-rescued after a factorisation that replaced pivots.  L D L^T / symmetric storage: the
+ * ordinary solve.  _device: nrhs columns (one at a time), leading dimension ld >= ndim.  Status codes as solver_hipmf_solve;
+ * ERROR_HIPMF_INVALID_VALUE for nrhs < 1 or ld < ndim. */
+int32_t solver_hipmf_solve_transpose(struct InterfaceHIPMF *solver, double *x, const double *rhs, C_BOOL verbose);
+int32_t solver_hipmf_solve_transpose_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
+
+/* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
+ * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
+ * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
+ * 1 all eight entries, 2 entries 0 - 4.  With a_i = sum_j |a_ij|, N_A = max a_i, N_x = |x|_inf, r = b - A x, d_i = (|A||x|)_i + |b_i|,
+ * I1 = {i : d_i > 1000 n eps (a_i N_x + |b_i|)}, I2 the rest:
+ *   [0] N_A  [1] N_x  [2] |r|_inf / (N_A N_x)  [3] omega1 = max_I1 |r_i| / d_i  [4] omega2 = max_I2 |r_i| / ((|A||x|)_i + a_i N_x)
+ *   [5] omega1 cond1 + omega2 cond2  [6] cond1  [7] cond2  (Arioli, Demmel & Duff 1989; cond by Hager / Higham's estimator with A^{-1}
+ *   and A^{-T}: at most 22 unrefined pass pairs, HIPMF_COUNTER_ANALYSIS_SOLVES).  The statistics of the solve are left as it set them.
+ * ERROR_HIPMF_INVALID_VALUE for an option other than 0, 1, 2. */
+int32_t solver_hipmf_solve_with_error_analysis(struct InterfaceHIPMF *solver, double *x, const double *rhs, double *error_analysis_array_len_8,
+                                               int32_t error_analysis_option, C_BOOL verbose);
+
 /* v = alpha * A * u on the device with the values of the last factorize (host pointers);
  * the CSR SpMV of russell_sparse/src/csr_matrix.rs:709-729 */
 int32_t solver_hipmf_mat_vec_mul(struct InterfaceHIPMF *solver, double *v, double alpha, const double *u);
@@ -214,6 +234,10 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
                                              what UMFPACK's dynamic pivoting, interface_umfpack.c:167, would have avoided) a column whose refined solution
                                              leaves |b - A x|_2 > 1e-13 |b|_2 is finished by flexible GMRES preconditioned with the factorisation
                                              (rank(E) + 1 steps in exact arithmetic); 0: not needed.  HIPMF_KRYLOV=0 switches it off */
+#define HIPMF_COUNTER_TRANSPOSED_SOLVES 20 /* right-hand sides solved with A^T (solver_hipmf_solve_transpose / _device; the complex twin's A^T / A^H) */
+#define HIPMF_COUNTER_ANALYSIS_SOLVES 21   /* pass pairs the condition estimates of the last solver_hipmf_solve_with_error_analysis took (at most 22) */
+#define HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS 22 /* steps of the Krylov rescue (A^T as the operator, the transposed pass pair as the preconditioner)
+                                                        in the last transposed solve; HIPMF_COUNTER_KRYLOV_ITERATIONS stays the last ordinary solve's */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -308,6 +332,8 @@ int32_t complex_solver_hipmf_factorize(struct InterfaceComplexHIPMF *solver, int
 int32_t complex_solver_hipmf_get_determinant(struct InterfaceComplexHIPMF *solver, double *determinant_coefficient_real,
                                              double *determinant_coefficient_imag, double *determinant_exponent);
 int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, C_BOOL verbose);
+/* conjugate: 1 -> A^H x = b, 0 -> A^T x = b (the real transposed solve of the real-equivalent system; umfpack_zi_solve's UMFPACK_Aat / UMFPACK_At) */
+int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose);
 int32_t complex_solver_hipmf_set_value_map(struct InterfaceComplexHIPMF *solver, int32_t nnz_in, const int32_t *seg_ptr, const int32_t *seg_idx);
 int32_t complex_solver_hipmf_factorize_mapped(struct InterfaceComplexHIPMF *solver, int32_t *effective_ordering, int32_t *effective_scaling,
                                               int32_t *num_perturbed_pivots, double *rcond_estimate, C_BOOL verbose, const double *input_values);

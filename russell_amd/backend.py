@@ -93,6 +93,25 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve")
         return x
 
+    def solve_transpose(self, rhs, verbose=False):
+        """x = A^{-T} rhs with the factor of A (L D L^T / symmetric storage: the ordinary solve)."""
+        b = np.ascontiguousarray(rhs, dtype=np.float64)
+        x = np.zeros(self.n)
+        code = self.lib.solver_hipmf_solve_transpose(self.h, x, b, int(verbose))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_transpose")
+        return x
+
+    def solve_with_error_analysis(self, rhs, option, verbose=False, array=None):
+        """(x, the eight MUMPS-style values) -- x as solve() returns it; option 1: all eight, 2: entries 0 - 4, 0: none (array untouched)."""
+        b = np.ascontiguousarray(rhs, dtype=np.float64)
+        x = np.zeros(self.n)
+        ea = np.zeros(8) if array is None else array
+        code = self.lib.solver_hipmf_solve_with_error_analysis(self.h, x, b, ea, int(option), int(verbose))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_with_error_analysis")
+        return x, ea
+
     def solve_many(self, rhs_colmajor):
         """rhs_colmajor: array of shape (nrhs, n) whose rows are the right-hand sides (= column-major n x nrhs)."""
         b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
@@ -128,7 +147,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22}
 
     OPTIONS = {"matching": 0, "pivoting": 1, "hybrid_memory": 2, "error_estimates": 3, "condition_numbers": 4, "sym_recheck": 5}
 
@@ -211,3 +230,8 @@ class Hipmf:
         code = self.lib.solver_hipmf_solve_device(self.h, d_x, d_rhs, nrhs, ld or self.n)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_device")
+
+    def solve_transpose_device(self, d_x, d_rhs, nrhs=1, ld=None):
+        code = self.lib.solver_hipmf_solve_transpose_device(self.h, d_x, d_rhs, nrhs, ld or self.n)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_transpose_device")

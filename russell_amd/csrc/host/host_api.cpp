@@ -722,9 +722,11 @@ std::string StatsLinSol::to_json(bool pretty) const {
       << ",\"initialize\":" << avg(initialize_ns) << ",\"factorize_array\":" << arr(factorize_ns) << ",\"factorize\":" << avg(factorize_ns)
       << ",\"solve_array\":" << arr(solve_ns) << ",\"solve\":" << avg(solve_ns) << ",\"total_ifs_array\":" << arr(total)
       << ",\"total_ifs\":" << avg(total) << ",\"verify\":" << verify_ns << "},"
-      // (stats_lin_sol.rs:100-113: MUMPS's own error analysis; zeros for every other solver, as in the reference)
-      << "\"mumps_stats\":{\"inf_norm_a\":0.0,\"inf_norm_x\":0.0,\"scaled_residual\":0.0,\"backward_error_omega1\":0.0,\"backward_error_omega2\":0.0,"
-         "\"normalized_delta_x\":0.0,\"condition_number1\":0.0,\"condition_number2\":0.0}}";
+      // (stats_lin_sol.rs:100-113: MUMPS's error analysis -- this backend's when LinSolParams asked for it, else zeros as in the reference)
+      << "\"mumps_stats\":{\"inf_norm_a\":" << f(mumps_stats[0]) << ",\"inf_norm_x\":" << f(mumps_stats[1]) << ",\"scaled_residual\":"
+      << f(mumps_stats[2]) << ",\"backward_error_omega1\":" << f(mumps_stats[3]) << ",\"backward_error_omega2\":" << f(mumps_stats[4])
+      << ",\"normalized_delta_x\":" << f(mumps_stats[5]) << ",\"condition_number1\":" << f(mumps_stats[6]) << ",\"condition_number2\":"
+      << f(mumps_stats[7]) << "}}";
     return pretty ? json_pretty(o.str()) : o.str();
 }
 
@@ -737,6 +739,9 @@ struct Backend {
     decltype(&solver_hipmf_initialize) initialize = nullptr;
     decltype(&solver_hipmf_factorize) factorize = nullptr;
     decltype(&solver_hipmf_solve) solve = nullptr;
+    decltype(&solver_hipmf_solve_transpose) solve_t = nullptr;
+    decltype(&solver_hipmf_solve_with_error_analysis) solve_ea = nullptr;
+    decltype(&complex_solver_hipmf_solve_transpose) zsolve_t = nullptr;
     decltype(&solver_hipmf_solve_many) solve_many = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
     decltype(&solver_hipmf_factorize_mapped) factorize_mapped = nullptr;
@@ -788,6 +793,9 @@ bool load_backend() {
     BIND(initialize, "solver_hipmf_initialize")
     BIND(factorize, "solver_hipmf_factorize")
     BIND(solve, "solver_hipmf_solve")
+    BIND(solve_t, "solver_hipmf_solve_transpose")
+    BIND(solve_ea, "solver_hipmf_solve_with_error_analysis")
+    BIND(zsolve_t, "complex_solver_hipmf_solve_transpose")
     BIND(solve_many, "solver_hipmf_solve_many")
     BIND(set_value_map, "solver_hipmf_set_value_map")
     BIND(factorize_mapped, "solver_hipmf_factorize_mapped")
@@ -910,6 +918,8 @@ StrError SolverHIPMF::factorize(const CooMatrix &mat, const LinSolParams *params
         if (e) return e;
     }
     LinSolParams par = params ? *params : LinSolParams();
+    // error analysis option (solver_mumps.rs:249-253)
+    error_analysis_option = par.compute_condition_numbers ? 1 : (par.compute_error_estimates ? 2 : 0);
     const int32_t verbose = par.verbose ? 1 : 0;
     if (!initialized) {
         compute_determinant = par.compute_determinant;
@@ -1010,7 +1020,20 @@ StrError SolverHIPMF::solve_slices(double *x, size_t nx, const double *rhs, size
     if (nx != initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
     if (nr != initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.solve((InterfaceHIPMF *)solver, x, rhs, verbose ? 1 : 0);
+    int32_t status = error_analysis_option == 0
+                         ? g_backend.solve((InterfaceHIPMF *)solver, x, rhs, verbose ? 1 : 0)
+                         : g_backend.solve_ea((InterfaceHIPMF *)solver, x, rhs, error_analysis_array_len_8, error_analysis_option, verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+StrError SolverHIPMF::solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (x.size() != initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.solve_t((InterfaceHIPMF *)solver, x.data(), rhs.data(), verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1201,6 +1224,17 @@ StrError ComplexSolverHIPMF::solve(std::vector<double> &x, const std::vector<dou
     return nullptr;
 }
 
+StrError ComplexSolverHIPMF::solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool conjugate, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (x.size() != 2 * initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_t((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), conjugate ? 1 : 0, verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
 void ComplexSolverHIPMF::update_stats(StatsLinSol &stats) const {
     stats.solver = "HIPMF";
     stats.initialize_ns.push_back(time_initialize_ns);
@@ -1242,6 +1276,7 @@ void SolverHIPMF::update_stats(StatsLinSol &stats) const {
     stats.perturbed_pivots = perturbed_pivots;
     stats.effective_matching = effective_matching ? "MaxProdScaled" : "None";
     stats.effective_pivoting = "LocalBlock"; // (enums.rs Pivoting::LocalBlock: pivot search inside the diagonal block of the supernode)
+    for (int k = 0; k < 8; k++) stats.mumps_stats[k] = error_analysis_array_len_8[k]; // (solver_mumps.rs:415-422)
 }
 
 StrError LinSolver::create(LinSolver &out, Genie genie) {
@@ -1689,6 +1724,13 @@ const char *rh_clinsolver_factorize(void *h, void *ccoo, const RhParams *params)
         return s->s->factorize(*(ComplexCooMatrix *)ccoo, &p);
     }
     return s->s->factorize(*(ComplexCooMatrix *)ccoo, nullptr);
+}
+const char *rh_clinsolver_solve_transpose(void *h, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t conjugate, int32_t verbose) {
+    RhComplexSolver *s = (RhComplexSolver *)h;
+    std::vector<double> xx((size_t)nx), rr(rhs, rhs + nr);
+    StrError e = s->s->solve_transpose(xx, rr, conjugate != 0, verbose != 0);
+    if (!e) std::copy(xx.begin(), xx.end(), x);
+    return e;
 }
 const char *rh_clinsolver_solve(void *h, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose) {
     RhComplexSolver *s = (RhComplexSolver *)h;

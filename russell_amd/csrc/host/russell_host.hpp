@@ -163,6 +163,7 @@ struct StatsLinSol {
     // hybrid_memory_factor, output.effective_pivoting / effective_mumps_num_threads / openmp_num_threads / umfpack_strategy /
     // umfpack_rcond_estimate) and the mumps_stats block (:100-113): a consumer of the reference's JSON finds every key
     std::string pivoting = "Unknown", effective_pivoting = "Unknown", umfpack_strategy = "Unknown";
+    double mumps_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // inf_norm_a, inf_norm_x, scaled_residual, omega1, omega2, normalized_delta_x, cond1, cond2
     bool has_hybrid_memory_factor = false;
     double hybrid_memory_factor = 0.0;
     size_t nrow = 0, ncol = 0, nnz = 0, nnz_actual = 0;
@@ -200,6 +201,12 @@ class SolverHIPMF : public LinSolTrait {
     StrError factorize(const CooMatrix &mat, const LinSolParams *params) override;
     StrError solve(std::vector<double> &x, const std::vector<double> &rhs, bool verbose) override;
     StrError solve_slices(double *x, size_t nx, const double *rhs, size_t nr, bool verbose); // (borrowed slices: no copies)
+    // extension (an inherent method, as solve_many: LinSolTrait stays the reference's): A^T x = rhs with the factor of A
+    StrError solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool verbose);
+    // solver_mumps.rs:249-253: compute_condition_numbers -> 1 (all eight values), compute_error_estimates -> 2 (entries 0 - 4), else 0;
+    // every solve then goes through solver_hipmf_solve_with_error_analysis, and update_stats fills mumps_stats (solver_mumps.rs:415-422)
+    int32_t error_analysis_option = 0;
+    double error_analysis_array_len_8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     void update_stats(StatsLinSol &stats) const override;
     uint64_t get_ns_init() const override { return time_initialize_ns; }
     uint64_t get_ns_fact() const override { return time_factorize_ns; }
@@ -254,6 +261,8 @@ class ComplexSolverHIPMF {
     StrError factorize(const ComplexCooMatrix &mat, const LinSolParams *params);
     // x, rhs: interleaved complex vectors of length 2 n
     StrError solve(std::vector<double> &x, const std::vector<double> &rhs, bool verbose);
+    // extension: A^T x = rhs (conjugate = false) or A^H x = rhs (conjugate = true)
+    StrError solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool conjugate, bool verbose);
     bool factorized = false;
     void update_stats(StatsLinSol &stats) const; // complex_lin_solver.rs:12-104 (ComplexLinSolTrait::update_stats)
     uint64_t get_ns_init() const { return time_initialize_ns; }

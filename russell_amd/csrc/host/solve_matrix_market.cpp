@@ -5,8 +5,8 @@
 // print the StatsLinSol JSON; `--nrun` repeats with a fresh solver and keeps the largest error; an out-of-memory
 // factorize prints the JSON with main.out_of_memory = true and exits 0; the bfwb62 solution is checked at 1e-10.
 // Options of the other backends that have no meaning here (MUMPS threads, cuDSS hybrid memory, vismatrix output,
-// error estimates, condition numbers, UMFPACK's strategy switch) are accepted and ignored so that the reference's
-// sweep scripts run unchanged.
+// UMFPACK's strategy switch) are accepted and ignored so that the reference's sweep scripts run unchanged; error estimates
+// (-x) and condition numbers (-y) select the MUMPS-style error analysis (LinSolParams, mumps_stats of the JSON).
 //
 // usage: solve_matrix_market [-g hipmf] [-o ORDERING] [-s SCALING] [-p] [-d] [-v] [-r NRUN] [--hide-json] FILE.mtx
 #include "russell_host.hpp"
@@ -27,7 +27,7 @@ uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nan
 
 struct Options {
     std::string matrix_market_file, genie = "hipmf", ordering = "Auto", scaling = "Auto", matching_sym = "None", matching_gen = "Auto";
-    bool positive_definite = false, verbose = false, determinant = false, hide_json = false;
+    bool positive_definite = false, verbose = false, determinant = false, hide_json = false, error_estimates = false, condition_numbers = false;
     long nrun = 1;
     bool has_hybrid = false;
     double hybrid = 0.0;
@@ -112,7 +112,9 @@ int main(int argc, char **argv) {
         else if (arg == "-v" || arg == "--verbose") opt.verbose = true;
         else if (arg == "-d" || arg == "--determinant") opt.determinant = true;
         else if (arg == "--hide-json") opt.hide_json = true;
-        else if (arg == "-x" || arg == "--error-estimates" || arg == "-y" || arg == "--condition-numbers" || arg == "-u" ||
+        else if (arg == "-x" || arg == "--error-estimates") opt.error_estimates = true;
+        else if (arg == "-y" || arg == "--condition-numbers") opt.condition_numbers = true;
+        else if (arg == "-u" ||
                  arg == "--enforce-unsymmetric-strategy" || arg == "--vismatrix" || arg == "--override-prevent-issue") {
             // options of UMFPACK / MUMPS: nothing to switch in this backend
         } else if (!arg.empty() && arg[0] == '-') return usage(("unknown option " + arg).c_str());
@@ -129,6 +131,8 @@ int main(int argc, char **argv) {
     params.scaling = scaling_from(opt.scaling);
     params.positive_definite = opt.positive_definite;
     params.compute_determinant = opt.determinant;
+    params.compute_error_estimates = opt.error_estimates;
+    params.compute_condition_numbers = opt.condition_numbers;
     params.verbose = opt.verbose;
 
     StatsLinSol stats;

@@ -286,6 +286,20 @@ int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *h, double *x, c
     return guarded(h, [&]() { return c_solve_body(h, x, rhs, verbose); });
 }
 
+// A^T z = c (conjugate = 0) or A^H z = c (conjugate = 1): the transpose of the real-equivalent form [a -b; b a] is the real-equivalent form
+// of A^H, so the real transposed solve of the 2n system IS the A^H solve; A^T is the same solve with the imaginary parts of c and z negated
+// on the way in and out (a device kernel).  Reference: umfpack_zi_solve's UMFPACK_At / UMFPACK_Aat systems (the complex shim calls it with
+// UMFPACK_A, interface_complex_umfpack.c:235).
+int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h || !x || !rhs) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (conjugate != 0 && conjugate != 1) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        h->solver.opt.verbose = verbose == 1;
+        return h->solver.solve_transpose(x, rhs, 1, h->solver.S.n, false, conjugate == 0);
+    });
+}
+
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *h) { return h ? h->solver.last_error.c_str() : "null solver"; }
 
 static int32_t c_get_stats_body(struct InterfaceComplexHIPMF *h, int64_t *is, double *ds) {

@@ -461,6 +461,47 @@ int32_t solver_hipmf_solve_device(struct InterfaceHIPMF *h, double *d_x, const d
     return guarded(h, [&]() { return solve_device_body(h, d_x, d_rhs, nrhs, ld); });
 }
 
+// Transposed solves A^T x = b on the factor of A (reference: the transposed solves UMFPACK offers through its sys argument,
+// UMFPACK_At in umfpack_di_solve as interface_umfpack.c:229 calls it with UMFPACK_A, and MUMPS's ICNTL(9) != 1 in the job-3 call of
+// interface_mumps.c:243-277); same status codes as solver_hipmf_solve.
+static int32_t solve_transpose_body(struct InterfaceHIPMF *h, double *x, const double *rhs, C_BOOL verbose) {
+    if (!h || !x || !rhs) return ERROR_NULL_POINTER;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_transpose(x, rhs, 1, h->solver.S.n, false);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("solver_hipmf_solve_transpose: Solution completed (%d refinement step(s), omega = %.3e)\n", h->solver.refinement_steps_done_t,
+               h->solver.last_omega_t);
+    return code;
+}
+
+int32_t solver_hipmf_solve_transpose(struct InterfaceHIPMF *h, double *x, const double *rhs, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_transpose_body(h, x, rhs, verbose); });
+}
+
+int32_t solver_hipmf_solve_transpose_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld) {
+    return guarded(h, [&]() {
+        if (!h || !d_x || !d_rhs) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (nrhs < 1 || ld < h->solver.S.n) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        return h->solver.solve_transpose(d_x, d_rhs, nrhs, ld, true);
+    });
+}
+
+// Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
+// (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
+// error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
+int32_t solver_hipmf_solve_with_error_analysis(struct InterfaceHIPMF *h, double *x, const double *rhs, double *error_analysis_array_len_8,
+                                               int32_t error_analysis_option, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h || !x || !rhs || !error_analysis_array_len_8) return (int32_t)ERROR_NULL_POINTER;
+        if (error_analysis_option < 0 || error_analysis_option > 2) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        int32_t code = solve_body(h, x, rhs, verbose);
+        if (code != SUCCESSFUL_EXIT) return code;
+        return h->solver.error_analysis(x, rhs, error_analysis_array_len_8, error_analysis_option);
+    });
+}
+
 int32_t solver_hipmf_mat_vec_mul(struct InterfaceHIPMF *h, double *v, double alpha, const double *u) {
     if (!h || !v || !u) return ERROR_NULL_POINTER;
     return guarded(h, [&]() { return h->solver.spmv(v, u, alpha, false); });
@@ -540,6 +581,9 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_SYM_WEAK_DIAGONAL: return s.sym_weak_diag_seen ? 1 : 0;
     case HIPMF_COUNTER_BCAST_SLICED_BYTES: return h->bcast_sliced_bytes;
     case HIPMF_COUNTER_KRYLOV_ITERATIONS: return s.krylov_iterations;
+    case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
+    case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
+    case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
     default: return -1;
     }
 }

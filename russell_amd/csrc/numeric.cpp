@@ -16,6 +16,7 @@
 #include <mutex>
 
 #include "kernels.hpp"
+#include "kernels_solve_transpose.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <pthread.h>
@@ -84,6 +85,7 @@ void Solver::release() {
     int caller_device = -1; // the caller's current device is restored on the way out
     if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
     (void)hipSetDevice(device);
+    tr_release();
     void *ptrs[] = {d_vs, d_vs2, d_sa_ptr, d_sa_k, d_sa_pos, d_zero, d_seg_ptr, d_seg_idx, d_vin, d_blk, d_work_blk, d_cs == d_rs ? nullptr : d_cs, matched ? d_rperm : nullptr, d_trace, d_sf, d_need, d_sync, d_dws,   d_ear,   d_fd,    d_ea,    d_st,    d_info, d_scalar, d_work, d_vals, d_xp,   d_r,    d_den,  d_b,    d_x,     d_du,   d_rows,
                     d_rel,   d_child, d_lists, d_tasks, d_rp,    d_ci,   d_arow, d_tptr, d_tidx, d_perm, d_sc_k, d_sc_at, d_ea_sc, d_sc_pos, d_diag, d_bigfd, d_row_blk, d_dcol, d_pool, d_lperm,
                     d_rs};
@@ -2979,7 +2981,7 @@ int32_t Solver::singular_verdict() {
 // z_k = M^{-1} v_k are kept, w_k = A z_k is formed with the true matrix): the near-singular solves with M only need to give USEFUL
 // directions, not accurate ones.  Host-side vectors (a rare path: only after a factorisation that perturbed pivots, and only for columns
 // whose refined solution is not accurate): M^{-1} v = one unrefined pass pair through the device kernels, A z = the device SpMV.
-int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device) {
+int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device, const KrylovOps *ops) {
     const int32_t n = S.n;
     const size_t nb = sizeof(double) * (size_t)n;
     std::vector<double> xh((size_t)n), bh((size_t)n), r((size_t)n), w((size_t)n);
@@ -2995,7 +2997,7 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device) {
         return (double)sqrtl(t);
     };
     auto residual = [&]() -> int32_t { // r = b - A x
-        int32_t c = spmv(w.data(), xh.data(), 1.0, false);
+        int32_t c = ops ? ops->apply(w.data(), xh.data()) : spmv(w.data(), xh.data(), 1.0, false);
         if (c != SUCCESSFUL_EXIT) return c;
         for (int32_t i = 0; i < n; i++) r[(size_t)i] = bh[(size_t)i] - w[(size_t)i];
         return SUCCESSFUL_EXIT;
@@ -3027,7 +3029,7 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device) {
         int32_t k = 0;
         for (; k < m; k++) {
             Z.emplace_back((size_t)n);
-            code = solve_core(Z[(size_t)k].data(), V[(size_t)k].data(), 1, n, false); // z_k = M^{-1} v_k
+            code = ops ? ops->precond(Z[(size_t)k].data(), V[(size_t)k].data()) : solve_core(Z[(size_t)k].data(), V[(size_t)k].data(), 1, n, false); // z_k = M^{-1} v_k
             if (code != SUCCESSFUL_EXIT) break;
             bool finite = true;
             for (double e : Z[(size_t)k]) finite = finite && std::isfinite(e);
@@ -3035,7 +3037,7 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device) {
                 Z.pop_back();
                 break;
             }
-            code = spmv(w.data(), Z[(size_t)k].data(), 1.0, false); // w = A z_k
+            code = ops ? ops->apply(w.data(), Z[(size_t)k].data()) : spmv(w.data(), Z[(size_t)k].data(), 1.0, false); // w = A z_k
             if (code != SUCCESSFUL_EXIT) break;
             krylov_iterations++;
             for (int32_t j = 0; j <= k; j++) { // modified Gram-Schmidt
@@ -3631,6 +3633,379 @@ int32_t Solver::determinant_complex(double *mantissa_re, double *mantissa_im, do
     if (mantissa_im) *mantissa_im = mi;
     if (exponent) *exponent = e;
     if (rcond) *rcond = (zmax > 0.0 && std::isfinite(zmin)) ? zmin / zmax : 0.0;
+    return SUCCESSFUL_EXIT;
+}
+
+// ---- transposed solves (A^T x = b) and the error analysis ----
+// The plan (built at the first transposed solve of a factor): per level the small fronts (one wavefront each) and, for the big fronts,
+// the assembly / gather tasks (TR_ROWS rows of the front's vector each) and the GEMV tasks (TR_COLS stored columns of E' resp. E each).
+// A^T as CSR: for row i of A^T (column i of A) the rows of A holding an entry in that column, in ascending order, and where its value
+// sits in d_vals -- values are read through the map, so refreshed values, factorize_mapped and adopt_factor need nothing here.
+int32_t Solver::tr_release() {
+    for (void *p : {(void *)d_tr_list, (void *)d_ttptr, (void *)d_ttrow, (void *)d_ttmap, (void *)d_tr_tasks, (void *)d_work_t, (void *)d_tvec, (void *)d_tnrm, (void *)d_anl})
+        if (p) (void)hipFree(p);
+    if (h_tnrm) (void)hipHostFree(h_tnrm);
+    d_tr_list = d_ttptr = d_ttrow = d_ttmap = nullptr, d_tr_tasks = nullptr, d_work_t = d_tvec = d_anl = nullptr, d_tnrm = nullptr, h_tnrm = nullptr;
+    tr_levels.clear();
+    tr_ready = false;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::tr_prepare() {
+    if (tr_ready) return SUCCESSFUL_EXIT;
+    const int32_t n = S.n;
+    std::vector<int32_t> list;
+    std::vector<SolveTask> tasks;
+    tr_levels.assign((size_t)S.nlevels, TrLevel());
+    for (int32_t l = 0; l < S.nlevels; l++) {
+        TrLevel &T = tr_levels[(size_t)l];
+        std::vector<int32_t> big;
+        T.small_off = (int32_t)list.size();
+        for (int32_t k = S.level_ptr[l]; k < S.level_ptr[l + 1]; k++) {
+            const int32_t s = S.level_sn[k];
+            if (S.fsize(s) <= SMALL_F) {
+                list.push_back(s);
+                T.small_pmax = std::max(T.small_pmax, S.npiv(s)), T.small_fmax = std::max(T.small_fmax, S.fsize(s));
+            } else {
+                big.push_back(s);
+            }
+        }
+        T.small_cnt = (int32_t)list.size() - T.small_off;
+        auto emit = [&](int32_t &off, int32_t &cnt, bool rows_of_front, bool all_cols, int32_t step) {
+            off = (int32_t)tasks.size();
+            for (int32_t s : big) {
+                const int32_t ext = (rows_of_front || all_cols) ? S.fsize(s) : S.npiv(s);
+                for (int32_t r0 = 0; r0 < ext; r0 += step) tasks.push_back({s, r0, std::min(ext, r0 + step)});
+            }
+            cnt = (int32_t)tasks.size() - off;
+        };
+        emit(T.asm_off, T.asm_cnt, true, false, TR_ROWS);  // forward: the front's vector
+        emit(T.gf_off, T.gf_cnt, false, true, TR_COLS);    // forward: the f columns of E'
+        emit(T.ga_off, T.ga_cnt, true, false, TR_ROWS);    // backward: the front's vector
+        emit(T.gb_off, T.gb_cnt, false, false, TR_COLS);   // backward: the p columns of E
+    }
+    HIPC(dev_upload(&d_tr_list, list), ERROR_HIP_MALLOC);
+    HIPC(dev_upload(&d_tr_tasks, tasks), ERROR_HIP_MALLOC);
+    // A^T by a counting pass over the stored pattern (rows ascending: the entries of a column of A come out in row order)
+    const int64_t nnz = S.nnz_a;
+    std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
+    HIPC(hipMemcpy(rp.data(), d_rp, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpy(ci.data(), d_ci, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    std::vector<int32_t> tp((size_t)n + 1, 0), trow((size_t)nnz), tmap((size_t)nnz);
+    for (int64_t k = 0; k < nnz; k++) tp[(size_t)ci[(size_t)k] + 1]++;
+    for (int32_t i = 0; i < n; i++) tp[(size_t)i + 1] += tp[(size_t)i];
+    std::vector<int32_t> fill(tp.begin(), tp.end() - 1);
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t k = rp[(size_t)i]; k < rp[(size_t)i + 1]; k++) {
+            const int32_t q = fill[(size_t)ci[(size_t)k]]++;
+            trow[(size_t)q] = i, tmap[(size_t)q] = k;
+        }
+    HIPC(dev_upload(&d_ttptr, tp), ERROR_HIP_MALLOC);
+    HIPC(dev_upload(&d_ttrow, trow), ERROR_HIP_MALLOC);
+    HIPC(dev_upload(&d_ttmap, tmap), ERROR_HIP_MALLOC);
+    HIPC(hipMalloc((void **)&d_work_t, sizeof(double) * ((size_t)std::max<int64_t>(work_up, 1) + 64)), ERROR_HIP_MALLOC);
+    HIPC(hipMalloc((void **)&d_tvec, sizeof(double) * 6 * (size_t)n), ERROR_HIP_MALLOC);
+    HIPC(hipMalloc((void **)&d_tnrm, sizeof(unsigned long long) * 2), ERROR_HIP_MALLOC);
+    HIPC(hipHostMalloc((void **)&h_tnrm, sizeof(double) * 2), ERROR_HIP_MALLOC);
+    tr_ready = true;
+    return SUCCESSFUL_EXIT;
+}
+
+// both passes of A^T on the permuted, scaled vector xp (in place), one launch per level and front class
+int32_t Solver::run_transposed(double *xp) {
+    const size_t nl = tr_levels.size();
+    for (size_t l = 0; l < nl; l++) {
+        const TrLevel &T = tr_levels[l];
+        if (T.small_cnt > 0) {
+            const int32_t ldu = T.small_pmax | 1;
+            hipLaunchKernelGGL(k_tr_fwd_small, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_fmax * (size_t)ldu, STREAM,
+                               d_tr_list + T.small_off, d_fd, d_pool, d_child, d_rel, d_work_t, xp, ldu);
+        }
+        if (T.asm_cnt > 0)
+            hipLaunchKernelGGL(k_tr_assemble, dim3(T.asm_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.asm_off, d_fd, d_child, d_rel, d_work_t, (const double *)xp);
+        if (T.gf_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemv<true>, dim3(T.gf_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gf_off, d_fd, d_pool, d_work_t, xp);
+    }
+    for (size_t l = nl; l-- > 0;) {
+        const TrLevel &T = tr_levels[l];
+        if (T.ga_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gather, dim3(T.ga_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.ga_off, d_fd, d_rows, d_work_t, (const double *)xp);
+        if (T.gb_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemv<false>, dim3(T.gb_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gb_off, d_fd, d_pool, d_work_t, xp);
+        if (T.small_cnt > 0) {
+            const int32_t ldl = T.small_fmax | 1;
+            hipLaunchKernelGGL(k_tr_bwd_small, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_pmax * (size_t)ldl, STREAM,
+                               d_tr_list + T.small_off, d_fd, d_pool, d_rows, d_lperm, xp, ldl);
+        }
+    }
+    return SUCCESSFUL_EXIT;
+}
+
+// y = A^{-T} v (device vectors, y != v allowed to alias d_tvec slots other than xp): entry with the column permutation and scaling,
+// exit with the row ones (A^ = Pr Rs A Cs Pc: b^_j = cs[cp_j] b[cp_j], x[rp_i] = rs[rp_i] y_i)
+int32_t Solver::tr_pass(double *y, const double *v) {
+    const int32_t n = S.n;
+    const dim3 g((n + 255) / 256), b(256);
+    double *xp = d_tvec + 2 * (size_t)n;
+    hipLaunchKernelGGL(k_tr_perm_in, g, b, 0, STREAM, n, d_perm, d_cs, v, xp);
+    int32_t code = run_transposed(xp);
+    if (code != SUCCESSFUL_EXIT) return code;
+    hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, xp, y, 0);
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::tr_spmv(double *y, const double *x) {
+    const int32_t n = S.n;
+    hipLaunchKernelGGL(k_tr_spmv, dim3((n + 255) / 256), dim3(256), 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, x, (const double *)nullptr, y,
+                       (unsigned long long *)nullptr);
+    return SUCCESSFUL_EXIT;
+}
+
+// One transposed solve of device vectors with the refinement rule of solve(): omega = max_i |r_i| / (|A^T||x| + |b|)_i; stop at omega <= eps,
+// after nstep steps or when a step fails to halve omega; a step that makes omega worse is taken back; a column within 64 eps is done
+// after its correction.
+int32_t Solver::tr_core(double *x, const double *bvec, int32_t nstep, double *omega, int32_t *steps) {
+    const int32_t n = S.n;
+    const dim3 g((n + 255) / 256), b(256);
+    const double EPS = 2.220446049250313e-16;
+    double *r = d_tvec + 3 * (size_t)n, *xp = d_tvec + 2 * (size_t)n; // (xp: after a correction step, the permuted correction)
+    *steps = 0;
+    *omega = INFINITY;
+    int32_t code = tr_pass(x, bvec);
+    if (code != SUCCESSFUL_EXIT || nstep <= 0) return code;
+    double prev = INFINITY;
+    for (int32_t it = 0;; it++) {
+        HIPC(hipMemsetAsync(d_tnrm, 0, sizeof(unsigned long long) * 2, STREAM), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_tr_spmv, g, b, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, (const double *)x, bvec, r, d_tnrm);
+        HIPC(hipMemcpyAsync(h_tnrm, d_tnrm, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        const double om = h_tnrm[1];
+        if (it > 0 && !(om < prev)) {
+            hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, (const double *)xp, x, 2); // take the last correction back
+            *omega = prev;
+            break;
+        }
+        *omega = om;
+        if (om <= EPS || it == nstep || (it > 0 && om > 0.5 * prev)) break;
+        prev = om;
+        hipLaunchKernelGGL(k_tr_perm_in, g, b, 0, STREAM, n, d_perm, d_cs, (const double *)r, xp);
+        code = run_transposed(xp);
+        if (code != SUCCESSFUL_EXIT) return code;
+        hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, (const double *)xp, x, 1);
+        (*steps)++;
+        if (prev <= 64.0 * EPS || it + 1 > nstep) break;
+    }
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs) {
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs) return ERROR_NULL_POINTER;
+    if (nrhs < 1 || ldx < S.n) return ERROR_HIPMF_INVALID_VALUE;
+    if ((S.sym_mode || d_tptr) && !conj_pairs) { // A^T = A (L D L^T fronts, symmetric storage): the ordinary solve, its bits
+        const int32_t code = solve(x, rhs, nrhs, ldx, on_device);
+        if (code == SUCCESSFUL_EXIT) transposed_solves += nrhs, last_omega_t = last_omega, refinement_steps_done_t = refinement_steps_done;
+        return code;
+    }
+    DeviceScope dev_scope(device);
+    int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    const int32_t n = S.n;
+    const size_t nb = sizeof(double) * (size_t)n;
+    const dim3 g((n + 255) / 256), b(256);
+    double *tb = d_tvec, *tx = d_tvec + (size_t)n;
+    krylov_iterations_t = 0;
+    for (int32_t j = 0; j < nrhs; j++) {
+        const double *bj = rhs + (int64_t)j * ldx;
+        double *xj = x + (int64_t)j * ldx;
+        HIPC(hipMemcpyAsync(tb, bj, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        if (conj_pairs) hipLaunchKernelGGL(k_tr_conj, g, b, 0, STREAM, n, tb);
+        double omega = INFINITY;
+        int32_t steps = 0;
+        code = tr_core(tx, tb, opt.refinement_nstep, &omega, &steps);
+        if (code != SUCCESSFUL_EXIT) return code;
+        if (krylov_enabled && !in_rescue && n_perturbed > 0 && !(omega <= krylov_omega_ok)) {
+            // FGMRES with A^T as the operator and the transposed pass pair as the preconditioner (host vectors; d_tvec slots 4 and 5).
+            // Its step count goes to krylov_iterations_t: krylov_iterations / krylov_last_relres stay what the last ordinary solve left.
+            double *tv = d_tvec + 4 * (size_t)n, *tz = d_tvec + 5 * (size_t)n;
+            KrylovOps ops;
+            ops.precond = [&](double *z, const double *v) -> int32_t {
+                HIPC(hipMemcpy(tv, v, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
+                const int32_t c = tr_pass(tz, tv);
+                if (c != SUCCESSFUL_EXIT) return c;
+                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+                HIPC(hipMemcpy(z, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+                return SUCCESSFUL_EXIT;
+            };
+            ops.apply = [&](double *w, const double *z) -> int32_t {
+                HIPC(hipMemcpy(tv, z, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
+                tr_spmv(tz, tv);
+                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+                HIPC(hipMemcpy(w, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+                return SUCCESSFUL_EXIT;
+            };
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            const int64_t keep_iter = krylov_iterations;
+            const double keep_relres = krylov_last_relres;
+            krylov_iterations = 0;
+            code = krylov_rescue(tx, tb, true, &ops);
+            if (j == 0) krylov_iterations_t = krylov_iterations;
+            krylov_iterations = keep_iter, krylov_last_relres = keep_relres;
+            if (code != SUCCESSFUL_EXIT) return code;
+        }
+        if (conj_pairs) hipLaunchKernelGGL(k_tr_conj, g, b, 0, STREAM, n, tx);
+        HIPC(hipMemcpyAsync(xj, tx, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        if (j == 0) last_omega_t = omega, refinement_steps_done_t = steps;
+    }
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    transposed_solves += nrhs;
+    return SUCCESSFUL_EXIT;
+}
+
+// ---- error analysis of a solution xbar of A x = b (Arioli, Demmel & Duff 1989; MUMPS's RINFOG(4..11)) ----
+//   a_i = sum_j |a_ij|, N_A = max a_i, N_x = |xbar|_inf, r = b - A xbar, d_i = (|A||xbar|)_i + |b_i|, tau_i = 1000 n eps (a_i N_x + |b_i|),
+//   I1 = {i : d_i > tau_i}, I2 = the rest.
+//   out[0] N_A, [1] N_x, [2] |r|_inf / (N_A N_x), [3] omega1 = max_{I1} |r_i| / d_i, [4] omega2 = max_{I2} |r_i| / ((|A||xbar|)_i + a_i N_x),
+//   [5] omega1 cond1 + omega2 cond2, [6] cond1 = est| |A^{-1}| w1 |_inf / N_x, [7] cond2 = est| |A^{-1}| w2 |_inf / N_x
+//   (w1 = d on I1, w2 = (|A||xbar|) + a N_x on I2, zeros elsewhere).
+// | |A^{-1}| w |_inf = |C|_1 with C = diag(w) A^{-T} is estimated by Hager / Higham's algorithm (LAPACK dlacn2): C v = w o (A^{-T} v) is one
+// transposed pass pair, C^T v = A^{-1} (w o v) one ordinary pass pair, both unrefined; at most 5 iterations + the alternating test vector,
+// i.e. at most 11 pass pairs per estimate.  The vector steps run on the device (only scalars come to the host), every reduction has a
+// fixed order: a repeat call gives the same bits.  (One liberty: the larger of two successive iterates' norms is kept -- both are lower
+// bounds of |C|_1 -- where dlacn2 keeps the later one.)
+int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *out, int32_t option) {
+    if (option == 0) return SUCCESSFUL_EXIT;
+    DeviceScope dev_scope(device);
+    const bool sym = S.sym_mode || d_tptr;
+    int32_t code = sym ? SUCCESSFUL_EXIT : tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    const int32_t n = S.n;
+    const size_t nb = sizeof(double) * (size_t)n;
+    const dim3 g((n + 255) / 256), b(256);
+    // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t, partials, scalars
+    // (kept per handle: a hipMalloc / hipFree pair of 12 n doubles per call would cost a device-wide synchronisation every time)
+    if (!d_anl) HIPC(hipMalloc((void **)&d_anl, nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
+    double *buf = d_anl;
+    double *X = buf, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + n, *W1 = AR + n, *W2 = W1 + n, *V = W2 + n, *Y = V + n, *Z = Y + n, *XI = Z + n, *T = XI + n;
+    double *pv = T + n, *sv = pv + EA_RED_WG;
+    unsigned long long *sc = (unsigned long long *)sv; // 8 words: maxima (bits), then the reduction result
+    int32_t *pi = (int32_t *)(sv + 8), *si = pi + EA_RED_WG;
+    HIPC(hipMemcpyAsync(X, xbar, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(B, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(sv, 0, sizeof(double) * 8 + sizeof(int32_t) * (EA_RED_WG + 8), STREAM), ERROR_HIP_MEMCPY);
+    hipLaunchKernelGGL(k_ea_rows, g, b, 0, STREAM, n, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, (const double *)X, (const double *)B, R, AX, AR, sc);
+    double h[8];
+    HIPC(hipMemcpyAsync(h, sc, sizeof(double) * 3, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    const double NA = h[0], NX = h[1], RN = h[2];
+    const double tau_scale = 1000.0 * (double)n * 2.220446049250313e-16;
+    hipLaunchKernelGGL(k_ea_split, g, b, 0, STREAM, n, tau_scale, NX, (const double *)R, (const double *)AX, (const double *)AR, (const double *)B, W1, W2, sc, si);
+    int32_t n2 = 0;
+    HIPC(hipMemcpyAsync(h + 3, sc + 3, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(&n2, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    const double om1 = h[3], om2 = h[4];
+    out[0] = NA, out[1] = NX, out[2] = (NA * NX > 0.0) ? RN / (NA * NX) : 0.0, out[3] = om1, out[4] = om2;
+    analysis_solves = 0;
+    if (option != 1) return SUCCESSFUL_EXIT;
+
+    // the statistics of the caller's solve stay as that solve left them
+    const double keep_omega = last_omega, keep_res = last_residual_inf, keep_relres = krylov_last_relres;
+    const std::vector<double> keep_col = col_omega;
+    const PhaseTimes keep_times = times;
+    const int32_t keep_steps = refinement_steps_done, keep_nstep = opt.refinement_nstep;
+    const int64_t keep_kry = krylov_iterations;
+    const bool keep_verbose = opt.verbose;
+    auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx) -> int32_t {
+        hipLaunchKernelGGL(k_ea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, n, mode, v, pv, pi);
+        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, STREAM, mode, (const double *)pv, (const int32_t *)pi, (double *)(sc + 5), si);
+        double t = 0.0;
+        int32_t ti = 0;
+        HIPC(hipMemcpyAsync(&t, sc + 5, sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipMemcpyAsync(&ti, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        *val = t;
+        if (idx) *idx = ti;
+        return SUCCESSFUL_EXIT;
+    };
+    auto inv = [&](double *y, const double *v) -> int32_t { // y = A^{-1} v, one unrefined ordinary pass pair
+        opt.refinement_nstep = 0, opt.verbose = false;
+        const bool keep_rescue = in_rescue;
+        in_rescue = true; // (no Krylov rescue inside)
+        const int32_t c = solve_core(y, v, 1, n, true);
+        in_rescue = keep_rescue;
+        analysis_solves++;
+        return c;
+    };
+    auto inv_t = [&](double *y, const double *v) -> int32_t { // y = A^{-T} v
+        if (sym) return inv(y, v);
+        const int32_t c = tr_pass(y, v);
+        analysis_solves++;
+        return c;
+    };
+    // C v and C^T v of C = diag(w) A^{-T}
+    auto cmul = [&](const double *w, double *y, const double *v) -> int32_t {
+        int32_t c = inv_t(T, v);
+        if (c != SUCCESSFUL_EXIT) return c;
+        hipLaunchKernelGGL(k_ea_hadamard, g, b, 0, STREAM, n, w, (const double *)T, y);
+        return SUCCESSFUL_EXIT;
+    };
+    auto ctmul = [&](const double *w, double *z, const double *v) -> int32_t {
+        hipLaunchKernelGGL(k_ea_hadamard, g, b, 0, STREAM, n, w, v, T);
+        return inv(z, T);
+    };
+    auto estimate = [&](const double *w, double *est) -> int32_t {
+        int32_t c;
+        hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 0, 0, V);
+        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+        if (n == 1) {
+            int32_t j0;
+            return reduce(Y, 1, est, &j0);
+        }
+        if ((c = reduce(Y, 0, est, nullptr)) != SUCCESSFUL_EXIT) return c;
+        HIPC(hipMemsetAsync(XI, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_ea_sign, g, b, 0, STREAM, n, (const double *)Y, XI, (int32_t *)(si + 1));
+        if ((c = ctmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
+        double zmax = 0.0;
+        int32_t j = 0;
+        if ((c = reduce(Z, 1, &zmax, &j)) != SUCCESSFUL_EXIT) return c;
+        for (int32_t iter = 2;; iter++) {
+            hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 2, j, V);
+            if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+            const double estold = *est;
+            double e = 0.0;
+            if ((c = reduce(Y, 0, &e, nullptr)) != SUCCESSFUL_EXIT) return c;
+            *est = std::max(e, estold);
+            int32_t changed = 0;
+            HIPC(hipMemsetAsync(si + 1, 0, sizeof(int32_t), STREAM), ERROR_HIP_MEMCPY);
+            hipLaunchKernelGGL(k_ea_sign, g, b, 0, STREAM, n, (const double *)Y, XI, (int32_t *)(si + 1));
+            HIPC(hipMemcpyAsync(&changed, si + 1, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            if (!changed || e <= estold) break; // repeated sign vector, or no growth
+            if ((c = ctmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
+            const int32_t jlast = j;
+            double zjlast = 0.0;
+            HIPC(hipMemcpyAsync(&zjlast, Z + jlast, sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            if ((c = reduce(Z, 1, &zmax, &j)) != SUCCESSFUL_EXIT) return c;
+            if (!(zjlast != zmax && iter < 5)) break;
+        }
+        hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 1, 0, V);
+        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+        double e = 0.0;
+        if ((c = reduce(Y, 0, &e, nullptr)) != SUCCESSFUL_EXIT) return c;
+        const double temp = 2.0 * (e / (3.0 * (double)n));
+        if (temp > *est) *est = temp;
+        return SUCCESSFUL_EXIT;
+    };
+    double e1 = 0.0, e2 = 0.0;
+    if (n - n2 > 0) code = estimate(W1, &e1);
+    if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
+    last_omega = keep_omega, last_residual_inf = keep_res, krylov_last_relres = keep_relres, col_omega = keep_col, times = keep_times;
+    refinement_steps_done = keep_steps, opt.refinement_nstep = keep_nstep, krylov_iterations = keep_kry, opt.verbose = keep_verbose;
+    if (code != SUCCESSFUL_EXIT) return code;
+    const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
+    out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
     return SUCCESSFUL_EXIT;
 }
 

@@ -126,7 +126,22 @@ class Solver {
     int32_t factorize_mapped(const double *input, bool on_device);
     int32_t solve(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device);
     int32_t solve_core(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device); // the driver of solve(): triangular passes + refinement
-    int32_t krylov_rescue(double *x, const double *rhs, bool on_device);                          // see numeric.cpp
+    // the operator pair of the Krylov rescue (host vectors): precond z = M^{-1} v, apply w = Op z; nullptr: the factorisation and A
+    struct KrylovOps {
+        std::function<int32_t(double *, const double *)> precond, apply;
+    };
+    int32_t krylov_rescue(double *x, const double *rhs, bool on_device, const KrylovOps *ops = nullptr); // see numeric.cpp
+    // Transposed solves A^T x = b on the stored factor (level-synchronous launches, kernels_solve_transpose.hpp), refined and rescued by the
+    // rules of solve(); conj_pairs: interleaved complex pairs whose imaginary parts are negated on the way in and out (the complex twin's
+    // A^T through the real-equivalent A^H).  L D L^T / symmetric storage: A^T = A, the ordinary solve.
+    int32_t solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs = false);
+    // MUMPS-style error analysis of a solution xbar of A x = b (host vectors; option 1: all eight values, 2: entries 0 - 4), see numeric.cpp
+    int32_t error_analysis(const double *xbar, const double *rhs, double *out, int32_t option);
+    int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
+    int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
+    int64_t krylov_iterations_t = 0; // FGMRES steps of the last transposed solve (krylov_iterations / krylov_last_relres stay the ordinary solve's)
+    double last_omega_t = 0.0;       // omega of the last transposed solve (first column)
+    int32_t refinement_steps_done_t = 0;
     int32_t singular_verdict();      // exactly zero pivots were met: singular (status 1), or only an unlucky static order (0)?  One probe solve decides
     int64_t zero_pivots_absorbed = 0; // exactly zero pivots of factorisations that the probe solve found NOT singular (summed)
     bool krylov_enabled = true;      // HIPMF_KRYLOV=0: no rescue (the refined solution is returned as it is)
@@ -421,6 +436,26 @@ class Solver {
     int32_t *d_row_blk = nullptr; // row blocks of the stream SpMV (k_spmv_stream)
     int32_t spmv_blocks = 0;
     void *ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // transposed solves (built at the first one): per level the small fronts and the tasks of the big ones, A^T as CSR through a
+    // map into d_vals, a workspace of its own (the tagged words of d_work stay as the ordinary pass pair left them)
+    struct TrLevel {
+        int32_t small_off = 0, small_cnt = 0, asm_off = 0, asm_cnt = 0, gf_off = 0, gf_cnt = 0, ga_off = 0, ga_cnt = 0, gb_off = 0, gb_cnt = 0;
+        int32_t small_pmax = 1, small_fmax = 1; // largest p / f of the level's small fronts (their LDS panels)
+    };
+    std::vector<TrLevel> tr_levels;
+    bool tr_ready = false;
+    int32_t *d_tr_list = nullptr, *d_ttptr = nullptr, *d_ttrow = nullptr, *d_ttmap = nullptr;
+    SolveTask *d_tr_tasks = nullptr;
+    double *d_work_t = nullptr, *d_tvec = nullptr; // d_tvec: six n-vectors (b, x, xp, r, v, z)
+    double *d_anl = nullptr;                       // error analysis: twelve n-vectors + reduction words (allocated at its first option-1/2 call)
+    unsigned long long *d_tnrm = nullptr;
+    double *h_tnrm = nullptr;
+    int32_t tr_prepare();
+    int32_t run_transposed(double *xp);
+    int32_t tr_core(double *x, const double *b, int32_t nstep, double *omega, int32_t *steps);
+    int32_t tr_pass(double *y, const double *v); // y = A^{-T} v on the device, one unrefined pass pair
+    int32_t tr_spmv(double *y, const double *x); // y = A^T x on the device
+    int32_t tr_release();
 };
 
 } // namespace hipmf

@@ -180,6 +180,7 @@ def _L():
         "rh_clinsolver_free": (None, [vp]),
         "rh_clinsolver_factorize": (cp, [vp, vp, pp(_RhParams)]),
         "rh_clinsolver_solve": (cp, [vp, vp, i64, vp, i64, i32]),
+        "rh_clinsolver_solve_transpose": (cp, [vp, vp, i64, vp, i64, i32, i32]),
         "rh_clinsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(f64), pp(i32)]),
         "rh_error_string": (cp, [i32]),
         "rh_format_nanoseconds": (None, [C.c_uint64, C.c_char_p, i32]),
@@ -601,6 +602,17 @@ class _ComplexActual:
         nx = r.size if x is None else 2 * len(x)
         out = np.zeros(nx)
         _check(_L().rh_clinsolver_solve(self._h, _ptr(out), out.size, _ptr(r), r.size, int(verbose)))
+        z = out.view(np.complex128)
+        if x is not None:
+            x[:] = z
+        return z
+
+    def solve_transpose(self, rhs, conjugate=False, x=None, verbose=False):
+        """A^T x = rhs, or A^H x = rhs with conjugate=True, with the factor of A (an extension of the reference's trait)."""
+        r = np.ascontiguousarray(np.asarray(rhs, dtype=np.complex128)).view(np.float64)
+        nx = r.size if x is None else 2 * len(x)
+        out = np.zeros(nx)
+        _check(_L().rh_clinsolver_solve_transpose(self._h, _ptr(out), out.size, _ptr(r), r.size, int(bool(conjugate)), int(verbose)))
         z = out.view(np.complex128)
         if x is not None:
             x[:] = z
