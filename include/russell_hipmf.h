@@ -235,7 +235,7 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
                                              leaves |b - A x|_2 > 1e-13 |b|_2 is finished by flexible GMRES preconditioned with the factorisation
                                              (rank(E) + 1 steps in exact arithmetic); 0: not needed.  HIPMF_KRYLOV=0 switches it off */
 #define HIPMF_COUNTER_TRANSPOSED_SOLVES 20 /* right-hand sides solved with A^T (solver_hipmf_solve_transpose / _device; the complex twin's A^T / A^H) */
-#define HIPMF_COUNTER_ANALYSIS_SOLVES 21   /* pass pairs the condition estimates of the last solver_hipmf_solve_with_error_analysis took (at most 22) */
+#define HIPMF_COUNTER_ANALYSIS_SOLVES 21   /* pass pairs the condition estimates of the last solver_hipmf_solve_with_error_analysis (complex: _solve_with_error_analysis) took (at most 22) */
 #define HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS 22 /* steps of the Krylov rescue (A^T as the operator, the transposed pass pair as the preconditioner)
                                                         in the last transposed solve; HIPMF_COUNTER_KRYLOV_ITERATIONS stays the last ordinary solve's */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
@@ -334,6 +334,20 @@ int32_t complex_solver_hipmf_get_determinant(struct InterfaceComplexHIPMF *solve
 int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, C_BOOL verbose);
 /* conjugate: 1 -> A^H x = b, 0 -> A^T x = b (the real transposed solve of the real-equivalent system; umfpack_zi_solve's UMFPACK_Aat / UMFPACK_At) */
 int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose);
+/* Solves exactly as complex_solver_hipmf_solve (the same x, bit for bit), then the error analysis of solver_hipmf_solve_with_error_analysis
+ * for the complex system (the argument shape of complex_solver_mumps_solve; RINFOG(4..11) of zmumps_c, interface_complex_mumps.c:243-280,
+ * read by complex_solver_mumps.rs:262-268,429-436).  x, rhs: interleaved complex vectors of length 2 n.  |.| is the complex MODULUS
+ * (hypot), n the complex order; a complex-symmetric handle (lower triangle) is analysed with the full matrix.  With
+ * a_i = sum_j |a_ij|, N_A = max a_i, N_x = max |x_i|, r = b - A x, d_i = (|A||x|)_i + |b_i|, tau_i = 1000 n eps (a_i N_x + |b_i|),
+ * I1 = {i : d_i > tau_i}, I2 the rest, the real weights w1 = d on I1, w2 = (|A||x|) + a N_x on I2 (zeros elsewhere):
+ *   [0] N_A  [1] N_x  [2] |r|_inf / (N_A N_x)  [3] omega1 = max_I1 |r_i| / d_i  [4] omega2 = max_I2 |r_i| / ((|A||x|)_i + a_i N_x)
+ *   [5] omega1 cond1 + omega2 cond2  [6] cond1 = est| |A^{-1}| w1 |_inf / N_x  [7] cond2 = est| |A^{-1}| w2 |_inf / N_x
+ *   (| |A^{-1}| w |_inf = |C|_1, C = diag(w) A^{-H}, by LAPACK zlacn2's iteration: complex signs z / |z| (1 where |z| <= DBL_MIN), no
+ *   repeated-sign test, at most 5 iterations + the real alternating vector; the larger of two successive iterates is kept.  At most 22
+ *   unrefined pass pairs of the real-equivalent system, HIPMF_COUNTER_ANALYSIS_SOLVES.)  The statistics of the solve are left as it set them.
+ * error_analysis_option: 0 none (array untouched), 1 all eight entries, 2 entries 0 - 4; ERROR_HIPMF_INVALID_VALUE for any other. */
+int32_t complex_solver_hipmf_solve_with_error_analysis(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, double *error_analysis_array_len_8,
+                                                       int32_t error_analysis_option, C_BOOL verbose);
 int32_t complex_solver_hipmf_set_value_map(struct InterfaceComplexHIPMF *solver, int32_t nnz_in, const int32_t *seg_ptr, const int32_t *seg_idx);
 int32_t complex_solver_hipmf_factorize_mapped(struct InterfaceComplexHIPMF *solver, int32_t *effective_ordering, int32_t *effective_scaling,
                                               int32_t *num_perturbed_pivots, double *rcond_estimate, C_BOOL verbose, const double *input_values);

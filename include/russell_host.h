@@ -98,6 +98,9 @@ const char *rh_clinsolver_solve(void *solver, double *x, int64_t nx, const doubl
 const char *rh_clinsolver_solve_transpose(void *solver, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t conjugate, int32_t verbose);
 /* determinant = (det_re + i det_im) x 10^det_exp (LinSolParams.compute_determinant; complex_solver_umfpack.rs:411-414) */
 void rh_clinsolver_outputs(void *solver, double *det_re, double *det_im, double *det_exp, double *rcond, int32_t *npert);
+/* the eight values of mumps_stats (RINFOG(4..11)) of the last solve when LinSolParams.compute_error_estimates (entries 0 - 4) or
+ * compute_condition_numbers (all eight) was set at factorize; zeros otherwise (complex_solver_mumps.rs:429-436) */
+void rh_clinsolver_mumps_stats(void *solver, double *out);
 
 void *rh_linsolver_new(int32_t genie, const char **err);
 void rh_linsolver_free(void *solver);

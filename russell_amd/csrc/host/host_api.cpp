@@ -742,6 +742,7 @@ struct Backend {
     decltype(&solver_hipmf_solve_transpose) solve_t = nullptr;
     decltype(&solver_hipmf_solve_with_error_analysis) solve_ea = nullptr;
     decltype(&complex_solver_hipmf_solve_transpose) zsolve_t = nullptr;
+    decltype(&complex_solver_hipmf_solve_with_error_analysis) zsolve_ea = nullptr;
     decltype(&solver_hipmf_solve_many) solve_many = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
     decltype(&solver_hipmf_factorize_mapped) factorize_mapped = nullptr;
@@ -796,6 +797,7 @@ bool load_backend() {
     BIND(solve_t, "solver_hipmf_solve_transpose")
     BIND(solve_ea, "solver_hipmf_solve_with_error_analysis")
     BIND(zsolve_t, "complex_solver_hipmf_solve_transpose")
+    BIND(zsolve_ea, "complex_solver_hipmf_solve_with_error_analysis")
     BIND(solve_many, "solver_hipmf_solve_many")
     BIND(set_value_map, "solver_hipmf_set_value_map")
     BIND(factorize_mapped, "solver_hipmf_factorize_mapped")
@@ -1171,6 +1173,8 @@ StrError ComplexSolverHIPMF::factorize(const ComplexCooMatrix &mat, const LinSol
         initialized_nnz = mat.nnz;
         initialized = true;
     }
+    // error analysis option (complex_solver_mumps.rs:262-268; a repeat call without params: 0, as there)
+    error_analysis_option = par.compute_condition_numbers ? 1 : (par.compute_error_estimates ? 2 : 0);
     // the value map belongs to the triplet order it was built from (the reference re-reads the indices on every call)
     if (value_map_set && (std::memcmp(map_i.data(), mat.indices_i.data(), sizeof(int32_t) * mat.nnz) != 0 ||
                           std::memcmp(map_j.data(), mat.indices_j.data(), sizeof(int32_t) * mat.nnz) != 0)) {
@@ -1218,7 +1222,10 @@ StrError ComplexSolverHIPMF::solve(std::vector<double> &x, const std::vector<dou
     if (x.size() != 2 * initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
     if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.zsolve((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), verbose ? 1 : 0);
+    int32_t status = error_analysis_option == 0
+                         ? g_backend.zsolve((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), verbose ? 1 : 0)
+                         : g_backend.zsolve_ea((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), error_analysis_array_len_8, error_analysis_option,
+                                               verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1249,6 +1256,7 @@ void ComplexSolverHIPMF::update_stats(StatsLinSol &stats) const {
     stats.perturbed_pivots = perturbed_pivots;
     stats.effective_matching = effective_matching ? "MaxProdScaled" : "None";
     stats.effective_pivoting = "LocalBlock";
+    for (int k = 0; k < 8; k++) stats.mumps_stats[k] = error_analysis_array_len_8[k]; // (complex_solver_mumps.rs:429-436)
 }
 
 StrError SolverHIPMF::solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs) {
@@ -1740,6 +1748,10 @@ const char *rh_clinsolver_solve(void *h, double *x, int64_t nx, const double *rh
     return e;
 }
 
+void rh_clinsolver_mumps_stats(void *h, double *out) {
+    const ComplexSolverHIPMF &s = *((RhComplexSolver *)h)->s;
+    for (int k = 0; k < 8; k++) out[k] = s.error_analysis_array_len_8[k];
+}
 void rh_clinsolver_outputs(void *h, double *det_re, double *det_im, double *det_exp, double *rcond, int32_t *npert) {
     RhComplexSolver *s = (RhComplexSolver *)h;
     s->s->get_determinant(*det_re, *det_im, *det_exp);

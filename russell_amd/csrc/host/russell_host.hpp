@@ -263,6 +263,11 @@ class ComplexSolverHIPMF {
     StrError solve(std::vector<double> &x, const std::vector<double> &rhs, bool verbose);
     // extension: A^T x = rhs (conjugate = false) or A^H x = rhs (conjugate = true)
     StrError solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool conjugate, bool verbose);
+    // complex_solver_mumps.rs:262-268: compute_condition_numbers -> 1 (all eight values), compute_error_estimates -> 2 (entries 0 - 4),
+    // else 0, set by every factorize; solve then goes through complex_solver_hipmf_solve_with_error_analysis, and update_stats fills
+    // mumps_stats (complex_solver_mumps.rs:429-436)
+    int32_t error_analysis_option = 0;
+    double error_analysis_array_len_8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool factorized = false;
     void update_stats(StatsLinSol &stats) const; // complex_lin_solver.rs:12-104 (ComplexLinSolTrait::update_stats)
     uint64_t get_ns_init() const { return time_initialize_ns; }

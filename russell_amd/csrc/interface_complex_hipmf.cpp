@@ -37,6 +37,7 @@ struct InterfaceComplexHIPMF {
     std::vector<int8_t> src_code;
     int32_t effective_ordering = 0;
     bool triplet_map = false; // the installed map reads the caller's COO triplets (complex_solver_hipmf_set_value_map)
+    int8_t pairs_state = 0;   // the pairing the complex error analysis relies on: 0 not checked yet, 1 holds, -1 broken
 };
 
 // No C++ exception crosses the C boundary (the same rule as interface_hipmf.cpp): a failed host allocation comes back as ERROR_MALLOC
@@ -300,6 +301,44 @@ int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *h, do
     });
 }
 
+// The complex error analysis (k_zea_rows) reads complex row i from row 2i of the real-equivalent CSR alone: stored entry (i, j) is the
+// adjacent pair (column 2j: +Re a_ij, column 2j+1: -Im a_ij).  build_real_equivalent always writes both, even where Im a_ij = 0, and the
+// solver keeps the pattern it was given; checked once per handle on the device's copy of the pattern and against the value map.
+static int32_t check_pairs(struct InterfaceComplexHIPMF *h) {
+    if (h->pairs_state == 0) {
+        std::vector<int32_t> rp, ci;
+        const int32_t code = h->solver.download_pattern(rp, ci);
+        if (code != SUCCESSFUL_EXIT) return code;
+        bool ok = rp.size() == (size_t)2 * h->n + 1 && ci.size() == h->src_code.size();
+        for (int32_t i = 0; ok && i < h->n; i++)
+            for (int32_t q = rp[(size_t)2 * i]; ok && q < rp[(size_t)2 * i + 1]; q += 2)
+                ok = q + 1 < rp[(size_t)2 * i + 1] && (ci[(size_t)q] & 1) == 0 && ci[(size_t)q + 1] == ci[(size_t)q] + 1 && h->src_code[(size_t)q] == 0 &&
+                     h->src_code[(size_t)q + 1] == 1 && h->src_entry[(size_t)q] == h->src_entry[(size_t)q + 1];
+        h->pairs_state = ok ? 1 : -1;
+    }
+    if (h->pairs_state > 0) return SUCCESSFUL_EXIT;
+    h->solver.last_error = "internal error: the real-equivalent rows 2i do not hold complex entries as adjacent (re, -im) pairs";
+    return ERROR_HIPMF_SYMBOLIC;
+}
+
+// Solve exactly as complex_solver_hipmf_solve does (the same x, bit for bit), then analyse x against A and b with complex moduli
+// (Solver::error_analysis_complex): the argument shape of complex_solver_mumps_solve, whose RINFOG(4..11) the reference copies out of
+// zmumps_c (interface_complex_mumps.c:243-280, complex_solver_mumps.rs:429-436).  error_analysis_option: 0 none (the array is not
+// touched), 1 all eight values, 2 entries 0 - 4.
+int32_t complex_solver_hipmf_solve_with_error_analysis(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, double *error_analysis_array_len_8,
+                                                       int32_t error_analysis_option, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h || !x || !rhs || !error_analysis_array_len_8) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (error_analysis_option < 0 || error_analysis_option > 2) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        int32_t code = error_analysis_option == 0 ? (int32_t)SUCCESSFUL_EXIT : check_pairs(h);
+        if (code != SUCCESSFUL_EXIT) return code;
+        code = c_solve_body(h, x, rhs, verbose);
+        if (code != SUCCESSFUL_EXIT) return code;
+        return h->solver.error_analysis_complex(x, rhs, error_analysis_array_len_8, error_analysis_option);
+    });
+}
+
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *h) { return h ? h->solver.last_error.c_str() : "null solver"; }
 
 static int32_t c_get_stats_body(struct InterfaceComplexHIPMF *h, int64_t *is, double *ds) {
@@ -337,6 +376,10 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_WAVE_FRONTS: return s.wave_front_count;
     case HIPMF_COUNTER_LEAF_FRONTS: return s.leaf_front_count();
     case HIPMF_COUNTER_SPLIT_SLABS: return s.split_slab_count();
+    case HIPMF_COUNTER_KRYLOV_ITERATIONS: return s.krylov_iterations;
+    case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
+    case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
+    case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
     default: return -1;
     }
 }

@@ -17,6 +17,7 @@
 
 #include "kernels.hpp"
 #include "kernels_solve_transpose.hpp"
+#include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <pthread.h>
@@ -4004,6 +4005,155 @@ int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *ou
     last_omega = keep_omega, last_residual_inf = keep_res, krylov_last_relres = keep_relres, col_omega = keep_col, times = keep_times;
     refinement_steps_done = keep_steps, opt.refinement_nstep = keep_nstep, krylov_iterations = keep_kry, opt.verbose = keep_verbose;
     if (code != SUCCESSFUL_EXIT) return code;
+    const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
+    out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> &ci) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    DeviceScope dev_scope(device);
+    rp.resize((size_t)S.n + 1), ci.resize((size_t)S.nnz_a);
+    HIPC(hipMemcpy(rp.data(), d_rp, sizeof(int32_t) * ((size_t)S.n + 1), hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    if (S.nnz_a > 0) HIPC(hipMemcpy(ci.data(), d_ci, sizeof(int32_t) * (size_t)S.nnz_a, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    return SUCCESSFUL_EXIT;
+}
+
+// ---- error analysis of the complex twin (complex_solver_hipmf_solve_with_error_analysis) ----
+// This handle holds the real-equivalent system of order n = 2 nc; xbar and rhs are interleaved complex vectors.  The definitions are the
+// real ones with |.| the complex modulus (include/russell_hipmf.h); the real analysis of the 2n system would sum |Re| + |Im| instead.
+// | |A^{-1}| w |_inf = |C|_1 with C = diag(w) A^{-H}: C v = w o (A^{-H} v) is one transposed pass pair of the 2n system (its transpose
+// IS the real-equivalent form of A^H), C^H v = A^{-1} (w o v) one ordinary pass pair, both unrefined.  The iteration is LAPACK zlacn2's:
+// the complex sign z / |z|, no repeat test of the sign vector, at most 5 iterations + the real alternating vector, i.e. at most 11 pass
+// pairs per estimate; the one liberty of the real path is kept (the larger of two successive iterates).  Vector steps on the device,
+// fixed-order reductions, only scalars come to the host.
+int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, double *out, int32_t option) {
+    if (option == 0) return SUCCESSFUL_EXIT;
+    if (S.sym_mode || d_tptr || (S.n & 1)) return ERROR_HIPMF_INVALID_VALUE; // (not a real-equivalent handle)
+    DeviceScope dev_scope(device);
+    int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    const int32_t n = S.n, nc = n / 2;
+    const size_t nb = sizeof(double) * (size_t)n;
+    const dim3 g((nc + 255) / 256), b(256);
+    // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t (complex vectors n doubles, ax .. w2 nc doubles), partials, scalars:
+    // the buffer of the real analysis (12 n doubles + the reduction words), allocated the same way
+    if (!d_anl) HIPC(hipMalloc((void **)&d_anl, nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
+    double *X = d_anl, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + nc, *W1 = AR + nc, *W2 = W1 + nc, *V = W2 + nc, *Y = V + n, *Z = Y + n,
+           *XI = Z + n, *T = XI + n;
+    double *pv = d_anl + 12 * (size_t)n, *sv = pv + EA_RED_WG;
+    unsigned long long *sc = (unsigned long long *)sv; // 8 words: maxima (bits), then the reduction results
+    int32_t *pi = (int32_t *)(sv + 8), *si = pi + EA_RED_WG;
+    HIPC(hipMemcpyAsync(X, xbar, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(B, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(sv, 0, sizeof(double) * 8 + sizeof(int32_t) * (EA_RED_WG + 8), STREAM), ERROR_HIP_MEMCPY);
+    hipLaunchKernelGGL(k_zea_rows, g, b, 0, STREAM, nc, d_rp, d_ci, d_vals, (const double *)X, (const double *)B, R, AX, AR, sc);
+    double h[8];
+    HIPC(hipMemcpyAsync(h, sc, sizeof(double) * 3, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    const double NA = h[0], NX = h[1], RN = h[2];
+    const double tau_scale = 1000.0 * (double)nc * 2.220446049250313e-16;
+    hipLaunchKernelGGL(k_zea_split, g, b, 0, STREAM, nc, tau_scale, NX, (const double *)R, (const double *)AX, (const double *)AR, (const double *)B, W1, W2, sc, si);
+    int32_t n2 = 0;
+    HIPC(hipMemcpyAsync(h + 3, sc + 3, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(&n2, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    const double om1 = h[3], om2 = h[4];
+    out[0] = NA, out[1] = NX, out[2] = (NA * NX > 0.0) ? RN / (NA * NX) : 0.0, out[3] = om1, out[4] = om2;
+    analysis_solves = 0;
+    if (option != 1) return SUCCESSFUL_EXIT;
+
+    // the statistics of the caller's solve stay as that solve left them
+    const double keep_omega = last_omega, keep_res = last_residual_inf, keep_relres = krylov_last_relres;
+    const std::vector<double> keep_col = col_omega;
+    const PhaseTimes keep_times = times;
+    const int32_t keep_steps = refinement_steps_done, keep_nstep = opt.refinement_nstep;
+    const int64_t keep_kry = krylov_iterations;
+    const bool keep_verbose = opt.verbose;
+    // sum |v_i| (mode 0) or max |v_i| and its first index (mode 1) over the moduli; with jprev >= 0 also |v_jprev| (same arithmetic)
+    auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) -> int32_t {
+        hipLaunchKernelGGL(k_zea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, nc, mode, v, pv, pi);
+        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, STREAM, mode, (const double *)pv, (const int32_t *)pi, (double *)(sc + 5), si);
+        if (jprev >= 0) hipLaunchKernelGGL(k_zea_abs_at, dim3(1), dim3(64), 0, STREAM, v, jprev, (double *)(sc + 6));
+        double t[2] = {0.0, 0.0};
+        int32_t ti = 0;
+        HIPC(hipMemcpyAsync(t, sc + 5, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipMemcpyAsync(&ti, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        *val = t[0];
+        if (idx) *idx = ti;
+        if (vprev) *vprev = t[1];
+        return SUCCESSFUL_EXIT;
+    };
+    auto inv = [&](double *y, const double *v) -> int32_t { // y = A^{-1} v, one unrefined ordinary pass pair
+        opt.refinement_nstep = 0, opt.verbose = false;
+        const bool keep_rescue = in_rescue;
+        in_rescue = true; // (no Krylov rescue inside)
+        const int32_t c = solve_core(y, v, 1, n, true);
+        in_rescue = keep_rescue;
+        analysis_solves++;
+        return c;
+    };
+    auto inv_h = [&](double *y, const double *v) -> int32_t { // y = A^{-H} v: the transposed pass pair of the 2n system
+        const int32_t c = tr_pass(y, v);
+        analysis_solves++;
+        return c;
+    };
+    // C v and C^H v of C = diag(w) A^{-H}
+    auto cmul = [&](const double *w, double *y, const double *v) -> int32_t {
+        int32_t c = inv_h(T, v);
+        if (c != SUCCESSFUL_EXIT) return c;
+        hipLaunchKernelGGL(k_zea_hadamard, g, b, 0, STREAM, nc, w, (const double *)T, y);
+        return SUCCESSFUL_EXIT;
+    };
+    auto chmul = [&](const double *w, double *z, const double *v) -> int32_t {
+        hipLaunchKernelGGL(k_zea_hadamard, g, b, 0, STREAM, nc, w, v, T);
+        return inv(z, T);
+    };
+    auto estimate = [&](const double *w, double *est) -> int32_t {
+        int32_t c;
+        hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 0, 0, V);
+        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+        if (nc == 1) {
+            int32_t j0;
+            return reduce(Y, 1, est, &j0, -1, nullptr);
+        }
+        if ((c = reduce(Y, 0, est, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+        hipLaunchKernelGGL(k_zea_sign, g, b, 0, STREAM, nc, (const double *)Y, XI);
+        if ((c = chmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
+        double zmax = 0.0;
+        int32_t j = 0;
+        if ((c = reduce(Z, 1, &zmax, &j, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+        for (int32_t iter = 2;; iter++) {
+            hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 2, j, V);
+            if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+            const double estold = *est;
+            double e = 0.0;
+            if ((c = reduce(Y, 0, &e, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+            *est = std::max(e, estold);
+            if (e <= estold) break; // no growth (zlacn2 has no repeated-sign test)
+            hipLaunchKernelGGL(k_zea_sign, g, b, 0, STREAM, nc, (const double *)Y, XI);
+            if ((c = chmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
+            double zjlast = 0.0;
+            if ((c = reduce(Z, 1, &zmax, &j, j, &zjlast)) != SUCCESSFUL_EXIT) return c;
+            if (!(zjlast != zmax && iter < 5)) break;
+        }
+        hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 1, 0, V);
+        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+        double e = 0.0;
+        if ((c = reduce(Y, 0, &e, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+        const double temp = 2.0 * (e / (3.0 * (double)nc));
+        if (temp > *est) *est = temp;
+        return SUCCESSFUL_EXIT;
+    };
+    double e1 = 0.0, e2 = 0.0;
+    if (nc - n2 > 0) code = estimate(W1, &e1);
+    if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
+    last_omega = keep_omega, last_residual_inf = keep_res, krylov_last_relres = keep_relres, col_omega = keep_col, times = keep_times;
+    refinement_steps_done = keep_steps, opt.refinement_nstep = keep_nstep, krylov_iterations = keep_kry, opt.verbose = keep_verbose;
+    if (code != SUCCESSFUL_EXIT) return code;
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
     out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
     return SUCCESSFUL_EXIT;

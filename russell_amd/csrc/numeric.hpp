@@ -137,6 +137,10 @@ class Solver {
     int32_t solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs = false);
     // MUMPS-style error analysis of a solution xbar of A x = b (host vectors; option 1: all eight values, 2: entries 0 - 4), see numeric.cpp
     int32_t error_analysis(const double *xbar, const double *rhs, double *out, int32_t option);
+    // the same for the complex twin: this handle holds the real-equivalent system of order 2 nc, xbar / rhs are interleaved complex vectors
+    // (kernels_error_analysis_complex.hpp; the caller has checked the pairing of the even rows), see numeric.cpp
+    int32_t error_analysis_complex(const double *xbar, const double *rhs, double *out, int32_t option);
+    int32_t download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> &ci); // host copies of the stored CSR pattern of A
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
     int64_t krylov_iterations_t = 0; // FGMRES steps of the last transposed solve (krylov_iterations / krylov_last_relres stay the ordinary solve's)

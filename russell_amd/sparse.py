@@ -182,6 +182,7 @@ def _L():
         "rh_clinsolver_solve": (cp, [vp, vp, i64, vp, i64, i32]),
         "rh_clinsolver_solve_transpose": (cp, [vp, vp, i64, vp, i64, i32, i32]),
         "rh_clinsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(f64), pp(i32)]),
+        "rh_clinsolver_mumps_stats": (None, [vp, vp]),
         "rh_error_string": (cp, [i32]),
         "rh_format_nanoseconds": (None, [C.c_uint64, C.c_char_p, i32]),
         "rh_is_memory_error": (i32, [cp]),
@@ -623,6 +624,14 @@ class _ComplexActual:
         dr, di, de, rc, npv = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int32()
         _L().rh_clinsolver_outputs(self._h, C.byref(dr), C.byref(di), C.byref(de), C.byref(rc), C.byref(npv))
         return dict(determinant_coefficient=complex(dr.value, di.value), determinant_exponent=de.value, rcond_estimate=rc.value, perturbed_pivots=npv.value)
+
+    def mumps_stats(self):
+        """the eight MUMPS-style values of the last solve (RINFOG(4..11): inf_norm_a, inf_norm_x, scaled_residual, omega1, omega2,
+        normalized_delta_x, condition_number1, condition_number2) when LinSolParams.compute_error_estimates / compute_condition_numbers
+        was set at factorize (complex_solver_mumps.rs:429-436); zeros otherwise"""
+        out = np.zeros(8)
+        _L().rh_clinsolver_mumps_stats(self._h, _ptr(out))
+        return out
 
 
 class ComplexLinSolver:
