@@ -107,7 +107,7 @@ def test_rccl_broadcast_and_sharded_solve_two_gpus(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_distributed_branch_with_one_rank():
-    """bench.py's many-RHS section under BENCH_FORCE_DIST=1: a torch `nccl` (= RCCL) process group of ONE rank drives the same code as
+    """bench.py --full's many-RHS section under BENCH_FORCE_DIST=1: a torch `nccl` (= RCCL) process group of ONE rank drives the same code as
     `--gpus N` -- unique id through the group, hipmf_comm_init_rank, solver_hipmf_broadcast_factor (plan check, MIN all-reduce,
     ncclBroadcast of the factor parts), the sharded solve -- with nranks as data.  What a node with N GPUs adds is ranks, not code."""
     import json
@@ -118,7 +118,7 @@ def test_bench_distributed_branch_with_one_rank():
         port = sk.getsockname()[1]
     env = dict(os.environ, BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--grid", "300",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--grid", "300",
                         "--nrhs", "32", "--grid3d", "0"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

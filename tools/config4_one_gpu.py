@@ -2,7 +2,7 @@
 """BASELINE config 4 on ONE GPU: 3D 7-point Poisson N^3 (default 200^3 = 8 M unknowns), handed over as its lower triangle
 (general_symmetric -> L D L^T on the tiled fronts), NRHS right-hand sides (default 256) resident in HBM, blocked solves.
 
-usage: python tools/config4_one_gpu.py [N [NRHS]]       (the 8-GPU split of the same job is bench.py --gpus 8 / many_rhs_multi_gpu.py)
+usage: python tools/config4_one_gpu.py [N [NRHS]]       (the 8-GPU split of the same job is bench.py --gpus 8 --full / many_rhs_multi_gpu.py)
 """
 import json
 import os

@@ -1,4 +1,4 @@
-"""Repeat call through the mirror of LinSolTrait with HOST pointers (the `host_api` section of bench.py alone): python tools/host_boundary.py [N]."""
+"""Repeat call through the mirror of LinSolTrait with HOST pointers (the `host_api` section of bench.py --full alone): python tools/host_boundary.py [N]."""
 import sys
 import time
 

@@ -5,7 +5,7 @@ The x 2 on FETCH_SIZE is the gfx950 correction of /opt/skills/guides/MI355X_MICR
 tools/microbench/fetch_calib.hip (profiles/r04_fetch_calib.txt: the counter moves 64 bytes per 128-byte line for every shape).
 The file is STAMPED with the factor the counters were taken on (nnz(L), nnz(U), supernodes, solve launches: the `factor` object and
 roofline of the bench line of the SAME build): bench.py refuses a traffic figure whose stamp does not match the build it is timing.
-usage: sptrsv_traffic.py <pmc_hbm.txt> <pass pairs per timed step> <algorithmic bytes> <physical bytes> <source label> [<bench.json of the same build>]"""
+usage: sptrsv_traffic.py <pmc_hbm.txt> <pass pairs per timed step> <algorithmic bytes> <physical bytes> <source label> [<bench.py --full line of the same build>]"""
 import json
 import re
 import sys
