@@ -21,10 +21,15 @@
 #include <cstdint>
 #include <cstdio>
 #include <new>
+#include <utility>
+
+#include "device_owner.hpp"
 
 #include "../../include/russell_hipmf.h"
 
 namespace {
+
+using hipmf::DeviceArray;
 
 constexpr int FDM_T = 256;
 
@@ -217,13 +222,13 @@ __global__ void __launch_bounds__(FDM_T) k_fdm_lmm_fill(FdmGrid g, const uint8_t
 }
 
 struct FdmHandle {
-    int64_t *d_off_all = nullptr; // Lagrange-multiplier form: offsets of every node's molecule (built at the first hipmf_fdm_lmm_* call)
+    DeviceArray<int64_t> d_off_all; // Lagrange-multiplier form: offsets of every node's molecule (built at the first hipmf_fdm_lmm_* call)
     int64_t nnz_k_all = 0;
     FdmGrid g;
     int64_t ntot = 0, totals[4] = {0, 0, 0, 0}; // nu, np, nnz(K-bar), nnz(K-check)
-    uint8_t *d_presc = nullptr;
-    int32_t *d_local = nullptr;
-    int64_t *d_off_bar = nullptr, *d_off_chk = nullptr;
+    DeviceArray<uint8_t> d_presc;
+    DeviceArray<int32_t> d_local;
+    DeviceArray<int64_t> d_off_bar, d_off_chk;
     int device = 0;
 };
 
@@ -243,11 +248,6 @@ struct FdmDeviceScope {
 void fdm_free(FdmHandle *h) {
     if (!h) return;
     FdmDeviceScope scope(h->device);
-    if (h->d_presc) (void)hipFree(h->d_presc);
-    if (h->d_local) (void)hipFree(h->d_local);
-    if (h->d_off_bar) (void)hipFree(h->d_off_bar);
-    if (h->d_off_chk) (void)hipFree(h->d_off_chk);
-    if (h->d_off_all) (void)hipFree(h->d_off_all);
     delete h;
 }
 
@@ -256,13 +256,13 @@ int32_t fdm_ensure_lmm(FdmHandle *h) {
     if (h->d_off_all) return 0;
     if ((int64_t)h->ntot + h->totals[1] > 0x7fffffffLL) return 803; // rows neq + ip are int32 in the triplets
     const int64_t nblocks = (h->ntot + FDM_T - 1) / FDM_T;
-    int64_t *d_bsum = nullptr, *d_tot = nullptr, *d_chk = nullptr, *d_all = nullptr;
-    int32_t *d_loc = nullptr;
-    bool ok = hipMalloc((void **)&d_bsum, sizeof(int64_t) * 4 * (size_t)nblocks) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_tot, sizeof(int64_t) * 4) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_loc, sizeof(int32_t) * (size_t)h->ntot) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_chk, sizeof(int64_t) * (size_t)h->ntot) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_all, sizeof(int64_t) * (size_t)h->ntot) == hipSuccess;
+    DeviceArray<int64_t> d_bsum, d_tot, d_chk, d_all;
+    DeviceArray<int32_t> d_loc;
+    bool ok = d_bsum.alloc(4 * (size_t)nblocks) == hipSuccess;
+    ok = ok && d_tot.alloc(4) == hipSuccess;
+    ok = ok && d_loc.alloc((size_t)h->ntot) == hipSuccess;
+    ok = ok && d_chk.alloc((size_t)h->ntot) == hipSuccess;
+    ok = ok && d_all.alloc((size_t)h->ntot) == hipSuccess;
     int64_t tot[4] = {0, 0, 0, 0};
     if (ok) {
         hipLaunchKernelGGL(k_fdm_block_sums, dim3((unsigned)nblocks), dim3(FDM_T), 0, 0, h->g, (const uint8_t *)nullptr, h->ntot, d_bsum);
@@ -270,15 +270,8 @@ int32_t fdm_ensure_lmm(FdmHandle *h) {
         hipLaunchKernelGGL(k_fdm_node_offsets, dim3((unsigned)nblocks), dim3(FDM_T), 0, 0, h->g, (const uint8_t *)nullptr, h->ntot, d_bsum, d_loc, d_all, d_chk);
         ok = hipMemcpy(tot, d_tot, sizeof(int64_t) * 4, hipMemcpyDeviceToHost) == hipSuccess && hipGetLastError() == hipSuccess;
     }
-    if (d_bsum) (void)hipFree(d_bsum);
-    if (d_tot) (void)hipFree(d_tot);
-    if (d_loc) (void)hipFree(d_loc);
-    if (d_chk) (void)hipFree(d_chk);
-    if (!ok) {
-        if (d_all) (void)hipFree(d_all);
-        return 200000; // ERROR_MALLOC's neighbour on the device side would be ERROR_HIP_MALLOC; the shared code says "memory"
-    }
-    h->d_off_all = d_all;
+    if (!ok) return 200000; // ERROR_MALLOC's neighbour on the device side would be ERROR_HIP_MALLOC; the shared code says "memory"
+    h->d_off_all = std::move(d_all);
     h->nnz_k_all = tot[2];
     return 0;
 }
@@ -301,17 +294,17 @@ void *hipmf_fdm_new(int32_t nx, int32_t ny, int32_t nz, int32_t periodic_x, int3
         return nullptr;
     }
     const int64_t nblocks = (h->ntot + FDM_T - 1) / FDM_T;
-    int64_t *d_bsum = nullptr, *d_tot = nullptr;
+    DeviceArray<int64_t> d_bsum, d_tot;
     bool ok = true;
     if (prescribed) {
-        ok = ok && hipMalloc((void **)&h->d_presc, (size_t)h->ntot) == hipSuccess;
+        ok = ok && h->d_presc.alloc((size_t)h->ntot) == hipSuccess;
         ok = ok && hipMemcpy(h->d_presc, prescribed, (size_t)h->ntot, hipMemcpyHostToDevice) == hipSuccess;
     }
-    ok = ok && hipMalloc((void **)&h->d_local, sizeof(int32_t) * (size_t)h->ntot) == hipSuccess;
-    ok = ok && hipMalloc((void **)&h->d_off_bar, sizeof(int64_t) * (size_t)h->ntot) == hipSuccess;
-    ok = ok && hipMalloc((void **)&h->d_off_chk, sizeof(int64_t) * (size_t)h->ntot) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_bsum, sizeof(int64_t) * 4 * (size_t)nblocks) == hipSuccess;
-    ok = ok && hipMalloc((void **)&d_tot, sizeof(int64_t) * 4) == hipSuccess;
+    ok = ok && h->d_local.alloc((size_t)h->ntot) == hipSuccess;
+    ok = ok && h->d_off_bar.alloc((size_t)h->ntot) == hipSuccess;
+    ok = ok && h->d_off_chk.alloc((size_t)h->ntot) == hipSuccess;
+    ok = ok && d_bsum.alloc(4 * (size_t)nblocks) == hipSuccess;
+    ok = ok && d_tot.alloc(4) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_fdm_block_sums, dim3((unsigned)nblocks), dim3(FDM_T), 0, 0, h->g, h->d_presc, h->ntot, d_bsum);
         hipLaunchKernelGGL(k_fdm_scan_blocks, dim3(1), dim3(1024), 0, 0, nblocks, d_bsum, d_tot);
@@ -319,8 +312,6 @@ void *hipmf_fdm_new(int32_t nx, int32_t ny, int32_t nz, int32_t periodic_x, int3
                            h->d_off_chk);
         ok = hipMemcpy(h->totals, d_tot, sizeof(int64_t) * 4, hipMemcpyDeviceToHost) == hipSuccess && hipGetLastError() == hipSuccess;
     }
-    if (d_bsum) (void)hipFree(d_bsum);
-    if (d_tot) (void)hipFree(d_tot);
     if (!ok) {
         fdm_free(h);
         return nullptr;

@@ -40,7 +40,7 @@ struct InterfaceHIPMF {
     SymbolicOptions so_keep;
     // device words of solver_hipmf_broadcast_factor's plan check (8 x int64 header, 2 x int32 status), allocated at initialize: no rank
     // can fail an allocation between two collectives
-    int64_t *d_hdr = nullptr;
+    DeviceArray<int64_t> d_hdr;
 };
 
 // No C++ exception crosses the C boundary: a failed host allocation (the analysis of a large matrix takes gigabytes) comes back as
@@ -86,7 +86,6 @@ struct InterfaceHIPMF *solver_hipmf_new(void) {
 void solver_hipmf_drop(struct InterfaceHIPMF *h) {
     if (!h) return;
     try {
-        if (h->d_hdr) (void)hipFree(h->d_hdr);
         h->solver.release();
     } catch (...) {
     }
@@ -206,8 +205,7 @@ static int32_t initialize_body(struct InterfaceHIPMF *h, int32_t ordering, int32
     }
     if (code == SUCCESSFUL_EXIT && !h->d_hdr) {
         DeviceGuard dg(h->solver.device);
-        if (hipMalloc((void **)&h->d_hdr, sizeof(int64_t) * 8 + sizeof(int32_t) * 2) != hipSuccess) {
-            h->d_hdr = nullptr;
+        if (h->d_hdr.alloc(8 + 1) != hipSuccess) { // (the two int32 words share the last int64)
             h->solver.release();
             h->expanded = false, h->nnz_lower = 0;
             return ERROR_HIP_MALLOC;
@@ -865,16 +863,12 @@ int32_t hipmf_device_mem_info(size_t *free_bytes, size_t *total_bytes) {
 int32_t hipmf_set_device(int32_t device) { return hipSetDevice(device) == hipSuccess ? SUCCESSFUL_EXIT : ERROR_HIPMF_NO_DEVICE; }
 int32_t hipmf_device_copy_bandwidth(int64_t bytes, int32_t reps, double *gb_per_s) {
     if (!gb_per_s || bytes < 1 || reps < 1) return ERROR_NULL_POINTER;
-    void *a = nullptr, *b = nullptr;
-    hipEvent_t e0, e1;
-    if (hipMalloc(&a, (size_t)bytes) != hipSuccess) return ERROR_HIP_MALLOC;
-    if (hipMalloc(&b, (size_t)bytes) != hipSuccess) {
-        (void)hipFree(a);
-        return ERROR_HIP_MALLOC;
-    }
+    DeviceArray<char> a, b;
+    EventOwner e0, e1;
+    if (a.alloc((size_t)bytes) != hipSuccess || b.alloc((size_t)bytes) != hipSuccess) return ERROR_HIP_MALLOC;
     (void)hipMemset(a, 1, (size_t)bytes);
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    (void)hipEventCreate(e0.put());
+    (void)hipEventCreate(e1.put());
     double best = 0.0;
     for (int32_t r = 0; r <= reps; r++) { // first copy = warm-up
         (void)hipEventRecord(e0, nullptr);
@@ -885,10 +879,6 @@ int32_t hipmf_device_copy_bandwidth(int64_t bytes, int32_t reps, double *gb_per_
         (void)hipEventElapsedTime(&ms, e0, e1);
         if (r > 0 && ms > 0.0f) best = std::max(best, 2.0 * (double)bytes / (ms * 1e-3) / 1e9);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(a);
-    (void)hipFree(b);
     *gb_per_s = best;
     return SUCCESSFUL_EXIT;
 }
@@ -911,11 +901,11 @@ __global__ void __launch_bounds__(256) k_mfma_probe(double *out, int32_t iters, 
 
 int32_t hipmf_device_mfma_rate(int32_t workgroups, int32_t iters, double *tflops) {
     if (!tflops || workgroups < 1 || iters < 1) return ERROR_NULL_POINTER;
-    double *d = nullptr;
-    if (hipMalloc((void **)&d, sizeof(double) * 256 * (size_t)workgroups) != hipSuccess) return ERROR_HIP_MALLOC;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    DeviceArray<double> d;
+    if (d.alloc(256 * (size_t)workgroups) != hipSuccess) return ERROR_HIP_MALLOC;
+    EventOwner e0, e1;
+    (void)hipEventCreate(e0.put());
+    (void)hipEventCreate(e1.put());
     double best = 0.0;
     for (int r = 0; r < 3; r++) { // first launch = warm-up
         (void)hipEventRecord(e0, nullptr);
@@ -927,9 +917,6 @@ int32_t hipmf_device_mfma_rate(int32_t workgroups, int32_t iters, double *tflops
         // 4 waves x 4 accumulators x 2048 flops per MFMA and iteration
         if (r > 0 && ms > 0.0f) best = std::max(best, (double)workgroups * 4.0 * 4.0 * 2048.0 * (double)iters / (ms * 1e-3) / 1e12);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(d);
     *tflops = best;
     return hipGetLastError() == hipSuccess ? SUCCESSFUL_EXIT : ERROR_HIP_LAUNCH;
 }

@@ -57,15 +57,6 @@ struct DeviceScope {
 
 constexpr int32_t MAX_LDS_DOUBLES = 7936; // 62 KiB of dynamic LDS for the w1 / v vectors of the big-front solves
 
-template <class T, class A>
-static hipError_t dev_upload(T **dptr, const std::vector<T, A> &v) {
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    hipError_t e = hipMalloc((void **)dptr, bytes);
-    if (e != hipSuccess) return e;
-    if (!v.empty()) e = hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
-
 Solver::Solver() {}
 
 bool Solver::is_mid_lu(int32_t s) const {
@@ -82,97 +73,15 @@ bool Solver::is_mid(int32_t s) const {
 Solver::~Solver() { release(); }
 
 void Solver::release() {
-    if (!stream && !d_pool && !d_fd) return;
-    int caller_device = -1; // the caller's current device is restored on the way out
-    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
-    (void)hipSetDevice(device);
-    tr_release();
-    void *ptrs[] = {d_vs, d_vs2, d_sa_ptr, d_sa_k, d_sa_pos, d_zero, d_seg_ptr, d_seg_idx, d_vin, d_blk, d_work_blk, d_cs == d_rs ? nullptr : d_cs, matched ? d_rperm : nullptr, d_trace, d_sf, d_need, d_sync, d_dws,   d_ear,   d_fd,    d_ea,    d_st,    d_info, d_scalar, d_work, d_vals, d_xp,   d_r,    d_den,  d_b,    d_x,     d_du,   d_rows,
-                    d_rel,   d_child, d_lists, d_tasks, d_rp,    d_ci,   d_arow, d_tptr, d_tidx, d_perm, d_sc_k, d_sc_at, d_ea_sc, d_sc_pos, d_diag, d_bigfd, d_row_blk, d_dcol, d_pool, d_lperm,
-                    d_rs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (d_sd) (void)hipFree(d_sd);
-    d_sd = nullptr;
-    if (d_chain) (void)hipFree(d_chain);
-    if (d_chain_cnt) (void)hipFree(d_chain_cnt);
-    d_chain = nullptr, d_chain_cnt = nullptr, chain_words = 0;
-    for (void *p : {(void *)d_wt_hdr, (void *)d_wt_meta, (void *)d_wt_wave, (void *)d_sf2, (void *)d_need2, (void *)d_rep_idx, (void *)d_rep, (void *)d_sf3,
-                    (void *)d_need3, (void *)d_sfk, (void *)d_needk, (void *)d_leaf, (void *)d_split_scr, (void *)d_split_cnt})
-        if (p) (void)hipFree(p);
-    d_leaf = nullptr, leaf_cnt = 0;
-    d_split_scr = nullptr, d_split_cnt = nullptr, split_units = 0, split_slabs = 0;
-    d_wt_hdr = nullptr, d_wt_meta = nullptr, d_wt_wave = nullptr, d_sf2 = nullptr, d_need2 = nullptr, d_rep_idx = nullptr, d_rep = nullptr;
-    rep_words = 0;
-    d_sf3 = nullptr, d_need3 = nullptr;
-    d_sfk = nullptr, d_needk = nullptr;
-    for (void *p : {(void *)d_emap, (void *)d_vlow})
-        if (p) (void)hipFree(p);
-    d_emap = nullptr, d_vlow = nullptr, nnz_low = 0;
-    wt_waves = wt_recs = sf2_fwd_cnt = sf2_bwd_cnt = 0, tree_active = false, tag_active = false, work_up = work_arm0 = 0;
-    tags_armed = false;
-    for (LaneBuffers &lb : extra_lanes) {
-        for (void *p : {(void *)lb.blk, (void *)lb.work, (void *)lb.sync, (void *)lb.norms})
-            if (p) (void)hipFree(p);
-        if (lb.stream) (void)hipStreamDestroy((hipStream_t)lb.stream);
-    }
-    extra_lanes.clear();
-    if (h_nrm) (void)hipHostFree(h_nrm);
-    h_nrm = nullptr;
-    if (h_stage) (void)hipHostFree(h_stage);
-    h_stage = nullptr;
-    d_dws = nullptr, d_ear = nullptr;
-    d_sf = nullptr, d_need = nullptr, d_sync = nullptr, d_trace = nullptr;
-    d_cs = nullptr, d_rperm = nullptr;
-    d_blk = nullptr, d_work_blk = nullptr;
-    if (d_norms_blk) (void)hipFree(d_norms_blk);
-    d_norms_blk = nullptr;
-    block_cols = 0, block_groups = 0;
-    d_seg_ptr = d_seg_idx = nullptr, d_vin = nullptr, nnz_in = 0;
-    d_sa_ptr = d_sa_k = nullptr, d_sa_pos = nullptr, d_zero = nullptr, zero_cnt = 0;
-    d_vs = d_vs2 = nullptr;
-    matched = false;
-    d_fd = nullptr, d_ea = nullptr, d_st = nullptr, d_info = nullptr, d_scalar = nullptr;
-    d_work = d_vals = d_xp = d_r = d_den = d_b = d_x = d_du = d_pool = d_rs = nullptr;
-    d_rows = d_rel = d_child = d_lists = d_tasks = d_rp = d_ci = d_arow = d_tptr = d_tidx = d_perm = d_lperm = nullptr;
-    d_sc_k = nullptr, d_sc_at = nullptr, d_ea_sc = nullptr, d_sc_pos = nullptr, d_diag = nullptr, d_bigfd = nullptr, d_row_blk = nullptr, d_dcol = nullptr;
-    for (auto &e : ev)
-        if (e) {
-            (void)hipEventDestroy((hipEvent_t)e);
-            e = nullptr;
-        }
-    if (stream) {
-        (void)hipStreamDestroy(STREAM);
-        stream = nullptr;
-    }
-    if (stream2) {
-        (void)hipStreamDestroy((hipStream_t)stream2);
-        stream2 = nullptr;
-    }
-#ifndef HIPMF_EMULATED
-    if (factor_graph) (void)hipGraphExecDestroy((hipGraphExec_t)factor_graph);
-#endif
-    factor_graph = nullptr, graph_launches = 0;
-    if (stream3) {
-        (void)hipStreamDestroy((hipStream_t)stream3);
-        stream3 = nullptr;
-    }
-    if (stream4) {
-        (void)hipStreamDestroy((hipStream_t)stream4);
-        stream4 = nullptr;
-    }
-    for (void **e : {&ev_fork, &ev_join, &ev_fork3, &ev_join3, &ev_pb, &ev_rest, &ev_pre0, &ev_pre1})
-        if (*e) {
-            (void)hipEventDestroy((hipEvent_t)*e);
-            *e = nullptr;
-        }
-    initialized = factorized = false;
+    DeviceScope dev_scope(device);
+    static_cast<SolverDevice &>(*this) = SolverDevice();
+    initialized = factorized = false, matched = false;
+    tree_active = tag_active = tags_armed = false, work_up = work_arm0 = 0;
     // (a hand-off time-out sends ONE analysis to the level-set launches -- the next initialize of this handle starts over with the
     //  dependency-driven solves; HIPMF_FUSED_SOLVE=0 is read again there)
     use_fused = true;
     sym_diag_looked = sym_weak_diag_seen = false;
     block_groups_last = 0;
-    if (caller_device >= 0 && caller_device != device) (void)hipSetDevice(caller_device);
 }
 
 int32_t Solver::initialize(int32_t n, const int32_t *rp, const int32_t *ci, bool sym_lower, const SymbolicOptions &sopt,
@@ -228,21 +137,16 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
     auto prep = [&]() -> int32_t {
         (void)hipSetDevice(device);
         if (!stream) {
-            hipStream_t st;
-            HIPC(hipStreamCreate(&st), ERROR_HIPMF_NO_DEVICE);
-            stream = st;
-            HIPC(hipStreamCreate(&st), ERROR_HIPMF_NO_DEVICE);
-            stream2 = st;
-            HIPC(hipStreamCreate(&st), ERROR_HIPMF_NO_DEVICE);
-            stream3 = st;
+            HIPC(hipStreamCreate(stream.put()), ERROR_HIPMF_NO_DEVICE);
+            HIPC(hipStreamCreate(stream2.put()), ERROR_HIPMF_NO_DEVICE);
+            HIPC(hipStreamCreate(stream3.put()), ERROR_HIPMF_NO_DEVICE);
             {
                 // (background work -- zero-fill of E / E', diagonal check beside the first levels: lowest priority, it must not take
                 //  compute units from the level's own launches; measured: level 0 took 225 us with the zero-fill beside it, 186 alone)
                 int least = 0, greatest = 0;
                 if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-                HIPC(hipStreamCreateWithPriority(&st, hipStreamDefault, least), ERROR_HIPMF_NO_DEVICE);
+                HIPC(hipStreamCreateWithPriority(stream4.put(), hipStreamDefault, least), ERROR_HIPMF_NO_DEVICE);
             }
-            stream4 = st;
             // events that order this handle's streams among themselves: no timing, and no system-scope fence at the record (the cache
             // write-back + invalidate of the default costs 5 - 7 us on the stream that records; kernels of the same device see each
             // other's results through the agent-scope release at a kernel's end).  HIPMF_EVENT_FENCE=1: the default flags.
@@ -263,19 +167,11 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
                 if (event_fence_free) xflags |= hipEventDisableSystemFence;
             }
 #endif
-            hipEvent_t e1, e2, e3, e4, e5, e6;
-            HIPC(hipEventCreateWithFlags(&e5, xflags), ERROR_HIPMF_NO_DEVICE);
-            HIPC(hipEventCreateWithFlags(&e6, xflags), ERROR_HIPMF_NO_DEVICE);
-            ev_pb = e5, ev_rest = e6;
-            hipEvent_t e7, e8;
-            HIPC(hipEventCreateWithFlags(&e7, xflags), ERROR_HIPMF_NO_DEVICE);
-            HIPC(hipEventCreateWithFlags(&e8, dflags), ERROR_HIPMF_NO_DEVICE);
-            ev_pre0 = e7, ev_pre1 = e8;
-            HIPC(hipEventCreateWithFlags(&e1, xflags), ERROR_HIPMF_NO_DEVICE);
-            HIPC(hipEventCreateWithFlags(&e2, xflags), ERROR_HIPMF_NO_DEVICE);
-            HIPC(hipEventCreateWithFlags(&e3, xflags), ERROR_HIPMF_NO_DEVICE);
-            HIPC(hipEventCreateWithFlags(&e4, xflags), ERROR_HIPMF_NO_DEVICE);
-            ev_fork = e1, ev_join = e2, ev_fork3 = e3, ev_join3 = e4;
+            HIPC(hipEventCreateWithFlags(ev_pb.put(), xflags), ERROR_HIPMF_NO_DEVICE);
+            HIPC(hipEventCreateWithFlags(ev_rest.put(), xflags), ERROR_HIPMF_NO_DEVICE);
+            HIPC(hipEventCreateWithFlags(ev_pre0.put(), xflags), ERROR_HIPMF_NO_DEVICE);
+            HIPC(hipEventCreateWithFlags(ev_pre1.put(), dflags), ERROR_HIPMF_NO_DEVICE);
+            for (EventOwner *e : {&ev_fork, &ev_join, &ev_fork3, &ev_join3}) HIPC(hipEventCreateWithFlags(e->put(), xflags), ERROR_HIPMF_NO_DEVICE);
         }
         {
             size_t free_b = 0, total_b = 0;
@@ -302,13 +198,13 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
             // (the row that opens a block may itself exceed the cap: it is closed by the next row)
             rb.push_back(n);
             spmv_blocks = (int32_t)rb.size() - 1;
-            HIPC(dev_upload(&d_row_blk, rb), ERROR_HIP_MALLOC);
+            HIPC(d_row_blk.upload(rb), ERROR_HIP_MALLOC);
         }
-        HIPC(hipMalloc((void **)&d_rp, sizeof(int32_t) * ((size_t)n + 1)), ERROR_HIP_MALLOC);
+        HIPC(d_rp.alloc((size_t)n + 1), ERROR_HIP_MALLOC);
         HIPC(hipMemcpy(d_rp, rp, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&d_ci, sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+        HIPC(d_ci.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
         if (nnz > 0) HIPC(hipMemcpy(d_ci, ci, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice), ERROR_HIP_MALLOC);
-        HIPC(dev_upload(&d_arow, h_arow), ERROR_HIP_MALLOC);
+        HIPC(d_arow.upload(h_arow), ERROR_HIP_MALLOC);
         if (sym_lower) {
             // transpose lists: for every row i, the stored entries (r, i), r > i, mirrored into row i
             std::vector<int32_t> tptr((size_t)n + 1, 0), tidx;
@@ -319,8 +215,8 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
             std::vector<int32_t> w(tptr.begin(), tptr.end() - 1);
             for (int64_t k = 0; k < nnz; k++)
                 if (ci[k] != h_arow[k]) tidx[w[ci[k]]++] = (int32_t)k;
-            HIPC(dev_upload(&d_tptr, tptr), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_tidx, tidx), ERROR_HIP_MALLOC);
+            HIPC(d_tptr.upload(tptr), ERROR_HIP_MALLOC);
+            HIPC(d_tidx.upload(tidx), ERROR_HIP_MALLOC);
         }
         return SUCCESSFUL_EXIT;
     };
@@ -755,7 +651,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
     auto tail = [&]() -> int32_t {
         lap("plan + descriptor uploads");
         const int64_t nnz = S.nnz_a;
-        HIPC(dev_upload(&d_perm, S.perm), ERROR_HIP_MALLOC);
+        HIPC(d_perm.upload(S.perm), ERROR_HIP_MALLOC);
         d_rperm = d_perm;
         {
             uint64_t hsh = 1469598103934665603ull;
@@ -769,11 +665,12 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
         if (matched) {
             std::vector<int32_t> rperm((size_t)n);
             for (int32_t k = 0; k < n; k++) rperm[k] = mrow[S.perm[k]];
-            HIPC(dev_upload(&d_rperm, rperm), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_cs, dc), ERROR_HIP_MALLOC);
+            HIPC(d_rperm_matched.upload(rperm), ERROR_HIP_MALLOC);
+            HIPC(d_cs_matched.upload(dc), ERROR_HIP_MALLOC);
+            d_rperm = d_rperm_matched, d_cs = d_cs_matched;
             std::vector<int32_t> dcol((size_t)n);
             for (int32_t j = 0; j < n; j++) dcol[(size_t)mrow[j]] = j; // row mrow[j] of A is pivot row j: its diagonal entry sits in column j
-            HIPC(dev_upload(&d_dcol, dcol), ERROR_HIP_MALLOC);
+            HIPC(d_dcol.upload(dcol), ERROR_HIP_MALLOC);
             // parity of the row permutation (determinant)
             std::vector<char> seen((size_t)n, 0);
             match_parity = 0;
@@ -829,7 +726,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
                 levels[(size_t)l].zero_off = AL.zero_off[(size_t)l], levels[(size_t)l].zero_cnt = AL.zero_n[(size_t)l];
             }
             zero_cnt = AL.zero_cnt;
-            HIPC(dev_upload(&d_sa_ptr, AL.sa_ptr), ERROR_HIP_MALLOC);
+            HIPC(d_sa_ptr.upload(AL.sa_ptr), ERROR_HIP_MALLOC);
             {
                 // descriptors in launch order (the plan is on the device already: read it back rather than keep host copies around)
                 std::vector<FrontDesc> h_fd((size_t)ns);
@@ -842,46 +739,42 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
                     sd[q].fd = h_fd[(size_t)s];
                     sd[q].e0 = AL.sa_ptr[(size_t)s], sd[q].e1 = AL.sa_ptr[(size_t)s + 1]; // (empty ranges for the big fronts, which never read them)
                 }
-                HIPC(dev_upload(&d_sd, sd), ERROR_HIP_MALLOC);
+                HIPC(d_sd.upload(sd), ERROR_HIP_MALLOC);
             }
-            HIPC(dev_upload(&d_sa_k, AL.sa_k), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_sa_pos, AL.sa_pos), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_sc_k, AL.sc_k), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_sc_at, AL.sc_at), ERROR_HIP_MALLOC);
+            HIPC(d_sa_k.upload(AL.sa_k), ERROR_HIP_MALLOC);
+            HIPC(d_sa_pos.upload(AL.sa_pos), ERROR_HIP_MALLOC);
+            HIPC(d_sc_k.upload(AL.sc_k), ERROR_HIP_MALLOC);
+            HIPC(d_sc_at.upload(AL.sc_at), ERROR_HIP_MALLOC);
             if (ea_lds_active()) {
-                HIPC(dev_upload(&d_ea_sc, AL.ea_sc), ERROR_HIP_MALLOC);
-                HIPC(dev_upload(&d_sc_pos, AL.sc_pos), ERROR_HIP_MALLOC);
+                HIPC(d_ea_sc.upload(AL.ea_sc), ERROR_HIP_MALLOC);
+                HIPC(d_sc_pos.upload(AL.sc_pos), ERROR_HIP_MALLOC);
             }
-            HIPC(dev_upload(&d_zero, AL.zt), ERROR_HIP_MALLOC);
+            HIPC(d_zero.upload(AL.zt), ERROR_HIP_MALLOC);
         }
         lap("assembly lists + zero tasks");
         std::vector<int64_t>().swap(S.amap);
         std::vector<int64_t>().swap(S.amap2);
         std::vector<int32_t>().swap(S.amap_sn);
-        HIPC(hipMalloc((void **)&d_vals, sizeof(double) * std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&d_vs, sizeof(double) * std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
-        if (sym_lower) HIPC(hipMalloc((void **)&d_vs2, sizeof(double) * std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+        HIPC(d_vals.alloc(std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+        HIPC(d_vs.alloc(std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+        if (sym_lower) HIPC(d_vs2.alloc(std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
         // (+ WT_X: a wave-subtree fetches its part of the vector / of the interchanges as WT_X entries from its first pivot column on)
-        for (double **p : {&d_xp, &d_r, &d_den, &d_b, &d_x, &d_du, &d_rs}) HIPC(hipMalloc((void **)p, sizeof(double) * ((size_t)n + WT_X)), ERROR_HIP_MALLOC);
+        for (DeviceArray<double> *p : {&d_xp, &d_r, &d_den, &d_b, &d_x, &d_du, &d_rs}) HIPC(p->alloc((size_t)n + WT_X), ERROR_HIP_MALLOC);
         if (matched) HIPC(hipMemcpy(d_rs, dr.data(), sizeof(double) * n, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
-        HIPC(hipMalloc((void **)&d_lperm, sizeof(int32_t) * ((size_t)n + WT_X)), ERROR_HIP_MALLOC);
+        HIPC(d_lperm.alloc((size_t)n + WT_X), ERROR_HIP_MALLOC);
         HIPC(hipMemsetAsync(d_lperm, 0, sizeof(int32_t) * ((size_t)n + WT_X), STREAM), ERROR_HIP_MEMCPY);
-        for (double *p : {d_xp, d_du}) HIPC(hipMemsetAsync(p + n, 0, sizeof(double) * WT_X, STREAM), ERROR_HIP_MEMCPY);
+        for (double *p : {d_xp.get(), d_du.get()}) HIPC(hipMemsetAsync(p + n, 0, sizeof(double) * WT_X, STREAM), ERROR_HIP_MEMCPY);
         // (complex pairs: the n / 2 complex pivots follow the n real ones)
-        HIPC(hipMalloc((void **)&d_diag, sizeof(double) * n * (opt.complex_pairs ? 2 : 1)), ERROR_HIP_MALLOC);
+        HIPC(d_diag.alloc((size_t)n * (opt.complex_pairs ? 2 : 1)), ERROR_HIP_MALLOC);
         if (S.sym_mode) d_cs = d_rs; // symmetric scaling S A S keeps the big fronts symmetric: column scale = row scale
         {
-            HIPC(hipMalloc((void **)&d_info, sizeof(FactorInfoExt)), ERROR_HIP_MALLOC);
+            HIPC(hipMalloc((void **)d_info.put(), sizeof(FactorInfoExt)), ERROR_HIP_MALLOC);
             FactorInfoExt ext = {};
             ext.zdiag = opt.complex_pairs ? d_diag + n : nullptr;
             HIPC(hipMemcpy(d_info, &ext, sizeof ext, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
         }
-        HIPC(hipMalloc((void **)&d_scalar, (4 + (size_t)RES_NORM_WORDS * SF_KMAX) * sizeof(unsigned long long)), ERROR_HIP_MALLOC); // (blocked solves: d_norms_blk)
-        for (auto &e : ev) {
-            hipEvent_t he;
-            HIPC(hipEventCreate(&he), ERROR_HIP_MALLOC);
-            e = he;
-        }
+        HIPC(d_scalar.alloc(4 + (size_t)RES_NORM_WORDS * SF_KMAX), ERROR_HIP_MALLOC); // (blocked solves: d_norms_blk)
+        for (EventOwner &e : ev) HIPC(hipEventCreate(e.put()), ERROR_HIP_MALLOC);
         HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
         lap("value / vector buffers");
         return SUCCESSFUL_EXIT;
@@ -1227,7 +1120,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             leaf_cnt = (int32_t)lf.size();
             if (leaf_cnt > 0) {
                 lf.insert(lf.end(), lb.begin(), lb.end());
-                HIPC(dev_upload(&d_leaf, lf), ERROR_HIP_MALLOC);
+                HIPC(d_leaf.upload(lf), ERROR_HIP_MALLOC);
             }
         }
         if (blocked_slabs || leaf_cnt > 0) {
@@ -1269,26 +1162,26 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             if (split_units > 0) {
                 if (split_units >= (int64_t)0x7fffffff) return ERROR_HIPMF_SYMBOLIC;
                 // (one set per group of a blocked launch)
-                HIPC(hipMalloc((void **)&d_split_scr, sizeof(double) * 256 * (size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
-                HIPC(hipMalloc((void **)&d_split_cnt, sizeof(int32_t) * (size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
+                HIPC(d_split_scr.alloc(256 * (size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
+                HIPC(d_split_cnt.alloc((size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
                 HIPC(hipMemset(d_split_cnt, 0, sizeof(int32_t) * (size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
             }
             sfk_host.clear();
             if (getenv("HIPMF_SF_TRACE"))
                 for (const SfTask &t : sf) sfk_host.push_back(t.kind), sfk_host.push_back(t.a);
-            HIPC(dev_upload(&d_sfk, sf), ERROR_HIP_MALLOC);
-            HIPC(dev_upload(&d_needk, need), ERROR_HIP_MALLOC);
+            HIPC(d_sfk.upload(sf), ERROR_HIP_MALLOC);
+            HIPC(d_needk.upload(need), ERROR_HIP_MALLOC);
             sf.swap(keep);
             need.swap(need_keep);
         }
         if (getenv("HIPMF_SF_TRACE")) { // profiling aid: four device-clock stamps per task of the upper (mixed) launches
             const size_t ntr = (size_t)(sf_fwd_cnt - sf_fwd_band) + (size_t)sf_bwd_top;
-            HIPC(hipMalloc((void **)&d_trace, sizeof(unsigned long long) * 8 * std::max<size_t>(ntr, 1)), ERROR_HIP_MALLOC);
+            HIPC(d_trace.alloc(8 * std::max<size_t>(ntr, 1)), ERROR_HIP_MALLOC);
             HIPC(hipMemset(d_trace, 0, sizeof(unsigned long long) * 8 * std::max<size_t>(ntr, 1)), ERROR_HIP_MALLOC);
             sf_host.clear();
             for (const SfTask &t : sf) sf_host.push_back(t.kind), sf_host.push_back(t.a);
         }
-        HIPC(dev_upload(&d_sf, sf), ERROR_HIP_MALLOC);
+        HIPC(d_sf.upload(sf), ERROR_HIP_MALLOC);
         // ---- bottom of the tree: one wavefront per subtree of small fronts (kernels_solve_tree.hpp) ----
         // A front is "closed" when it and all its descendants are small fronts and the subtree stays within the caps (fronts, panel
         // bytes, pivots = the part of x the wave keeps in LDS, LDS stack = sum of f over a root-to-leaf path of fronts with children);
@@ -1396,9 +1289,9 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
                     meta_f.insert(meta_f.end(), meta_b.begin(), meta_b.end());
                     meta_f.resize(meta_f.size() + WT_MI, 0); // (a batch's meta block is fetched as WT_MI words whatever it holds)
                     wav_f.insert(wav_f.end(), wav_b.begin(), wav_b.end());
-                    HIPC(dev_upload(&d_wt_hdr, hdr_f), ERROR_HIP_MALLOC);
-                    HIPC(dev_upload(&d_wt_meta, meta_f), ERROR_HIP_MALLOC);
-                    HIPC(dev_upload(&d_wt_wave, wav_f), ERROR_HIP_MALLOC);
+                    HIPC(d_wt_hdr.upload(hdr_f), ERROR_HIP_MALLOC);
+                    HIPC(d_wt_meta.upload(meta_f), ERROR_HIP_MALLOC);
+                    HIPC(d_wt_wave.upload(wav_f), ERROR_HIP_MALLOC);
                 }
             }
             if (tree_ok) {
@@ -1442,20 +1335,18 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
                                 if (S.fsize(S.level_sn[k]) > SMALL_F) ridx[(size_t)S.level_sn[k]] = ntop++;
                     rep_words = (int64_t)ntop * SF_REP * 16;
                     if (ntop > 0) {
-                        HIPC(dev_upload(&d_rep_idx, ridx), ERROR_HIP_MALLOC);
+                        HIPC(d_rep_idx.upload(ridx), ERROR_HIP_MALLOC);
                         // (one set per solve lane: a lane clears and uses its own words whatever the other lanes are doing)
-                        HIPC(hipMalloc((void **)&d_rep, sizeof(int32_t) * 2 * (size_t)rep_words * MAX_SOLVE_LANES), ERROR_HIP_MALLOC);
+                        HIPC(d_rep.alloc(2 * (size_t)rep_words * MAX_SOLVE_LANES), ERROR_HIP_MALLOC);
                         HIPC(hipMemset(d_rep, 0, sizeof(int32_t) * 2 * (size_t)rep_words * MAX_SOLVE_LANES), ERROR_HIP_MALLOC);
                     }
                 }
-                HIPC(dev_upload(&d_sf2, sf), ERROR_HIP_MALLOC);
-                HIPC(dev_upload(&d_need2, need), ERROR_HIP_MALLOC);
+                HIPC(d_sf2.upload(sf), ERROR_HIP_MALLOC);
+                HIPC(d_need2.upload(need), ERROR_HIP_MALLOC);
                 if (d_trace) { // (profiling aid: the stamps of THIS list's tasks)
-                    (void)hipFree(d_trace);
-                    d_trace = nullptr;
                     // (room for the stamps of the blocked instances' upper launches too: a blocked solve writes into the same buffer)
                     const size_t ntr2 = std::max<size_t>(std::max<size_t>(sf.size(), (size_t)(sfk_fwd_cnt - sfk_fwd_band) + (size_t)sfk_bwd_top), 1);
-                    HIPC(hipMalloc((void **)&d_trace, sizeof(unsigned long long) * 8 * ntr2), ERROR_HIP_MALLOC);
+                    HIPC(d_trace.alloc(8 * ntr2), ERROR_HIP_MALLOC);
                     HIPC(hipMemset(d_trace, 0, sizeof(unsigned long long) * 8 * ntr2), ERROR_HIP_MALLOC);
                     sf_host.clear();
                     for (const SfTask &t : sf) sf_host.push_back(t.kind), sf_host.push_back(t.a);
@@ -1481,9 +1372,9 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             HIPMF_ALLOW_LDS((k_fwd_fused<false, 1, true, true>), sizeof(double) * 256 * (size_t)up_stage);
             HIPMF_ALLOW_LDS((k_bwd_fused<false, 1, false, true, true>), sizeof(double) * 256 * (size_t)up_stage_bwd);
         }
-        HIPC(dev_upload(&d_need, need), ERROR_HIP_MALLOC);
+        HIPC(d_need.upload(need), ERROR_HIP_MALLOC);
         // (per group of a blocked launch: forward counters | backward counters | one word -- group 0's is the sticky error word)
-        HIPC(hipMalloc((void **)&d_sync, sizeof(int32_t) * SF_GMAX * (2 * (size_t)(SF_SYNC_HEADER + ns) + 1)), ERROR_HIP_MALLOC);
+        HIPC(d_sync.alloc(SF_GMAX * (2 * (size_t)(SF_SYNC_HEADER + ns) + 1)), ERROR_HIP_MALLOC);
         HIPC(hipMemset(d_sync, 0, sizeof(int32_t) * SF_GMAX * (2 * (size_t)(SF_SYNC_HEADER + ns) + 1)), ERROR_HIP_MALLOC);
         return SUCCESSFUL_EXIT;
     };
@@ -1932,38 +1823,36 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
     allbig_off = (int32_t)lists.size();
     allbig_cnt = (int32_t)allbig.size();
     lists.insert(lists.end(), allbig.begin(), allbig.end());
-    HIPC(dev_upload(&d_fd, fd), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_bigfd, bigfd), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_ea, ea), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_ear, ear), ERROR_HIP_MALLOC);
+    HIPC(d_fd.upload(fd), ERROR_HIP_MALLOC);
+    HIPC(d_bigfd.upload(bigfd), ERROR_HIP_MALLOC);
+    HIPC(d_ea.upload(ea), ERROR_HIP_MALLOC);
+    HIPC(d_ear.upload(ear), ERROR_HIP_MALLOC);
     dws_stride = std::max(max_big, 1);
-    HIPC(hipMalloc((void **)&d_dws, sizeof(double) * 2 * NB * NB * (size_t)std::max(max_big, 1)), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_st, stasks), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_lists, lists), ERROR_HIP_MALLOC);
+    HIPC(d_dws.alloc(2 * NB * NB * (size_t)std::max(max_big, 1)), ERROR_HIP_MALLOC);
+    HIPC(d_st.upload(stasks), ERROR_HIP_MALLOC);
+    HIPC(d_lists.upload(lists), ERROR_HIP_MALLOC);
     n_lists = (int64_t)lists.size();
-    HIPC(dev_upload(&d_tasks, tasks), ERROR_HIP_MALLOC);
+    HIPC(d_tasks.upload(tasks), ERROR_HIP_MALLOC);
     if (!chain.empty()) {
-        ChainTask *dc = nullptr;
-        HIPC(dev_upload(&dc, chain), ERROR_HIP_MALLOC);
-        d_chain = dc;
+        HIPC(d_chain.upload(chain), ERROR_HIP_MALLOC);
         chain_words += 1; // the error word
-        HIPC(hipMalloc((void **)&d_chain_cnt, sizeof(int32_t) * (size_t)chain_words), ERROR_HIP_MALLOC);
+        HIPC(d_chain_cnt.alloc((size_t)chain_words), ERROR_HIP_MALLOC);
     }
-    HIPC(dev_upload(&d_rows, S.sn_rows), ERROR_HIP_MALLOC);
+    HIPC(d_rows.upload(S.sn_rows), ERROR_HIP_MALLOC);
     {
         // (+ 64 entries: the solve kernels read relative indices and workspace entries from clamped addresses, unconditionally)
         // (no padded copy of the array on the host: at 200^3 it holds hundreds of megabytes)
-        HIPC(hipMalloc((void **)&d_rel, sizeof(int32_t) * (S.rel.size() + 64)), ERROR_HIP_MALLOC);
+        HIPC(d_rel.alloc(S.rel.size() + 64), ERROR_HIP_MALLOC);
         if (!S.rel.empty()) HIPC(hipMemcpy(d_rel, S.rel.data(), sizeof(int32_t) * S.rel.size(), hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
         HIPC(hipMemset(d_rel + S.rel.size(), 0, sizeof(int32_t) * 64), ERROR_HIP_MEMCPY);
     }
-    HIPC(dev_upload(&d_child, S.child_idx), ERROR_HIP_MALLOC);
+    HIPC(d_child.upload(S.child_idx), ERROR_HIP_MALLOC);
     pl_lap("descriptor / index uploads");
     // (+ WT_CHUNK: the wave-subtree kernels read the factor in whole 1 KB pieces)
     // (tried: these two allocations on a host thread of their own beside the planning -- the runtime serialises the plan uploads behind
     //  the large allocation, initialize of the 200^3 matrix 6.0 -> 6.9 s)
-    HIPC(hipMalloc((void **)&d_pool, sizeof(double) * (std::max<int64_t>(pool_doubles, 1) + WT_CHUNK)), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_work, sizeof(double) * (std::max<int64_t>(work_doubles, 1) + 64)), ERROR_HIP_MALLOC);
+    HIPC(d_pool.alloc(std::max<int64_t>(pool_doubles, 1) + WT_CHUNK), ERROR_HIP_MALLOC);
+    HIPC(d_work.alloc(std::max<int64_t>(work_doubles, 1) + 64), ERROR_HIP_MALLOC);
     pl_lap("pool + workspace allocation");
     if (tail) {
         const int32_t tcode = tail();
@@ -2060,12 +1949,9 @@ int32_t Solver::set_value_map(int64_t nin, const int32_t *seg_ptr, const int32_t
         if (k >= nin) return ERROR_HIPMF_INVALID_VALUE;
     }
     DeviceScope dev_scope(device);
-    for (void *p : {(void *)d_seg_ptr, (void *)d_seg_idx, (void *)d_vin})
-        if (p) (void)hipFree(p);
-    d_seg_ptr = d_seg_idx = nullptr, d_vin = nullptr;
-    HIPC(hipMalloc((void **)&d_seg_ptr, sizeof(int32_t) * (nnz + 1)), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_seg_idx, sizeof(int32_t) * nmap), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_vin, sizeof(double) * nin), ERROR_HIP_MALLOC);
+    HIPC(d_seg_ptr.alloc(nnz + 1), ERROR_HIP_MALLOC);
+    HIPC(d_seg_idx.alloc(nmap), ERROR_HIP_MALLOC);
+    HIPC(d_vin.alloc(nin), ERROR_HIP_MALLOC);
     HIPC(hipMemcpy(d_seg_ptr, seg_ptr, sizeof(int32_t) * (nnz + 1), hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
     HIPC(hipMemcpy(d_seg_idx, seg_idx, sizeof(int32_t) * nmap, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
     nnz_in = nin;
@@ -2515,12 +2401,12 @@ int32_t Solver::run_factor() {
                 if (g) (void)hipGraphDestroy(g);
             }
             (void)hipGetLastError();
-            if (ok) factor_graph = (void *)ge, graph_launches = launches - before;
+            if (ok) factor_graph.reset(ge), graph_launches = launches - before;
             else use_graph = false;
             launches = before;
         }
         if (factor_graph) {
-            HIPC(hipGraphLaunch((hipGraphExec_t)factor_graph, STREAM), ERROR_HIP_LAUNCH);
+            HIPC(hipGraphLaunch(factor_graph, STREAM), ERROR_HIP_LAUNCH);
             launches += graph_launches;
             replayed = true;
         }
@@ -2614,7 +2500,7 @@ int32_t Solver::run_triangular(double *xp, int32_t nk, double *wrk, int64_t xstr
             // one wavefront per subtree of small fronts at the bottom (k_wt_fwd / k_wt_bwd), LDS-staged dependency-driven tasks above
             const int32_t wg = (wt_waves + WT_WAVES - 1) / WT_WAVES;
             const size_t dyn = sizeof(double) * 256 * (size_t)up_stage;
-            unsigned long long *no_tr = (timed && d_trace) ? d_trace : nullptr;
+            unsigned long long *no_tr = (timed && d_trace) ? d_trace.get() : nullptr;
             const int32_t *const no_rep_idx = nullptr;
             int *const no_rep = nullptr;
             if (wg > 0)
@@ -2879,8 +2765,8 @@ int32_t Solver::build_level_tasks() {
     const int32_t nf = (int32_t)sf.size();
     sf3_lvl_b.assign(1, 0);
     for (int32_t l = S.nlevels - 1; l >= 0; l--) emit_level(l, false), sf3_lvl_b.push_back((int32_t)sf.size() - nf);
-    HIPC(dev_upload(&d_sf3, sf), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_need3, need), ERROR_HIP_MALLOC);
+    HIPC(d_sf3.upload(sf), ERROR_HIP_MALLOC);
+    HIPC(d_need3.upload(need), ERROR_HIP_MALLOC);
     return SUCCESSFUL_EXIT;
 }
 
@@ -3143,14 +3029,7 @@ int32_t Solver::solve_core(double *x, const double *rhs, int32_t nrhs, int64_t l
     if (KB > 1 && block_cols >= KB && block_cols * block_groups >= KB * GB) KB = block_cols, GB = block_groups; // (the buffers exist and are wide enough: keep their shape)
     if (KB > 1 && block_cols > 0 && (block_cols < KB || block_cols * block_groups < KB * GB)) {
         // wider blocks than the buffers of an earlier call hold: let them go, they are allocated again below
-        for (void *p : {(void *)d_blk, (void *)d_work_blk, (void *)d_norms_blk})
-            if (p) (void)hipFree(p);
-        d_blk = d_work_blk = nullptr, d_norms_blk = nullptr;
-        for (LaneBuffers &lb : extra_lanes) {
-            for (void *p : {(void *)lb.blk, (void *)lb.work, (void *)lb.sync, (void *)lb.norms})
-                if (p) (void)hipFree(p);
-            if (lb.stream) (void)hipStreamDestroy((hipStream_t)lb.stream);
-        }
+        d_blk.reset(), d_work_blk.reset(), d_norms_blk.reset();
         extra_lanes.clear();
         block_cols = 0, block_groups = 0;
     }
@@ -3183,23 +3062,19 @@ int32_t Solver::solve_core(double *x, const double *rhs, int32_t nrhs, int64_t l
     const size_t lane_cols = (size_t)SF_KMAX * SF_GMAX;                      // columns a lane's norm buffers are sized for
     if (KB > 1 && !d_blk) {
         // xp | du | r | den | b | x: six n x KS blocks, plus KS solve workspaces (columns at the stride that leaves the tagged shadow out)
-        HIPC(hipMalloc((void **)&d_blk, sizeof(double) * 6 * (size_t)n * KS), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&d_work_blk, sizeof(double) * ((size_t)std::max<int64_t>(work_blk_doubles, 1) * KS + 64)), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&d_norms_blk, (size_t)RES_NORM_WORDS * lane_cols * sizeof(unsigned long long)), ERROR_HIP_MALLOC);
+        HIPC(d_blk.alloc(6 * (size_t)n * KS), ERROR_HIP_MALLOC);
+        HIPC(d_work_blk.alloc((size_t)std::max<int64_t>(work_blk_doubles, 1) * KS + 64), ERROR_HIP_MALLOC);
+        HIPC(d_norms_blk.alloc((size_t)RES_NORM_WORDS * lane_cols), ERROR_HIP_MALLOC);
     }
-    if (!h_nrm) HIPC(hipHostMalloc((void **)&h_nrm, sizeof(double) * RES_NORM_WORDS * lane_cols * MAX_SOLVE_LANES), ERROR_HIP_MALLOC);
+    if (!h_nrm) HIPC(h_nrm.alloc(RES_NORM_WORDS * lane_cols * MAX_SOLVE_LANES), ERROR_HIP_MALLOC);
     while ((int32_t)extra_lanes.size() < nlanes - 1) {
-        LaneBuffers lb;
-        hipStream_t st = nullptr;
-        HIPC(hipStreamCreate(&st), ERROR_HIPMF_NO_DEVICE);
-        lb.stream = st;
-        extra_lanes.push_back(lb); // (registered first: release() frees whatever a failed allocation leaves behind)
-        LaneBuffers &r = extra_lanes.back();
-        HIPC(hipMalloc((void **)&r.blk, sizeof(double) * 6 * (size_t)n * KS), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&r.work, sizeof(double) * ((size_t)std::max<int64_t>(work_blk_doubles, 1) * KS + 64)), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&r.sync, sizeof(int32_t) * sync_words * SF_GMAX), ERROR_HIP_MALLOC);
+        LaneBuffers &r = extra_lanes.emplace_back(); // (registered first: release() frees whatever a failed allocation leaves behind)
+        HIPC(hipStreamCreate(r.stream.put()), ERROR_HIPMF_NO_DEVICE);
+        HIPC(r.blk.alloc(6 * (size_t)n * KS), ERROR_HIP_MALLOC);
+        HIPC(r.work.alloc((size_t)std::max<int64_t>(work_blk_doubles, 1) * KS + 64), ERROR_HIP_MALLOC);
+        HIPC(r.sync.alloc(sync_words * SF_GMAX), ERROR_HIP_MALLOC);
         HIPC(hipMemset(r.sync, 0, sizeof(int32_t) * sync_words * SF_GMAX), ERROR_HIP_MALLOC);
-        HIPC(hipMalloc((void **)&r.norms, (size_t)RES_NORM_WORDS * lane_cols * sizeof(unsigned long long)), ERROR_HIP_MALLOC);
+        HIPC(r.norms.alloc((size_t)RES_NORM_WORDS * lane_cols), ERROR_HIP_MALLOC);
     }
     SolveLane lanes[MAX_SOLVE_LANES];
     {
@@ -3238,7 +3113,7 @@ int32_t Solver::solve_core(double *x, const double *rhs, int32_t nrhs, int64_t l
     const bool staged = !on_device && nrhs == 1 && !seen;
     if (!on_device && nrhs == 1) last_host_rhs = rhs, last_host_x = x;
     if (staged) {
-        if (!h_stage) HIPC(hipHostMalloc((void **)&h_stage, sizeof(double) * 2 * (size_t)n), ERROR_HIP_MALLOC);
+        if (!h_stage) HIPC(h_stage.alloc(2 * (size_t)n), ERROR_HIP_MALLOC);
         memcpy(h_stage, rhs, sizeof(double) * (size_t)n);
     }
     HIPC(hipEventRecord((hipEvent_t)ev[6], STREAM), ERROR_HIP_SYNCHRONIZE);
@@ -3473,11 +3348,8 @@ int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &ema
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (nnz_lower < 1 || (int64_t)emap.size() != S.nnz_a) return ERROR_HIPMF_INVALID_VALUE;
     DeviceScope dev_scope(device);
-    for (void *p : {(void *)d_emap, (void *)d_vlow})
-        if (p) (void)hipFree(p);
-    d_emap = nullptr, d_vlow = nullptr;
-    HIPC(dev_upload(&d_emap, emap), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_vlow, sizeof(double) * (size_t)nnz_lower), ERROR_HIP_MALLOC);
+    HIPC(d_emap.upload(emap), ERROR_HIP_MALLOC);
+    HIPC(d_vlow.alloc((size_t)nnz_lower), ERROR_HIP_MALLOC);
     nnz_low = nnz_lower;
     if (&emap != &h_emap) h_emap = emap;
     return SUCCESSFUL_EXIT;
@@ -3642,16 +3514,6 @@ int32_t Solver::determinant_complex(double *mantissa_re, double *mantissa_im, do
 // the assembly / gather tasks (TR_ROWS rows of the front's vector each) and the GEMV tasks (TR_COLS stored columns of E' resp. E each).
 // A^T as CSR: for row i of A^T (column i of A) the rows of A holding an entry in that column, in ascending order, and where its value
 // sits in d_vals -- values are read through the map, so refreshed values, factorize_mapped and adopt_factor need nothing here.
-int32_t Solver::tr_release() {
-    for (void *p : {(void *)d_tr_list, (void *)d_ttptr, (void *)d_ttrow, (void *)d_ttmap, (void *)d_tr_tasks, (void *)d_work_t, (void *)d_tvec, (void *)d_tnrm, (void *)d_anl})
-        if (p) (void)hipFree(p);
-    if (h_tnrm) (void)hipHostFree(h_tnrm);
-    d_tr_list = d_ttptr = d_ttrow = d_ttmap = nullptr, d_tr_tasks = nullptr, d_work_t = d_tvec = d_anl = nullptr, d_tnrm = nullptr, h_tnrm = nullptr;
-    tr_levels.clear();
-    tr_ready = false;
-    return SUCCESSFUL_EXIT;
-}
-
 int32_t Solver::tr_prepare() {
     if (tr_ready) return SUCCESSFUL_EXIT;
     const int32_t n = S.n;
@@ -3685,8 +3547,8 @@ int32_t Solver::tr_prepare() {
         emit(T.ga_off, T.ga_cnt, true, false, TR_ROWS);    // backward: the front's vector
         emit(T.gb_off, T.gb_cnt, false, false, TR_COLS);   // backward: the p columns of E
     }
-    HIPC(dev_upload(&d_tr_list, list), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_tr_tasks, tasks), ERROR_HIP_MALLOC);
+    HIPC(d_tr_list.upload(list), ERROR_HIP_MALLOC);
+    HIPC(d_tr_tasks.upload(tasks), ERROR_HIP_MALLOC);
     // A^T by a counting pass over the stored pattern (rows ascending: the entries of a column of A come out in row order)
     const int64_t nnz = S.nnz_a;
     std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
@@ -3701,13 +3563,13 @@ int32_t Solver::tr_prepare() {
             const int32_t q = fill[(size_t)ci[(size_t)k]]++;
             trow[(size_t)q] = i, tmap[(size_t)q] = k;
         }
-    HIPC(dev_upload(&d_ttptr, tp), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_ttrow, trow), ERROR_HIP_MALLOC);
-    HIPC(dev_upload(&d_ttmap, tmap), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_work_t, sizeof(double) * ((size_t)std::max<int64_t>(work_up, 1) + 64)), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_tvec, sizeof(double) * 6 * (size_t)n), ERROR_HIP_MALLOC);
-    HIPC(hipMalloc((void **)&d_tnrm, sizeof(unsigned long long) * 2), ERROR_HIP_MALLOC);
-    HIPC(hipHostMalloc((void **)&h_tnrm, sizeof(double) * 2), ERROR_HIP_MALLOC);
+    HIPC(d_ttptr.upload(tp), ERROR_HIP_MALLOC);
+    HIPC(d_ttrow.upload(trow), ERROR_HIP_MALLOC);
+    HIPC(d_ttmap.upload(tmap), ERROR_HIP_MALLOC);
+    HIPC(d_work_t.alloc((size_t)std::max<int64_t>(work_up, 1) + 64), ERROR_HIP_MALLOC);
+    HIPC(d_tvec.alloc(6 * (size_t)n), ERROR_HIP_MALLOC);
+    HIPC(d_tnrm.alloc(2), ERROR_HIP_MALLOC);
+    HIPC(h_tnrm.alloc(2), ERROR_HIP_MALLOC);
     tr_ready = true;
     return SUCCESSFUL_EXIT;
 }
@@ -3886,7 +3748,7 @@ int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *ou
     const dim3 g((n + 255) / 256), b(256);
     // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t, partials, scalars
     // (kept per handle: a hipMalloc / hipFree pair of 12 n doubles per call would cost a device-wide synchronisation every time)
-    if (!d_anl) HIPC(hipMalloc((void **)&d_anl, nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
+    if (!d_anl) HIPC(hipMalloc((void **)d_anl.put(), nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
     double *buf = d_anl;
     double *X = buf, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + n, *W1 = AR + n, *W2 = W1 + n, *V = W2 + n, *Y = V + n, *Z = Y + n, *XI = Z + n, *T = XI + n;
     double *pv = T + n, *sv = pv + EA_RED_WG;
@@ -4038,7 +3900,7 @@ int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, do
     const dim3 g((nc + 255) / 256), b(256);
     // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t (complex vectors n doubles, ax .. w2 nc doubles), partials, scalars:
     // the buffer of the real analysis (12 n doubles + the reduction words), allocated the same way
-    if (!d_anl) HIPC(hipMalloc((void **)&d_anl, nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
+    if (!d_anl) HIPC(hipMalloc((void **)d_anl.put(), nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
     double *X = d_anl, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + nc, *W1 = AR + nc, *W2 = W1 + nc, *V = W2 + nc, *Y = V + n, *Z = Y + n,
            *XI = Z + n, *T = XI + n;
     double *pv = d_anl + 12 * (size_t)n, *sv = pv + EA_RED_WG;

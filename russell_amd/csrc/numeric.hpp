@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "device_owner.hpp"
 #include "symbolic.hpp"
 
 namespace hipmf {
@@ -112,7 +113,127 @@ struct LevelPlan {
     int32_t chain_cnt = 0;
 };
 
-class Solver {
+struct ChainTask;
+
+// transposed solves (built at the first one): per level the small fronts and the tasks of the big ones, A^T as CSR through a
+// map into d_vals, a workspace of its own (the tagged words of d_work stay as the ordinary pass pair left them)
+struct SolverTransposed {
+    struct TrLevel {
+        int32_t small_off = 0, small_cnt = 0, asm_off = 0, asm_cnt = 0, gf_off = 0, gf_cnt = 0, ga_off = 0, ga_cnt = 0, gb_off = 0, gb_cnt = 0;
+        int32_t small_pmax = 1, small_fmax = 1; // largest p / f of the level's small fronts (their LDS panels)
+    };
+    std::vector<TrLevel> tr_levels;
+    bool tr_ready = false;
+    DeviceArray<int32_t> d_tr_list, d_ttptr, d_ttrow, d_ttmap;
+    DeviceArray<SolveTask> d_tr_tasks;
+    DeviceArray<double> d_work_t, d_tvec; // d_tvec: six n-vectors (b, x, xp, r, v, z)
+    DeviceArray<double> d_anl;            // error analysis: twelve n-vectors + reduction words (allocated at its first option-1/2 call)
+    DeviceArray<unsigned long long> d_tnrm;
+    PinnedArray<double> h_tnrm;
+};
+
+// Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
+// counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
+// events, the streams.
+struct SolverDevice : SolverTransposed {
+    // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
+    DeviceArray<double> d_pool;
+    DeviceArray<int32_t> d_lperm;
+    DeviceArray<double> d_rs;
+    DeviceArray<double> d_cs_matched;     // column scaling of the matching ...
+    double *d_cs = nullptr;               // ... as the kernels read it (nullptr: none; == d_rs in symmetric mode)
+    DeviceArray<int32_t> d_rperm_matched; // row of A that is row i of the permuted system, under a matching ...
+    int32_t *d_rperm = nullptr;           // ... as the kernels read it (== d_perm without matching)
+    DeviceArray<int32_t> d_dcol; // column of the (matched) diagonal entry of every row of A (nullptr: identity)
+    DeviceArray<LeafRec> d_leaf;   // records of the leaves: forward part, then backward part (other panel offsets)
+    int32_t leaf_cnt = 0;
+    int64_t split_units = 0;       // 256-double units of the scratch of partial sums
+    int64_t split_slabs = 0;
+    DeviceArray<double> d_split_scr;
+    DeviceArray<int32_t> d_split_cnt; // one arrival counter per unit (the first unit of a slab's group is used; reset by the last arriver)
+    DeviceArray<SfTask> d_sfk;
+    DeviceArray<int32_t> d_needk;
+    DeviceArray<SfTask> d_sf3;   // tasks of the level-by-level launches of the dependency-driven kernels (fallback of L D L^T / very large fronts)
+    DeviceArray<int32_t> d_need3;
+    DeviceArray<FrontDesc> d_fd;
+    DeviceArray<FrontDesc> d_bigfd; // copies of the tiled fronts' descriptors, level by level in slot order
+    DeviceArray<EaTask> d_ea;
+    DeviceArray<EaRange> d_ear;
+    DeviceArray<double> d_dws; // factorised diagonal tiles of the current tiled step, one per active big front
+    DeviceArray<SolveTask> d_st;
+    DeviceArray<SfTask> d_sf; // dependency-driven solve (kernels_solve_fused.hpp): one launch per direction
+    DeviceArray<WtHdr> d_wt_hdr;              // batch headers: forward part, then backward part
+    DeviceArray<int32_t> d_wt_meta;           // meta blocks of the batches (records + index lists): forward part, then backward part
+    DeviceArray<WtWave> d_wt_wave;            // batch range and first pivot column of every wave-subtree: forward part, then backward part
+    int32_t wt_waves = 0, wt_recs = 0;        // wave-subtrees, fronts they hold
+    DeviceArray<SfTask> d_sf2;                // tasks of the fronts above the wave-subtrees: forward, then backward
+    int32_t sf2_fwd_cnt = 0, sf2_bwd_cnt = 0;
+    DeviceArray<int32_t> d_rep_idx;           // per front: index of its "complete" replicas (tiled fronts of the top levels), else -1
+    DeviceArray<int32_t> d_rep;               // the replicas: forward part, then backward part (zeroed before every pass)
+    int64_t rep_words = 0;
+    DeviceArray<int32_t> d_need2;             // completed-task counts of that list (the slabs are cut differently)
+    DeviceArray<int32_t> d_need;              // completed-task counts that mark a front as done: [0, ns) forward, [ns, 2 ns) backward
+    DeviceArray<int32_t> d_sync;              // 2 x (SF_SYNC_HEADER + ns) ints: ticket, error word, counters; zeroed before every pass
+    DeviceArray<ChainTask> d_chain;           // ChainTask records of all chained levels
+    DeviceArray<int32_t> d_chain_cnt;         // their counters (3 per front and step) + the error word (last); zeroed before every factorisation
+    int64_t chain_words = 0;
+    // fused assembly of the small fronts (k_small_factor) and zero-fill of the big ones only
+    DeviceArray<int32_t> d_sa_ptr, d_sa_k;
+    DeviceArray<uint16_t> d_sa_pos;
+    DeviceArray<ZeroTask> d_zero;
+    DeviceArray<double> d_vs, d_vs2; // scaled values (and the mirrored ones of symmetric-lower storage)
+    int32_t zero_cnt = 0;
+    DeviceArray<int32_t> d_seg_ptr, d_seg_idx; // value map (set_value_map)
+    DeviceArray<int32_t> d_emap;      // expansion of symmetric-lower values to the analysed general storage (set_expansion)
+    DeviceArray<double> d_vlow;       // staging of the caller's lower-triangle values
+    int64_t nnz_low = 0;
+    DeviceArray<double> d_vin;
+    int64_t nnz_in = 0;
+    DeviceArray<SmallDesc> d_sd;      // per position of d_lists: descriptor + entry range of a small front
+    DeviceArray<double> d_blk, d_work_blk; // many-RHS blocks (allocated at the first multi-column solve)
+    DeviceArray<unsigned long long> d_norms_blk; // norm slots of lane 0's blocked solves (block_cols * block_groups columns)
+    int32_t block_cols = 0;    // columns per block of the many-RHS driver once its buffers exist (8 or 16; HIPMF_BLOCK_COLS forces one)
+    int32_t block_groups = 0;  // blocks ("groups", kernels_solve_fused.hpp SfGroups) a dependency-driven launch of the many-RHS driver carries once its
+                               // buffers exist (1 .. SF_GMAX); block_cols * block_groups columns travel together
+    DeviceArray<unsigned long long> d_trace;  // HIPMF_SF_TRACE=<file>: device-clock stamps of the upper tasks (profiling aid)
+    DeviceArray<FactorInfo> d_info;
+    DeviceArray<unsigned long long> d_scalar; // [0] anorm bits, [4 ...] the norm slots of k_residual (lane 0)
+    DeviceArray<double> d_work, d_vals, d_xp, d_r, d_den, d_b, d_x, d_du;
+    DeviceArray<int32_t> d_rows, d_rel, d_child, d_lists, d_tasks;
+    DeviceArray<int32_t> d_rp, d_ci, d_arow, d_tptr, d_tidx, d_perm;
+    DeviceArray<int32_t> d_ea_sc;   // k_extend_add_lds: per task, the range of its entries of A in d_sc_k / d_sc_pos (cumulative, all levels)
+    DeviceArray<uint16_t> d_sc_pos; // ... position inside the task's tile
+    DeviceArray<int32_t> d_sc_k;    // scatter lists of the tiled fronts, by level: input entry k (or ~k: mirrored copy) ...
+    DeviceArray<int64_t> d_sc_at;   // ... and the pool offset it goes to
+    DeviceArray<double> d_diag;     // pivots in pivot order (determinant, rcond, D of the symmetric fronts)
+    DeviceArray<int32_t> d_row_blk; // row blocks of the stream SpMV (k_spmv_stream)
+    // further lanes of the solve driver (allocated at the first solve with more than one block): stream, block buffers, hand-off
+    // words, norms; lane 0 is the solver's own stream and buffers
+    struct LaneBuffers {
+        StreamOwner stream;
+        DeviceArray<double> blk, work;
+        DeviceArray<int32_t> sync;
+        DeviceArray<unsigned long long> norms;
+    };
+    std::vector<LaneBuffers> extra_lanes;
+    PinnedArray<double> h_nrm;   // pinned: norms of every lane
+    PinnedArray<double> h_stage; // pinned: rhs | x of a single host-pointer solve
+#ifndef HIPMF_EMULATED
+    GraphExecOwner factor_graph; // the launches of a factorisation's levels, captured once and replayed (use_graph)
+#endif
+    int64_t graph_launches = 0;
+    EventOwner ev[8];
+    EventOwner ev_fork, ev_join;
+    EventOwner ev_pb, ev_rest;
+    EventOwner ev_pre0, ev_pre1; // the work before the first level that only the big fronts need (zero-fill of E / E', identity blocks, diagonal check) runs on stream4 beside the levels of small fronts
+    EventOwner ev_fork3, ev_join3;
+    StreamOwner stream;
+    StreamOwner stream2; // the small fronts of a level are factorised beside its tiled steps
+    StreamOwner stream3; // ... and so are the fronts one workgroup factorises (k_front)
+    StreamOwner stream4; // ... and the bulk of a split trailing update (HIPMF_UPD_SPLIT)
+};
+
+class Solver : public SolverDevice {
   public:
     Solver();
     ~Solver();
@@ -205,30 +326,14 @@ class Solver {
     int64_t persist_bytes() const { return S.persist_doubles * 8; }
     double last_residual_inf = 0.0, last_omega = 0.0;
     int device = 0;
-    void *stream = nullptr;
-    void *stream2 = nullptr;          // the small fronts of a level are factorised beside its tiled steps
-    void *ev_fork = nullptr, *ev_join = nullptr;
     // the launches of a factorisation's levels, captured once and replayed (HIPMF_FACTOR_GRAPH=0: eager launches)
     bool use_graph = false; // (measured: no gain at 1000 x 1000 -- the gaps at the level boundaries are the cross-stream edges themselves, not host latency)
-    void *factor_graph = nullptr;
-    int64_t graph_launches = 0;
     bool use_binv = false;            // HIPMF_BLOCK_INV=1: LU fronts of the tiled path take ONE launch per step (kernels_factor_binv.hpp) instead of k_panel + k_update; measured slower (profiles/r04_rejected_experiments.txt)
-    void *stream4 = nullptr;          // ... and the bulk of a split trailing update (HIPMF_UPD_SPLIT)
-    void *ev_pb = nullptr, *ev_rest = nullptr;
-    void *ev_pre0 = nullptr, *ev_pre1 = nullptr; // the work before the first level that only the big fronts need (zero-fill of E / E', identity blocks, diagonal check) runs on stream4 beside the levels of small fronts
     int32_t upd_split_min = 0;        // HIPMF_UPD_SPLIT=n: full steps (two-launch form) with at least n update workgroups are split (0: never; measured: no gain)
-    void *stream3 = nullptr;          // ... and so are the fronts one workgroup factorises (k_front)
-    void *ev_fork3 = nullptr, *ev_join3 = nullptr;
     std::string last_error;
     std::mutex err_mutex; // (the planning thread of initialize and the calling thread both report through last_error)
 
-    // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
-    double *d_pool = nullptr;
-    int64_t pool_doubles = 0;
-    int32_t *d_lperm = nullptr;
-    double *d_rs = nullptr;
-    double *d_cs = nullptr;       // column scaling of the matching (nullptr: none)
-    int32_t *d_rperm = nullptr;   // row of A that is row i of the permuted system (== d_perm without matching)
+    int64_t pool_doubles = 0;     // doubles of the factor in d_pool
     bool matched = false;         // a maximum-product matching pre-permutation is in force
     int32_t match_parity = 0;     // parity of its row permutation (for the determinant)
 
@@ -242,7 +347,6 @@ class Solver {
     SymbolicOptions sopt_keep;
     bool sym_lower_keep = false, rematching = false;
     bool rematch_futile = false; // the last re-matching left a weak diagonal: no further attempts for this handle
-    int32_t *d_dcol = nullptr; // column of the (matched) diagonal entry of every row of A (nullptr: identity)
     int32_t run_factor();
     // forward + backward on nk permuted, scaled vectors (column c at xp + c * xstr, its workspace at wrk + c * wstr)
     struct SolveLane;
@@ -257,19 +361,11 @@ class Solver {
     // round 5: the leaves of the tree leave the task lists of the blocked (many-RHS) solves: one wavefront carries sixteen columns through
     // LEAF_PER_WAVE leaves (kernels_solve_leaf.hpp).  HIPMF_LEAF_KERNELS=0: every small front stays a task.
     bool leaf_kernels = true;
-    LeafRec *d_leaf = nullptr;   // records of the leaves: forward part, then backward part (other panel offsets)
-    int32_t leaf_cnt = 0;
     // blocked instances, backward pass, levels of few slabs with long dot products (the top of a 3D factor): a slab's dot products are
     // split over Q consecutive tasks (k_bwd_fused); forward, the largest fronts of such levels get narrower slabs.  A level qualifies
     // below split_tasks slabs (HIPMF_SPLIT_TASKS, 0: never), a front from split_minlen rows on (HIPMF_SPLIT_MINLEN).
     int32_t split_tasks = 512, split_minlen = 2048; // (split_minlen: 2 048 x the planned block groups unless HIPMF_SPLIT_MINLEN says otherwise)
     bool split_minlen_env = false;
-    int64_t split_units = 0;       // 256-double units of the scratch of partial sums
-    int64_t split_slabs = 0;
-    double *d_split_scr = nullptr;
-    int32_t *d_split_cnt = nullptr; // one arrival counter per unit (the first unit of a slab's group is used; reset by the last arriver)
-    SfTask *d_sfk = nullptr;
-    int32_t *d_needk = nullptr;
     int32_t sfk_fwd_cnt = 0, sfk_bwd_cnt = 0, sfk_fwd_band = 0, sfk_bwd_top = 0;
     bool rearm_tags = false;                   // HIPMF_REARM_TAGS=1: k_wt_bwd re-arms the tagged words for the next pass pair instead of a memset before every pass pair
                                                // (built and measured in round 6: same bits, NOT faster -- pass pair 0.4037 - 0.4076 against 0.4012 - 0.4058 ms, solve
@@ -278,22 +374,12 @@ class Solver {
     bool plain_band = true;                    // HIPMF_PLAIN_BAND=0: the all-small band of the blocked solves stays ONE dependency-driven launch per direction
     std::vector<int32_t> sfk_band_f, sfk_band_b; // task offsets of the band's levels in d_sfk (forward: levels ascending from task 0; backward: relative to
                                                // the first backward task, the band's levels descending) -- one PLAIN launch per level (round 6)
-    SfTask *d_sf3 = nullptr;   // tasks of the level-by-level launches of the dependency-driven kernels (fallback of L D L^T / very large fronts)
-    int32_t *d_need3 = nullptr;
     std::vector<int32_t> sf3_lvl, sf3_lvl_b; // task offsets per level: forward (leaves first), backward (root first)
     bool tri_pending = false;
     std::vector<LevelPlan> levels;
     int64_t work_doubles = 0;
     int32_t allbig_off = 0, allbig_cnt = 0, dws_stride = 1;
-    // device buffers
-    FrontDesc *d_fd = nullptr;
-    FrontDesc *d_bigfd = nullptr; // copies of the tiled fronts' descriptors, level by level in slot order
-    EaTask *d_ea = nullptr;
-    EaRange *d_ear = nullptr;
-    double *d_dws = nullptr; // factorised diagonal tiles of the current tiled step, one per active big front
-    SolveTask *d_st = nullptr;
     // dependency-driven solve (kernels_solve_fused.hpp): one launch per direction
-    SfTask *d_sf = nullptr;
     int32_t sf_fwd_cnt = 0, sf_bwd_cnt = 0; // forward tasks first, then the backward tasks
     int32_t sf_fwd_band = 0, sf_bwd_top = 0; // tasks of the all-small bottom band (forward: first; backward: after sf_bwd_top)
     int32_t sf_fwd_launch = 0;              // == sf_fwd_cnt unless the profiling knob HIPMF_SF_FWD_LEVELS cuts the pass short
@@ -306,22 +392,12 @@ class Solver {
     int32_t up_stage_bwd = 48;              // HIPMF_UP_STAGE_BWD: the same for E' in the backward pass (the dot products run over f, not p)
     int32_t up_stage_mid = 8;               // HIPMF_UP_STAGE_MID: the same for the backward slabs BELOW the top levels (0: none)
     int32_t up_top_fronts = 40;             // HIPMF_UP_TOP_FRONTS: the top levels are those above which no level has more tiled fronts
-    WtHdr *d_wt_hdr = nullptr;              // batch headers: forward part, then backward part
-    int32_t *d_wt_meta = nullptr;           // meta blocks of the batches (records + index lists): forward part, then backward part
-    WtWave *d_wt_wave = nullptr;            // batch range and first pivot column of every wave-subtree: forward part, then backward part
-    int32_t wt_waves = 0, wt_recs = 0;      // wave-subtrees, fronts they hold
     int32_t wt_hdr_fwd = 0, wt_hdr_bwd = 0; // batches of the forward / backward part
     int64_t wt_meta_fwd = 0;                // words of the forward part of d_wt_meta
-    SfTask *d_sf2 = nullptr;                // tasks of the fronts above the wave-subtrees: forward, then backward
-    int32_t sf2_fwd_cnt = 0, sf2_bwd_cnt = 0;
     int32_t sf2_fwd_mid = 0, sf2_bwd_top = 0; // forward: tasks below the top levels come first; backward: the top levels' tasks come first
-    int32_t *d_rep_idx = nullptr;           // per front: index of its "complete" replicas (tiled fronts of the top levels), else -1
-    int32_t *d_rep = nullptr;               // the replicas: forward part, then backward part (zeroed before every pass)
-    int64_t rep_words = 0;
     bool up_pair_xcd = true;                // HIPMF_UP_PAIR_XCD=0: the 8-row slabs of a top-level front in row order (1: neighbours eight tasks apart = same XCD)
     int32_t up_max_groups = 32;             // HIPMF_UP_MAX_GROUPS: column groups of a top-level slab at most (32: 8-row slabs; 16: 16-row slabs = whole 128-byte lines)
     bool use_rep = true;                    // HIPMF_UP_REPLICAS=0: every waiter polls the front's counter
-    int32_t *d_need2 = nullptr;             // completed-task counts of that list (the slabs are cut differently)
     bool tree_active = false;               // the plan above exists for this matrix
     bool use_tag = true;                    // HIPMF_TAG_SOLVE=0: completion counters instead of data-tagged hand-offs above the wave-subtrees
     bool wave_fronts = true;                // HIPMF_WAVE_FRONTS=0: the big fronts of few rows / pivots right above the wave-subtrees stay 256-thread slab tasks in the forward pass
@@ -335,8 +411,6 @@ class Solver {
     int64_t work_arm0 = 0;                  // ... of which the first work_arm0 doubles (the roots of the wave-subtrees) are not armed: k_wt_fwd writes them in a launch of its own
     int64_t work_up = 0;                    // doubles at the head of a solve workspace: the vectors of the fronts outside the wave-subtrees' interiors
                                             // (tag_active: followed by n doubles, the tagged shadow of x)
-    int32_t *d_need = nullptr;              // completed-task counts that mark a front as done: [0, ns) forward, [ns, 2 ns) backward
-    int32_t *d_sync = nullptr;              // 2 x (SF_SYNC_HEADER + ns) ints: ticket, error word, counters; zeroed before every pass
     bool overlap_small = true;              // HIPMF_OVERLAP_SMALL=0: everything on one stream
     bool small_pair = false;                // HIPMF_SMALL_PAIR=1: the two k_small_factor launches of an all-small level side by side (third stream)
     int32_t sf_big_rows = 6, sf_big_front = 2048; // forward solve: fronts with at least sf_big_front rows use slabs of 2^sf_big_rows rows
@@ -349,9 +423,6 @@ class Solver {
     int32_t chain_max_update = 16384;       // ... no step of it has more update workgroups than this (HIPMF_CHAIN_MAX_WGS: wide steps are bound by throughput, and
                                             //     the 8-byte agent-scope accesses of the chained form cost more per byte) ...
     int32_t chain_min_update = 0;           // ... and its widest step has at least this many (HIPMF_CHAIN_MIN_WGS)
-    void *d_chain = nullptr;                // ChainTask records of all chained levels
-    int32_t *d_chain_cnt = nullptr;         // their counters (3 per front and step) + the error word (last); zeroed before every factorisation
-    int64_t chain_words = 0;
     int32_t upd32_max_front = 256;          // LU: levels whose largest tiled front has at most this many rows update with 32 x 32 tiles, one wave per tile
                                             // (HIPMF_UPD32_MAXF; 0: never).  Bit-identical to the 64 x 64 instance; 1000 x 1000: 7.30 -> 7.23 ms.  The L D L^T
                                             // fronts keep the 64 x 64 tiles (measured: 6.32 -> 6.35 ms with the small ones)
@@ -376,90 +447,32 @@ class Solver {
     int32_t small_split = 28; // small fronts up to this size get their own launch per level (HIPMF_SMALL_SPLIT, 0: one launch)
     bool slab64 = false;                    // HIPMF_SOLVE_SLAB64=1: same slab shape in both solve paths (bitwise comparable)
     int32_t sf_err[2] = {0, 0};
-    // fused assembly of the small fronts (k_small_factor) and zero-fill of the big ones only
-    int32_t *d_sa_ptr = nullptr, *d_sa_k = nullptr;
-    uint16_t *d_sa_pos = nullptr;
-    ZeroTask *d_zero = nullptr;
-    double *d_vs = nullptr, *d_vs2 = nullptr; // scaled values (and the mirrored ones of symmetric-lower storage)
-    int32_t zero_cnt = 0;
-    int32_t *d_seg_ptr = nullptr, *d_seg_idx = nullptr; // value map (set_value_map)
-    int32_t *d_emap = nullptr;      // expansion of symmetric-lower values to the analysed general storage (set_expansion)
-    double *d_vlow = nullptr;       // staging of the caller's lower-triangle values
-    int64_t nnz_low = 0;
     std::vector<int32_t> h_emap;
     int32_t load_values(const double *values, bool on_device); // values (CSR order of the caller) -> d_vals
-    double *d_vin = nullptr;
-    int64_t nnz_in = 0;
     int64_t n_lists = 0;            // entries of d_lists
-    SmallDesc *d_sd = nullptr;      // per position of d_lists: descriptor + entry range of a small front
-    double *d_blk = nullptr, *d_work_blk = nullptr; // many-RHS blocks (allocated at the first multi-column solve)
-    // further lanes of the solve driver (allocated at the first solve with more than one block): stream, block buffers, hand-off
-    // words, norms; lane 0 is the solver's own stream and buffers
     static constexpr int32_t MAX_SOLVE_LANES = 4;
-    struct LaneBuffers {
-        void *stream = nullptr;
-        double *blk = nullptr, *work = nullptr;
-        int32_t *sync = nullptr;
-        unsigned long long *norms = nullptr;
-    };
-    std::vector<LaneBuffers> extra_lanes;
-    double *h_nrm = nullptr;   // pinned: norms of every lane
-    double *h_stage = nullptr; // pinned: rhs | x of a single host-pointer solve
     int32_t solve_lanes = 1;   // HIPMF_SOLVE_LANES (1..4).  One since late round 4: two launches full of workgroups that wait for each other's
                                // lower-numbered tasks no longer pay (0.304 against 0.307 - 0.313 ms per right-hand side at 1000^2 with 256
                                // right-hand sides, 0.307 against 0.365 with 64) and, concurrently resident, every few runs one of them ran
                                // into a hand-off time-out (3.7 s; profiles/r04_solve_lanes.txt)
     bool solve_lanes_auto = true; // no HIPMF_SOLVE_LANES given: one lane when the factor exceeds 64 GB (solve())
-    int32_t block_cols = 0;    // columns per block of the many-RHS driver once its buffers exist (8 or 16; HIPMF_BLOCK_COLS forces one)
-    int32_t block_groups = 0;  // blocks ("groups", kernels_solve_fused.hpp SfGroups) a dependency-driven launch of the many-RHS driver carries once its
-                               // buffers exist (1 .. SF_GMAX); block_cols * block_groups columns travel together
     bool prepare_only = false;     // solve() stops after its buffers exist (prepare_many)
     int32_t block_groups_plan = 1; // ... what initialize planned for (HIPMF_BLOCK_GROUPS, else by the size of the factor): the split-dot-product scratch is sized by it
     double block_groups_max_bytes = 1e18; // factors up to this many bytes carry SF_GMAX blocks per launch, larger ones one (HIPMF_BLOCK_GROUPS_BYTES; no limit by default: measured to pay up to config 4's 84 GB, profiles/r06_block_groups.txt)
-    unsigned long long *d_norms_blk = nullptr; // norm slots of lane 0's blocked solves (block_cols * block_groups columns)
     int64_t work_blk_doubles = 0;  // stride between the columns of a blocked solve workspace: work_doubles without the tagged shadow xt
-    unsigned long long *d_trace = nullptr;  // HIPMF_SF_TRACE=<file>: device-clock stamps of the upper tasks (profiling aid)
     std::vector<int32_t> sf_host, sfk_host; // (kind, front) per task (single-column lists / blocked list), kept only when tracing
-    FactorInfo *d_info = nullptr;
-    unsigned long long *d_scalar = nullptr; // [0] anorm bits, [4 ...] the norm slots of k_residual (lane 0)
-    double *d_work = nullptr, *d_vals = nullptr, *d_xp = nullptr, *d_r = nullptr, *d_den = nullptr, *d_b = nullptr, *d_x = nullptr,
-           *d_du = nullptr;
-    int32_t *d_rows = nullptr, *d_rel = nullptr, *d_child = nullptr, *d_lists = nullptr, *d_tasks = nullptr;
-    int32_t *d_rp = nullptr, *d_ci = nullptr, *d_arow = nullptr, *d_tptr = nullptr, *d_tidx = nullptr, *d_perm = nullptr;
     bool mid_lu_split = false;    // HIPMF_MID_LU_SPLIT=1: the k_front_lu fronts of a level in three launches by LDS class (two or four fronts per CU for the smaller ones); measured slower: 6.58 -> 6.95 ms
     bool upd_xcd = true;          // HIPMF_UPD_XCD=0: the tiles of a full trailing update in plain order (1: whole tile columns per XCD)
     bool use_ea_lds = true;       // HIPMF_EA_LDS=0: LU working blocks go back to k_zero + k_scatter + k_extend_add (read-modify-write per child) instead of k_extend_add_lds
     bool ea_lds_active() const { return use_ea_lds; }
     bool use_ea_lu = true;        // HIPMF_EA_LU=0: the first diagonal tiles go back to k_diag0 / the first panel launch
     bool ea_lu_active() const { return ea_lds_active() && use_ea_lu && !use_binv; }
-    int32_t *d_ea_sc = nullptr;   // k_extend_add_lds: per task, the range of its entries of A in d_sc_k / d_sc_pos (cumulative, all levels)
-    uint16_t *d_sc_pos = nullptr; // ... position inside the task's tile
-    int32_t *d_sc_k = nullptr;   // scatter lists of the tiled fronts, by level: input entry k (or ~k: mirrored copy) ...
-    int64_t *d_sc_at = nullptr;  // ... and the pool offset it goes to
-    double *d_diag = nullptr;    // pivots in pivot order (determinant, rcond, D of the symmetric fronts)
-    int32_t *d_row_blk = nullptr; // row blocks of the stream SpMV (k_spmv_stream)
     int32_t spmv_blocks = 0;
-    void *ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // transposed solves (built at the first one): per level the small fronts and the tasks of the big ones, A^T as CSR through a
-    // map into d_vals, a workspace of its own (the tagged words of d_work stay as the ordinary pass pair left them)
-    struct TrLevel {
-        int32_t small_off = 0, small_cnt = 0, asm_off = 0, asm_cnt = 0, gf_off = 0, gf_cnt = 0, ga_off = 0, ga_cnt = 0, gb_off = 0, gb_cnt = 0;
-        int32_t small_pmax = 1, small_fmax = 1; // largest p / f of the level's small fronts (their LDS panels)
-    };
-    std::vector<TrLevel> tr_levels;
-    bool tr_ready = false;
-    int32_t *d_tr_list = nullptr, *d_ttptr = nullptr, *d_ttrow = nullptr, *d_ttmap = nullptr;
-    SolveTask *d_tr_tasks = nullptr;
-    double *d_work_t = nullptr, *d_tvec = nullptr; // d_tvec: six n-vectors (b, x, xp, r, v, z)
-    double *d_anl = nullptr;                       // error analysis: twelve n-vectors + reduction words (allocated at its first option-1/2 call)
-    unsigned long long *d_tnrm = nullptr;
-    double *h_tnrm = nullptr;
     int32_t tr_prepare();
     int32_t run_transposed(double *xp);
     int32_t tr_core(double *x, const double *b, int32_t nstep, double *omega, int32_t *steps);
     int32_t tr_pass(double *y, const double *v); // y = A^{-T} v on the device, one unrefined pass pair
     int32_t tr_spmv(double *y, const double *x); // y = A^T x on the device
-    int32_t tr_release();
 };
 
 } // namespace hipmf

@@ -10,6 +10,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -17,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -185,8 +187,10 @@ inline void run_block(int nthreads) {
     }
 }
 
-template <class K, class... Args>
-inline void launch(K kernel, dim3 grid, dim3 block, size_t shmem, Args... args) {
+// (the arguments are converted to the kernel's parameter types here, as a launch on the device does: an owner of device memory
+//  passes its pointer)
+template <class... P, class... Args>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t shmem, Args &&...args) {
     g_gridDim = grid;
     g_blockDim = block;
     if (g_dynshared.size() < shmem + 16) g_dynshared.resize(shmem + 16);
@@ -195,7 +199,8 @@ inline void launch(K kernel, dim3 grid, dim3 block, size_t shmem, Args... args) 
         fprintf(stderr, "hipemu: block too large\n");
         abort();
     }
-    g_body = [=]() { kernel(args...); };
+    std::tuple<std::decay_t<P>...> params(std::forward<Args>(args)...);
+    g_body = [=]() { std::apply(kernel, params); };
     for (unsigned z = 0; z < grid.z; z++)
         for (unsigned y = 0; y < grid.y; y++)
             for (unsigned x = 0; x < grid.x; x++) {
@@ -308,6 +313,12 @@ inline int atomicOr(int *p, int v) {
 }
 
 // ---- host runtime --------------------------------------------------------------------------------
+// live device allocations, pinned allocations, streams and events (hipemu_live_objects: the CPU tests check that a handle gives back
+// what it took)
+inline std::atomic<long long> hipemu_live[4];
+extern "C" __attribute__((used, visibility("default"))) inline void hipemu_live_objects(long long *out) {
+    for (int k = 0; k < 4; k++) out[k] = hipemu_live[k].load();
+}
 // (development: an allocation beyond HIPEMU_LAZY_GB -- the pool of a large problem whose PLAN is being timed -- is address space only:
 // untouched pages cost nothing, no poison)
 inline std::unordered_map<void *, size_t> &hipemu_lazy_blocks() {
@@ -321,17 +332,22 @@ inline hipError_t hipMalloc(void **p, size_t bytes) {
         if (q == MAP_FAILED) return hipErrorOutOfMemory;
         hipemu_lazy_blocks()[q] = bytes;
         *p = q;
+        hipemu_live[0]++;
         return hipSuccess;
     }
     *p = malloc(bytes ? bytes : 1);
-    if (*p) memset(*p, 0xCD, bytes); // poison: catches reads of uninitialised device memory
-    return *p ? hipSuccess : hipErrorOutOfMemory;
+    if (!*p) return hipErrorOutOfMemory;
+    memset(*p, 0xCD, bytes); // poison: catches reads of uninitialised device memory
+    hipemu_live[0]++;
+    return hipSuccess;
 }
 template <class T>
 inline hipError_t hipMalloc(T **p, size_t bytes) {
     return hipMalloc((void **)p, bytes);
 }
 inline hipError_t hipFree(void *p) {
+    if (!p) return hipSuccess;
+    hipemu_live[0]--;
     auto &lz = hipemu_lazy_blocks();
     auto it = lz.find(p);
     if (it != lz.end()) {
@@ -344,13 +360,16 @@ inline hipError_t hipFree(void *p) {
 }
 inline hipError_t hipHostMalloc(void **p, size_t bytes, unsigned = 0) {
     *p = malloc(bytes ? bytes : 1);
-    return *p ? hipSuccess : hipErrorOutOfMemory;
+    if (!*p) return hipErrorOutOfMemory;
+    hipemu_live[1]++;
+    return hipSuccess;
 }
 template <class T>
 inline hipError_t hipHostMalloc(T **p, size_t bytes, unsigned f = 0) {
     return hipHostMalloc((void **)p, bytes, f);
 }
 inline hipError_t hipHostFree(void *p) {
+    if (p) hipemu_live[1]--;
     free(p);
     return hipSuccess;
 }
@@ -378,10 +397,16 @@ inline hipError_t hipDeviceGetStreamPriorityRange(int *least, int *greatest) {
 }
 inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { return hipStreamCreate(s); }
 inline hipError_t hipStreamCreate(hipStream_t *s) {
-    *s = nullptr;
+    *s = malloc(1); // (a distinct handle per stream, as the runtime gives; launches ignore it)
+    if (!*s) return hipErrorOutOfMemory;
+    hipemu_live[2]++;
     return hipSuccess;
 }
-inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamDestroy(hipStream_t s) {
+    if (s) hipemu_live[2]--;
+    free(s);
+    return hipSuccess;
+}
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -403,9 +428,11 @@ inline hipError_t hipMemGetInfo(size_t *fr, size_t *tot) {
 }
 inline hipError_t hipEventCreate(hipEvent_t *e) {
     *e = new hipemu_event();
+    hipemu_live[3]++;
     return hipSuccess;
 }
 inline hipError_t hipEventDestroy(hipEvent_t e) {
+    if (e) hipemu_live[3]--;
     delete e;
     return hipSuccess;
 }
