@@ -112,14 +112,18 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_with_error_analysis")
         return x, ea
 
-    def solve_many(self, rhs_colmajor):
-        """rhs_colmajor: array of shape (nrhs, n) whose rows are the right-hand sides (= column-major n x nrhs)."""
+    def solve_many(self, rhs_colmajor, ld=None):
+        """rhs_colmajor: array of shape (nrhs, ld) whose rows hold the right-hand sides in their first n entries (= column-major
+        ld x nrhs; ld defaults to n).  Returns x in the same layout: zeros where the library writes nothing, except that the
+        ld - n padding entries of every row are those of rhs_colmajor."""
         b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
-        if b.ndim != 2 or b.shape[1] != self.n:
-            raise ValueError("solve_many expects an array of shape (nrhs, n) with n = %d, got %r" % (self.n, b.shape))
+        ld = self.n if ld is None else int(ld)
+        if b.ndim != 2 or b.shape[1] != ld:
+            raise ValueError("solve_many expects an array of shape (nrhs, ld) with ld = %d, got %r" % (ld, b.shape))
         nrhs = b.shape[0]
         x = np.zeros_like(b)
-        code = self.lib.solver_hipmf_solve_many(self.h, x, b, nrhs, self.n, 0)
+        x[:, self.n:] = b[:, self.n:]
+        code = self.lib.solver_hipmf_solve_many(self.h, x, b, nrhs, ld, 0)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_many")
         return x
