@@ -140,10 +140,19 @@ int32_t solver_hipmf_solve_device(struct InterfaceHIPMF *solver, double *d_x, co
 /* Transposed solves A^T x = b with the factor of A: no second analysis or factorisation (UMFPACK's UMFPACK_At system of umfpack_di_solve,
  * which interface_umfpack.c:229 calls with UMFPACK_A; MUMPS's ICNTL(9) in the job-3 call of interface_mumps.c:243-277).  Refined by the rule
  * of solver_hipmf_solve (residual of A^T), Krylov-rescued after a factorisation that replaced pivots.  L D L^T / symmetric storage: the
- * ordinary solve.  _device: nrhs columns (one at a time), leading dimension ld >= ndim.  Status codes as solver_hipmf_solve;
+ * ordinary solve.  _device: nrhs columns, leading dimension ld >= ndim; it remains the ONE-AT-A-TIME form (every column reads the whole
+ * factor): many columns belong to solver_hipmf_solve_transpose_many / _many_device below.  Status codes as solver_hipmf_solve;
  * ERROR_HIPMF_INVALID_VALUE for nrhs < 1 or ld < ndim. */
 int32_t solver_hipmf_solve_transpose(struct InterfaceHIPMF *solver, double *x, const double *rhs, C_BOOL verbose);
 int32_t solver_hipmf_solve_transpose_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
+/* nrhs right-hand sides of A^T X = B, column-major, leading dimension ld >= ndim; blocks of 16 columns travel through the transposed
+ * level launches together (each factor entry is read once per block).  Refinement, Krylov rescue and status codes per column as
+ * solver_hipmf_solve_transpose; L D L^T / symmetric storage: solver_hipmf_solve_many / _solve_device.  ERROR_HIPMF_INVALID_VALUE for
+ * nrhs < 1 or ld < ndim.  A column's result does not depend on the block or the position it travels in; blocked and one-at-a-time
+ * solves agree to rounding, not bit for bit (nrhs == 1 IS the one-at-a-time solve).  d_x may be d_rhs.  Without memory for the block
+ * buffers (about 64 ndim + 16 x the solve workspace doubles) the columns are solved one at a time. */
+int32_t solver_hipmf_solve_transpose_many(struct InterfaceHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose);
+int32_t solver_hipmf_solve_transpose_many_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
@@ -234,10 +243,12 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
                                              what UMFPACK's dynamic pivoting, interface_umfpack.c:167, would have avoided) a column whose refined solution
                                              leaves |b - A x|_2 > 1e-13 |b|_2 is finished by flexible GMRES preconditioned with the factorisation
                                              (rank(E) + 1 steps in exact arithmetic); 0: not needed.  HIPMF_KRYLOV=0 switches it off */
-#define HIPMF_COUNTER_TRANSPOSED_SOLVES 20 /* right-hand sides solved with A^T (solver_hipmf_solve_transpose / _device; the complex twin's A^T / A^H) */
+#define HIPMF_COUNTER_TRANSPOSED_SOLVES 20 /* right-hand sides solved with A^T (solver_hipmf_solve_transpose / _device / _many / _many_device; the complex twin's A^T / A^H) */
 #define HIPMF_COUNTER_ANALYSIS_SOLVES 21   /* pass pairs the condition estimates of the last solver_hipmf_solve_with_error_analysis (complex: _solve_with_error_analysis) took (at most 22) */
 #define HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS 22 /* steps of the Krylov rescue (A^T as the operator, the transposed pass pair as the preconditioner)
                                                         in the last transposed solve; HIPMF_COUNTER_KRYLOV_ITERATIONS stays the last ordinary solve's */
+#define HIPMF_COUNTER_TRANSPOSED_BLOCKS 23 /* 16-column blocks the last solver_hipmf_solve_transpose_many / _many_device ran through the blocked
+                                              kernels (0: it fell back to the column loop, or A^T = A and the ordinary blocked solve ran) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

@@ -128,6 +128,20 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_many")
         return x
 
+    def solve_transpose_many(self, rhs_colmajor, ld=None):
+        """X = A^{-T} B for an array of shape (nrhs, ld) as solve_many takes and returns it; 16 columns per pass pair over the factor."""
+        b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
+        ld = self.n if ld is None else int(ld)
+        if b.ndim != 2 or b.shape[1] != ld:
+            raise ValueError("solve_transpose_many expects an array of shape (nrhs, ld) with ld = %d, got %r" % (ld, b.shape))
+        nrhs = b.shape[0]
+        x = np.zeros_like(b)
+        x[:, self.n:] = b[:, self.n:]
+        code = self.lib.solver_hipmf_solve_transpose_many(self.h, x, b, nrhs, ld, 0)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_transpose_many")
+        return x
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -151,7 +165,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23}
 
     OPTIONS = {"matching": 0, "pivoting": 1, "hybrid_memory": 2, "error_estimates": 3, "condition_numbers": 4, "sym_recheck": 5}
 
@@ -239,3 +253,9 @@ class Hipmf:
         code = self.lib.solver_hipmf_solve_transpose_device(self.h, d_x, d_rhs, nrhs, ld or self.n)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_transpose_device")
+
+    def solve_transpose_many_device(self, d_x, d_rhs, nrhs, ld=None):
+        """device-resident columns of A^T X = B, 16 per pass pair over the factor (solve_transpose_device: one at a time)"""
+        code = self.lib.solver_hipmf_solve_transpose_many_device(self.h, d_x, d_rhs, nrhs, ld or self.n)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_transpose_many_device")

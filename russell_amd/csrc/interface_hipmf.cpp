@@ -486,6 +486,30 @@ int32_t solver_hipmf_solve_transpose_device(struct InterfaceHIPMF *h, double *d_
     });
 }
 
+// Many transposed right-hand sides, 16 per pass pair (Solver::solve_transpose_many); the statistics are those of column 0.
+int32_t solver_hipmf_solve_transpose_many(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h || !x || !rhs) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (nrhs < 1 || ld < h->solver.S.n) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        h->solver.opt.verbose = verbose == 1;
+        const int32_t code = h->solver.solve_transpose_many(x, rhs, nrhs, ld, false);
+        if (verbose == 1 && code == SUCCESSFUL_EXIT)
+            printf("solver_hipmf_solve_transpose_many: Solution completed (%d column(s), %lld block(s); column 0: %d refinement step(s), omega = %.3e)\n", nrhs,
+                   (long long)h->solver.transposed_blocks, h->solver.refinement_steps_done_t, h->solver.last_omega_t);
+        return code;
+    });
+}
+
+int32_t solver_hipmf_solve_transpose_many_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld) {
+    return guarded(h, [&]() {
+        if (!h || !d_x || !d_rhs) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (nrhs < 1 || ld < h->solver.S.n) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        return h->solver.solve_transpose_many(d_x, d_rhs, nrhs, ld, true);
+    });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -582,6 +606,7 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
     case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
     case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
+    case HIPMF_COUNTER_TRANSPOSED_BLOCKS: return s.transposed_blocks;
     default: return -1;
     }
 }

@@ -17,6 +17,7 @@
 
 #include "kernels.hpp"
 #include "kernels_solve_transpose.hpp"
+#include "kernels_solve_transpose_blocked.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3661,6 +3662,38 @@ int32_t Solver::tr_core(double *x, const double *bvec, int32_t nstep, double *om
     return SUCCESSFUL_EXIT;
 }
 
+// FGMRES on one transposed column (device vectors tx, tb: not d_tvec slots 2 .. 5) with A^T as the operator and the transposed pass pair as the
+// preconditioner (host vectors; d_tvec slots 4 and 5).  Its step count goes to krylov_iterations_t (first column only): krylov_iterations /
+// krylov_last_relres stay what the last ordinary solve left.
+int32_t Solver::tr_rescue(double *tx, const double *tb, bool first_column) {
+    const size_t nb = sizeof(double) * (size_t)S.n;
+    double *tv = d_tvec + 4 * (size_t)S.n, *tz = d_tvec + 5 * (size_t)S.n;
+    KrylovOps ops;
+    ops.precond = [&](double *z, const double *v) -> int32_t {
+        HIPC(hipMemcpy(tv, v, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
+        const int32_t c = tr_pass(tz, tv);
+        if (c != SUCCESSFUL_EXIT) return c;
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        HIPC(hipMemcpy(z, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        return SUCCESSFUL_EXIT;
+    };
+    ops.apply = [&](double *w, const double *z) -> int32_t {
+        HIPC(hipMemcpy(tv, z, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
+        tr_spmv(tz, tv);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        HIPC(hipMemcpy(w, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        return SUCCESSFUL_EXIT;
+    };
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    const int64_t keep_iter = krylov_iterations;
+    const double keep_relres = krylov_last_relres;
+    krylov_iterations = 0;
+    const int32_t code = krylov_rescue(tx, tb, true, &ops);
+    if (first_column) krylov_iterations_t = krylov_iterations;
+    krylov_iterations = keep_iter, krylov_last_relres = keep_relres;
+    return code;
+}
+
 int32_t Solver::solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs) {
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs) return ERROR_NULL_POINTER;
@@ -3688,32 +3721,7 @@ int32_t Solver::solve_transpose(double *x, const double *rhs, int32_t nrhs, int6
         code = tr_core(tx, tb, opt.refinement_nstep, &omega, &steps);
         if (code != SUCCESSFUL_EXIT) return code;
         if (krylov_enabled && !in_rescue && n_perturbed > 0 && !(omega <= krylov_omega_ok)) {
-            // FGMRES with A^T as the operator and the transposed pass pair as the preconditioner (host vectors; d_tvec slots 4 and 5).
-            // Its step count goes to krylov_iterations_t: krylov_iterations / krylov_last_relres stay what the last ordinary solve left.
-            double *tv = d_tvec + 4 * (size_t)n, *tz = d_tvec + 5 * (size_t)n;
-            KrylovOps ops;
-            ops.precond = [&](double *z, const double *v) -> int32_t {
-                HIPC(hipMemcpy(tv, v, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
-                const int32_t c = tr_pass(tz, tv);
-                if (c != SUCCESSFUL_EXIT) return c;
-                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-                HIPC(hipMemcpy(z, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
-                return SUCCESSFUL_EXIT;
-            };
-            ops.apply = [&](double *w, const double *z) -> int32_t {
-                HIPC(hipMemcpy(tv, z, nb, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
-                tr_spmv(tz, tv);
-                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-                HIPC(hipMemcpy(w, tz, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
-                return SUCCESSFUL_EXIT;
-            };
-            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-            const int64_t keep_iter = krylov_iterations;
-            const double keep_relres = krylov_last_relres;
-            krylov_iterations = 0;
-            code = krylov_rescue(tx, tb, true, &ops);
-            if (j == 0) krylov_iterations_t = krylov_iterations;
-            krylov_iterations = keep_iter, krylov_last_relres = keep_relres;
+            code = tr_rescue(tx, tb, j == 0);
             if (code != SUCCESSFUL_EXIT) return code;
         }
         if (conj_pairs) hipLaunchKernelGGL(k_tr_conj, g, b, 0, STREAM, n, tx);
@@ -3723,6 +3731,155 @@ int32_t Solver::solve_transpose(double *x, const double *rhs, int32_t nrhs, int6
     }
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     transposed_solves += nrhs;
+    return SUCCESSFUL_EXIT;
+}
+
+// ---- blocked transposed solves: TR_KB columns per pass pair (kernels_solve_transpose_blocked.hpp) ----
+// The buffers of the blocked path, allocated at its first call: the interleaved workspace (TR_KB values per row of every front, beside
+// d_work and d_work_t), four n x TR_KB block vectors (b, x, xp, r), the norm words.  The launches run over the task lists tr_prepare
+// built on tr_levels: TR_ROWS rows per assembly / gather task, and -- the product kernel's tile -- TR_COLS stored columns per product task.
+int32_t Solver::tr_prepare_blocked() {
+    if (tr_blk_ready) return SUCCESSFUL_EXIT;
+    const size_t n = (size_t)S.n;
+    if (d_work_tb.alloc(((size_t)std::max<int64_t>(work_up, 1) + 64) * TR_KB) != hipSuccess || d_tblk.alloc(4 * n * TR_KB) != hipSuccess ||
+        d_tnrm_blk.alloc(2 * TR_KB) != hipSuccess || h_tnrm_blk.alloc(2 * TR_KB) != hipSuccess) {
+        d_work_tb.reset(), d_tblk.reset(), d_tnrm_blk.reset(), h_tnrm_blk.reset();
+        (void)hipGetLastError(); // (the caller runs the column loop instead: the failed allocation is not its error)
+        return ERROR_HIP_MALLOC;
+    }
+    tr_blk_ready = true;
+    return SUCCESSFUL_EXIT;
+}
+
+// both passes of A^T on the permuted, scaled block XP (n x TR_KB at stride n, in place), one launch per level and front class
+int32_t Solver::run_transposed_blocked(double *XP) {
+    const size_t nl = tr_levels.size();
+    const int64_t xs = S.n;
+    for (size_t l = 0; l < nl; l++) {
+        const TrLevel &T = tr_levels[l];
+        if (T.small_cnt > 0) {
+            const int32_t ldu = T.small_pmax | 1;
+            hipLaunchKernelGGL(k_tr_fwd_small_blk, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_fmax * (size_t)ldu, STREAM,
+                               d_tr_list + T.small_off, d_fd, d_pool, d_child, d_rel, d_work_tb, XP, xs, ldu);
+        }
+        if (T.asm_cnt > 0)
+            hipLaunchKernelGGL(k_tr_assemble_blk, dim3(T.asm_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.asm_off, d_fd, d_child, d_rel, d_work_tb, (const double *)XP, xs);
+        if (T.gf_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemm_blk<true>, dim3(T.gf_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gf_off, d_fd, d_pool, d_work_tb, XP, xs);
+    }
+    for (size_t l = nl; l-- > 0;) {
+        const TrLevel &T = tr_levels[l];
+        if (T.ga_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gather_blk, dim3(T.ga_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.ga_off, d_fd, d_rows, d_work_tb, (const double *)XP, xs);
+        if (T.gb_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemm_blk<false>, dim3(T.gb_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gb_off, d_fd, d_pool, d_work_tb, XP, xs);
+        if (T.small_cnt > 0) {
+            const int32_t ldl = T.small_fmax | 1;
+            hipLaunchKernelGGL(k_tr_bwd_small_blk, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_pmax * (size_t)ldl, STREAM,
+                               d_tr_list + T.small_off, d_fd, d_pool, d_rows, d_lperm, XP, xs, ldl);
+        }
+    }
+    return SUCCESSFUL_EXIT;
+}
+
+// nrhs columns of A^T X = B, TR_KB at a time.  Per block: entry (column permutation and scaling), the two passes, exit (row ones), then
+// tr_core's refinement rule column by column with ONE residual launch and one host look at the block's omegas per step -- columns that are
+// done leave through the mask (they ride through the correcting passes as zeros and the exit kernel leaves them alone) --, then the
+// transposed FGMRES rescue of solve_transpose for the columns that need it.  One column, A^T = A, HIPMF_TRANSPOSE_BLOCKED=0 or no memory
+// for the block buffers: solve_transpose (transposed_blocks stays 0).
+int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device) {
+    transposed_blocks = 0;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs) return ERROR_NULL_POINTER;
+    if (nrhs < 1 || ldx < S.n) return ERROR_HIPMF_INVALID_VALUE;
+    if (nrhs == 1 || S.sym_mode || d_tptr) return solve_transpose(x, rhs, nrhs, ldx, on_device);
+    DeviceScope dev_scope(device);
+    {
+        const int32_t code = tr_prepare();
+        if (code != SUCCESSFUL_EXIT) return code;
+        const char *e = getenv("HIPMF_TRANSPOSE_BLOCKED");
+        if ((e && e[0] == '0') || tr_prepare_blocked() != SUCCESSFUL_EXIT) return solve_transpose(x, rhs, nrhs, ldx, on_device);
+    }
+    const int32_t n = S.n, nstep = opt.refinement_nstep;
+    const size_t nb = sizeof(double) * (size_t)n, nz = (size_t)n;
+    const double EPS = 2.220446049250313e-16;
+    const dim3 g((n + 255) / 256), gp((n + 255) / 256, TR_KB / PERM_CW), b(256);
+    double *TB = d_tblk, *TX = TB + nz * TR_KB, *XP = TX + nz * TR_KB, *R = XP + nz * TR_KB;
+    const uintptr_t xa = (uintptr_t)x, ra = (uintptr_t)rhs, span = sizeof(double) * (size_t)nrhs * (size_t)ldx;
+    const bool aliased = on_device && xa < ra + span && ra < xa + span; // (x written while rhs is still read: the block's columns are staged)
+    krylov_iterations_t = 0;
+    int64_t blocks = 0;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += TR_KB, blocks++) {
+        const int32_t nk = std::min<int32_t>(TR_KB, nrhs - j0);
+        const uint64_t all = (1ull << nk) - 1ull;
+        const double *B = rhs + (int64_t)j0 * ldx;
+        double *X = x + (int64_t)j0 * ldx;
+        int64_t bs = ldx, xs = ldx;
+        if (!on_device || aliased) {
+            for (int32_t c = 0; c < nk; c++)
+                HIPC(hipMemcpyAsync(TB + nz * c, B + (int64_t)c * ldx, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            B = TB, bs = n;
+        }
+        if (!on_device) X = TX, xs = n;
+        hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, B, bs, XP, (int64_t)n, all, nk);
+        int32_t code = run_transposed_blocked(XP);
+        if (code != SUCCESSFUL_EXIT) return code;
+        hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 0, all, nk);
+        double omega[TR_KB], prev[TR_KB];
+        int32_t steps[TR_KB];
+        for (int c = 0; c < TR_KB; c++) omega[c] = prev[c] = INFINITY, steps[c] = 0;
+        uint64_t active = nstep > 0 ? all : 0;
+        for (int32_t it = 0; active; it++) {
+            HIPC(hipMemsetAsync(d_tnrm_blk, 0, sizeof(unsigned long long) * 2 * TR_KB, STREAM), ERROR_HIP_MEMCPY);
+            hipLaunchKernelGGL(k_tr_residual_cols, g, b, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, (const double *)X, xs, B, bs, R, (int64_t)n,
+                               d_tnrm_blk, nk, active);
+            HIPC(hipMemcpyAsync(h_tnrm_blk, d_tnrm_blk, sizeof(double) * 2 * TR_KB, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            uint64_t back = 0, corr = 0;
+            for (int c = 0; c < nk; c++) {
+                if (!((active >> c) & 1ull)) continue;
+                const double om = h_tnrm_blk[2 * c + 1];
+                if (it > 0 && !(om < prev[c])) {
+                    back |= 1ull << c, omega[c] = prev[c]; // take the last correction back
+                    continue;
+                }
+                omega[c] = om;
+                if (om <= EPS || it == nstep || (it > 0 && om > 0.5 * prev[c])) continue;
+                prev[c] = om, corr |= 1ull << c;
+            }
+            if (back) hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 2, back, nk);
+            if (!corr) break;
+            hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, (const double *)R, (int64_t)n, XP, (int64_t)n, corr, nk);
+            code = run_transposed_blocked(XP);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 1, corr, nk);
+            active = 0;
+            for (int c = 0; c < nk; c++)
+                if ((corr >> c) & 1ull) {
+                    steps[c]++;
+                    if (!(prev[c] <= 64.0 * EPS || it + 1 > nstep)) active |= 1ull << c;
+                }
+        }
+        if (krylov_enabled && !in_rescue && n_perturbed > 0) {
+            double *tb = d_tvec, *tx = d_tvec + nz;
+            for (int c = 0; c < nk; c++) {
+                if (omega[c] <= krylov_omega_ok) continue;
+                HIPC(hipMemcpyAsync(tb, B + (int64_t)c * bs, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                HIPC(hipMemcpyAsync(tx, X + (int64_t)c * xs, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                code = tr_rescue(tx, tb, j0 + c == 0);
+                if (code != SUCCESSFUL_EXIT) return code;
+                HIPC(hipMemcpyAsync(X + (int64_t)c * xs, tx, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+            }
+        }
+        if (!on_device)
+            for (int32_t c = 0; c < nk; c++)
+                HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ldx, TX + nz * c, nb, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        if (j0 == 0) last_omega_t = omega[0], refinement_steps_done_t = steps[0];
+    }
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    transposed_solves += nrhs;
+    transposed_blocks = blocks;
     return SUCCESSFUL_EXIT;
 }
 

@@ -130,6 +130,12 @@ struct SolverTransposed {
     DeviceArray<double> d_anl;            // error analysis: twelve n-vectors + reduction words (allocated at its first option-1/2 call)
     DeviceArray<unsigned long long> d_tnrm;
     PinnedArray<double> h_tnrm;
+    // blocked transposed solves (allocated at the first one): the interleaved workspace (16 values per row of every front), four
+    // n x 16 block vectors (b, x, xp, r), the norm words of a block (|r|, omega per column)
+    bool tr_blk_ready = false;
+    DeviceArray<double> d_work_tb, d_tblk;
+    DeviceArray<unsigned long long> d_tnrm_blk;
+    PinnedArray<double> h_tnrm_blk;
 };
 
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
@@ -256,6 +262,10 @@ class Solver : public SolverDevice {
     // rules of solve(); conj_pairs: interleaved complex pairs whose imaginary parts are negated on the way in and out (the complex twin's
     // A^T through the real-equivalent A^H).  L D L^T / symmetric storage: A^T = A, the ordinary solve.
     int32_t solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs = false);
+    // The same for many columns, 16 at a time through the blocked kernels (kernels_solve_transpose_blocked.hpp): every factor entry is read
+    // once per block.  One column, A^T = A or no memory for the block buffers: solve_transpose.
+    int32_t solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device);
+    int64_t transposed_blocks = 0;   // 16-column blocks the last solve_transpose_many ran through the blocked kernels (0: it went to solve_transpose)
     // MUMPS-style error analysis of a solution xbar of A x = b (host vectors; option 1: all eight values, 2: entries 0 - 4), see numeric.cpp
     int32_t error_analysis(const double *xbar, const double *rhs, double *out, int32_t option);
     // the same for the complex twin: this handle holds the real-equivalent system of order 2 nc, xbar / rhs are interleaved complex vectors
@@ -473,6 +483,9 @@ class Solver : public SolverDevice {
     int32_t tr_core(double *x, const double *b, int32_t nstep, double *omega, int32_t *steps);
     int32_t tr_pass(double *y, const double *v); // y = A^{-T} v on the device, one unrefined pass pair
     int32_t tr_spmv(double *y, const double *x); // y = A^T x on the device
+    int32_t tr_rescue(double *tx, const double *tb, bool first_column); // FGMRES on one transposed column (the preconditioner: tr_pass)
+    int32_t tr_prepare_blocked();
+    int32_t run_transposed_blocked(double *XP);
 };
 
 } // namespace hipmf
