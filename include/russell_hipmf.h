@@ -154,6 +154,36 @@ int32_t solver_hipmf_solve_transpose_device(struct InterfaceHIPMF *solver, doubl
 int32_t solver_hipmf_solve_transpose_many(struct InterfaceHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose);
 int32_t solver_hipmf_solve_transpose_many_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 
+/* Sparse right-hand sides and selected solution rows (MUMPS's ICNTL(20); cuDSS and PARDISO have partial solves):
+ *   x_sel(k, c) = (A^{-1} B)(sel_idx[k], c),  k < nsel, c < nrhs,  column-major with ldx >= nsel
+ * for B (ndim x nrhs) in compressed-column form: column c holds the rows rhs_idx[e] with values rhs_val[e], rhs_ptr[c] <= e < rhs_ptr[c + 1];
+ * row indices 0-based and strictly ascending within a column; an empty column gives a zero column.  sel_idx == NULL: all ndim rows
+ * (nsel is ignored, ldx >= ndim).  Duplicates in sel_idx are allowed.
+ * Blocks of 16 columns travel through level-synchronous launches over the MARKED fronts of the elimination tree only: a non-zero touches
+ * the fronts on the path from its front to the root in the forward pass, a wanted row the fronts on the path from the root to its front in
+ * the backward pass; every other front would compute exact zeros or values nobody reads.
+ * ACCURACY: one UNREFINED pass pair per column -- no iterative refinement and no Krylov rescue: both need the full residual, which reads
+ * all of x and A and would undo the pruning (MUMPS treats ICNTL(20) / ICNTL(30) the same way).  The rows returned for a selection are bit
+ * for bit the rows of the sel_idx == NULL result of the same columns.
+ * The ordinary solve runs instead -- solver_hipmf_solve_device on the expanded columns, refined and rescued as the handle is set up,
+ * followed by the selection -- for every block of a handle whose last factorisation replaced pivots (num_perturbed_pivots > 0), and for a
+ * block whose marked fronts would read more than the share HIPMF_PRUNE_MAX_SHARE (environment, read per call; default 0.25) of the factor
+ * entries a full pass pair reads, and for a block of one column when a full pass pair reads less than HIPMF_PRUNE_MIN_BYTES (default 2e9;
+ * a share of 1 or more switches both rules off).  HIPMF_COUNTER_PRUNED_BLOCKS tells how many blocks of the last call ran pruned; dstats[8] is the time
+ * between HIP events around the call's uploads, launches and copies (solver_hipmf_inverse_entries: summed over its blocks).
+ * _device: every array is a device pointer (the index arrays are read back once: the marking runs on the host).
+ * ERROR_HIPMF_INVALID_VALUE: nrhs < 1, an index out of range, decreasing rhs_ptr, unsorted or duplicate rows in a column, nsel < 1 with a
+ * non-NULL sel_idx, ldx too small.  ERROR_NEED_INITIALIZATION / ERROR_NEED_FACTORIZATION before the respective phase. */
+int32_t solver_hipmf_solve_sparse(struct InterfaceHIPMF *solver, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr,
+                                  const int32_t *rhs_idx, const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose);
+int32_t solver_hipmf_solve_sparse_device(struct InterfaceHIPMF *solver, double *d_x_sel, int32_t ldx, int32_t nrhs, const int32_t *d_rhs_ptr,
+                                         const int32_t *d_rhs_idx, const double *d_rhs_val, int32_t nsel, const int32_t *d_sel_idx, C_BOOL verbose);
+/* values[e] = (A^{-1})(rows[e], cols[e]), e < nent (MUMPS's ICNTL(30)); host arrays, any order, duplicates allowed.  A layer over
+ * solver_hipmf_solve_sparse: the distinct columns are sorted by their position in the elimination order, taken 16 at a time as unit
+ * vectors, and the rows asked for in a block are its selection.  Accuracy, fallbacks and status codes as solver_hipmf_solve_sparse
+ * (ERROR_HIPMF_INVALID_VALUE: nent < 1 or an index out of range); HIPMF_COUNTER_PRUNED_BLOCKS sums over the blocks. */
+int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *solver, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -249,6 +279,11 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
                                                         in the last transposed solve; HIPMF_COUNTER_KRYLOV_ITERATIONS stays the last ordinary solve's */
 #define HIPMF_COUNTER_TRANSPOSED_BLOCKS 23 /* 16-column blocks the last solver_hipmf_solve_transpose_many / _many_device ran through the blocked
                                               kernels (0: it fell back to the column loop, or A^T = A and the ordinary blocked solve ran) */
+#define HIPMF_COUNTER_PRUNED_FWD_FRONTS 24 /* fronts the forward pass of the last pruned block of the last solver_hipmf_solve_sparse / _device /
+                                              solver_hipmf_inverse_entries visited */
+#define HIPMF_COUNTER_PRUNED_BWD_FRONTS 25 /* ... and its backward pass (sel_idx == NULL: every front) */
+#define HIPMF_COUNTER_PRUNED_BLOCKS 26     /* 16-column blocks of the last such call that ran pruned (0: everything went through the ordinary solve) */
+#define HIPMF_COUNTER_PRUNED_BYTES 27      /* bytes of factor entries (8 p f per front and pass) the marked fronts of the last pruned block hold, forward + backward */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

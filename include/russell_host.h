@@ -107,6 +107,11 @@ void rh_linsolver_free(void *solver);
 const char *rh_linsolver_factorize(void *solver, void *coo, const struct RhParams *params_or_null);
 const char *rh_linsolver_solve(void *solver, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose);
 const char *rh_linsolver_solve_many(void *solver, double *x, const double *rhs, int64_t n, int64_t nrhs);
+/* extensions of the HIPMF backend (solver_hipmf_solve_sparse / solver_hipmf_inverse_entries of russell_hipmf.h): right-hand sides in
+ * compressed-column form (ptr: ncol + 1 entries), sel == NULL: all rows; x_sel column-major with nx = (nsel or ndim) * ncol entries */
+const char *rh_linsolver_solve_sparse(void *solver, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val,
+                                      int64_t nsel, const int32_t *sel, int32_t verbose);
+const char *rh_linsolver_inverse_entries(void *solver, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose);
 void rh_linsolver_times(void *solver, uint64_t *ns3);
 void rh_linsolver_outputs(void *solver, double *det_coef, double *det_exp, double *rcond, int32_t *eff_ordering, int32_t *eff_scaling, int32_t *npert);
 const char *rh_linsolver_stats_json(void *solver, void *coo, const char *name, const double *x, const double *rhs);

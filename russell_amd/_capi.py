@@ -34,6 +34,10 @@ SYMBOLS = {
     "solver_hipmf_solve_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "solver_hipmf_solve_transpose_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, C.c_int32]),
     "solver_hipmf_solve_transpose_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "solver_hipmf_solve_sparse": (C.c_int32, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, i32p, f64p, C.c_int32, C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_sparse_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                      C.c_void_p, C.c_int32]),
+    "solver_hipmf_inverse_entries": (C.c_int32, [C.c_void_p, C.c_int32, i32p, i32p, f64p, C.c_int32]),
     "solver_hipmf_solve_with_error_analysis": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_int32]),
     "solver_hipmf_mat_vec_mul": (C.c_int32, [C.c_void_p, f64p, C.c_double, f64p]),
     "solver_hipmf_get_permutation": (C.c_int32, [C.c_void_p, i32p]),

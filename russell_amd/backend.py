@@ -142,6 +142,35 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_transpose_many")
         return x
 
+    def solve_sparse(self, rhs_ptr, rhs_idx, rhs_val, select=None, ldx=None, verbose=False):
+        """Rows `select` (None: all n) of A^{-1} B for B in compressed-column form (rhs_ptr of nrhs + 1 entries, 0-based row indices ascending
+        within a column): an array of shape (nrhs, ldx) whose rows hold the columns' selected entries in their first nsel places (ldx
+        defaults to nsel).  One unrefined pass pair over the marked fronts per block of 16 columns."""
+        ptr = np.ascontiguousarray(rhs_ptr, dtype=np.int32)
+        idx = np.ascontiguousarray(rhs_idx, dtype=np.int32)
+        val = np.ascontiguousarray(rhs_val, dtype=np.float64)
+        nrhs = int(ptr.size) - 1
+        sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32)
+        nsel = self.n if sel is None else int(sel.size)
+        ldx = nsel if ldx is None else int(ldx)
+        x = np.zeros((max(nrhs, 0), max(ldx, 0)))
+        code = self.lib.solver_hipmf_solve_sparse(self.h, x, ldx, nrhs, ptr, idx, val, nsel, None if sel is None else sel.ctypes.data, int(verbose))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_sparse")
+        return x
+
+    def inverse_entries(self, rows, cols, verbose=False):
+        """(A^{-1})[rows[e], cols[e]] for every e (any order, duplicates allowed), 16 distinct columns per pruned pass pair."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        if r.shape != c.shape or r.ndim != 1:
+            raise ValueError("inverse_entries expects two index vectors of equal length, got %r and %r" % (r.shape, c.shape))
+        v = np.zeros(r.size)
+        code = self.lib.solver_hipmf_inverse_entries(self.h, int(r.size), r, c, v, int(verbose))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_inverse_entries")
+        return v
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -165,7 +194,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27}
 
     OPTIONS = {"matching": 0, "pivoting": 1, "hybrid_memory": 2, "error_estimates": 3, "condition_numbers": 4, "sym_recheck": 5}
 
@@ -259,3 +288,9 @@ class Hipmf:
         code = self.lib.solver_hipmf_solve_transpose_many_device(self.h, d_x, d_rhs, nrhs, ld or self.n)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_transpose_many_device")
+
+    def solve_sparse_device(self, d_x_sel, ldx, nrhs, d_rhs_ptr, d_rhs_idx, d_rhs_val, nsel, d_sel_idx=None):
+        """solve_sparse with every array resident on the device (d_sel_idx None: all n rows)"""
+        code = self.lib.solver_hipmf_solve_sparse_device(self.h, d_x_sel, int(ldx), int(nrhs), d_rhs_ptr, d_rhs_idx, d_rhs_val, int(nsel), d_sel_idx, 0)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_sparse_device")

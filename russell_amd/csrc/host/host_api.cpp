@@ -744,6 +744,8 @@ struct Backend {
     decltype(&complex_solver_hipmf_solve_transpose) zsolve_t = nullptr;
     decltype(&complex_solver_hipmf_solve_with_error_analysis) zsolve_ea = nullptr;
     decltype(&solver_hipmf_solve_many) solve_many = nullptr;
+    decltype(&solver_hipmf_solve_sparse) solve_sparse = nullptr;
+    decltype(&solver_hipmf_inverse_entries) inverse_entries = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
     decltype(&solver_hipmf_factorize_mapped) factorize_mapped = nullptr;
     decltype(&solver_hipmf_get_stats) get_stats = nullptr;
@@ -799,6 +801,8 @@ bool load_backend() {
     BIND(zsolve_t, "complex_solver_hipmf_solve_transpose")
     BIND(zsolve_ea, "complex_solver_hipmf_solve_with_error_analysis")
     BIND(solve_many, "solver_hipmf_solve_many")
+    BIND(solve_sparse, "solver_hipmf_solve_sparse")
+    BIND(inverse_entries, "solver_hipmf_inverse_entries")
     BIND(set_value_map, "solver_hipmf_set_value_map")
     BIND(factorize_mapped, "solver_hipmf_factorize_mapped")
     BIND(get_stats, "solver_hipmf_get_stats")
@@ -1265,6 +1269,45 @@ StrError SolverHIPMF::solve_many(std::vector<double> &x, const std::vector<doubl
     if (rhs.size() != initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
     uint64_t t0 = now_ns();
     int32_t status = g_backend.solve_many((InterfaceHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+StrError SolverHIPMF::solve_sparse(std::vector<double> &x_sel, const std::vector<int32_t> &ptr, const std::vector<int32_t> &idx, const std::vector<double> &val,
+                                   const std::vector<int32_t> &select, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (ptr.size() < 2) return "the sparse right-hand side must have at least one column";
+    const size_t ncol = ptr.size() - 1, ndim = initialized_ndim;
+    if (ptr[0] != 0) return "the column pointers of the sparse right-hand side must start at zero";
+    for (size_t c = 0; c < ncol; c++)
+        if (ptr[c + 1] < ptr[c]) return "the column pointers of the sparse right-hand side must not decrease";
+    if (idx.size() != (size_t)ptr[ncol] || val.size() != idx.size()) return "the dimension of the arrays of the sparse right-hand side is incorrect";
+    for (size_t c = 0; c < ncol; c++)
+        for (int32_t e = ptr[c]; e < ptr[c + 1]; e++) {
+            if (idx[(size_t)e] < 0 || (size_t)idx[(size_t)e] >= ndim) return "a row index of the sparse right-hand side is outside range";
+            if (e > ptr[c] && idx[(size_t)e] <= idx[(size_t)e - 1]) return "the row indices of a column of the sparse right-hand side must be ascending and unique";
+        }
+    for (int32_t q : select)
+        if (q < 0 || (size_t)q >= ndim) return "a selected row is outside range";
+    const size_t nout = select.empty() ? ndim : select.size();
+    if (x_sel.size() != nout * ncol) return "the dimension of the array of selected unknown values x is incorrect";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.solve_sparse((InterfaceHIPMF *)solver, x_sel.data(), (int32_t)nout, (int32_t)ncol, ptr.data(), idx.data(), val.data(),
+                                            (int32_t)select.size(), select.empty() ? nullptr : select.data(), verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+StrError SolverHIPMF::inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (rows.empty() || rows.size() != cols.size()) return "the arrays of row and column indices must have the same, positive length";
+    if (values.size() != rows.size()) return "the dimension of the array of values is incorrect";
+    for (size_t e = 0; e < rows.size(); e++)
+        if (rows[e] < 0 || (size_t)rows[e] >= initialized_ndim || cols[e] < 0 || (size_t)cols[e] >= initialized_ndim) return "an index of an entry of the inverse is outside range";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.inverse_entries((InterfaceHIPMF *)solver, (int32_t)rows.size(), rows.data(), cols.data(), values.data(), verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1791,6 +1834,31 @@ const char *rh_linsolver_solve_many(void *h, double *x, const double *rhs, int64
     std::vector<double> xx((size_t)(n * nrhs)), rr(rhs, rhs + n * nrhs);
     StrError e = a->solve_many(xx, rr, (size_t)nrhs);
     if (!e) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+const char *rh_linsolver_solve_sparse(void *h, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val, int64_t nsel,
+                                      const int32_t *sel, int32_t verbose) {
+    RhSolver *s = (RhSolver *)h;
+    SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
+    if (!a) return "solve_sparse is only available with Genie::Hipmf";
+    if (ncol < 1 || !ptr) return "the sparse right-hand side must have at least one column";
+    const std::vector<int32_t> pp(ptr, ptr + ncol + 1);
+    const size_t nz = pp[(size_t)ncol] > 0 ? (size_t)pp[(size_t)ncol] : 0;
+    const std::vector<int32_t> ii(idx, idx + nz), ss(sel, sel + (sel ? nsel : 0));
+    const std::vector<double> vv(val, val + nz);
+    std::vector<double> xx((size_t)nx);
+    StrError e = a->solve_sparse(xx, pp, ii, vv, ss, verbose != 0);
+    if (!e) std::copy(xx.begin(), xx.end(), x_sel);
+    return e;
+}
+const char *rh_linsolver_inverse_entries(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose) {
+    RhSolver *s = (RhSolver *)h;
+    SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
+    if (!a) return "inverse_entries is only available with Genie::Hipmf";
+    const std::vector<int32_t> rr(rows, rows + (nent > 0 ? nent : 0)), cc(cols, cols + (nent > 0 ? nent : 0));
+    std::vector<double> vv(rr.size());
+    StrError e = a->inverse_entries(vv, rr, cc, verbose != 0);
+    if (!e) std::copy(vv.begin(), vv.end(), values);
     return e;
 }
 void rh_linsolver_times(void *h, uint64_t *ns3) {

@@ -213,6 +213,13 @@ class SolverHIPMF : public LinSolTrait {
     uint64_t get_ns_solve() const override { return time_solve_ns; }
     // extension: many right-hand sides, column-major n x nrhs
     StrError solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs);
+    // extension: sparse right-hand sides in compressed-column form (ptr: ncol + 1 entries; row indices ascending within a column) and a
+    // selection of rows (empty: all of them): x_sel column-major, (select.size() or ndim) x ncol; one unrefined pass pair over the fronts
+    // the non-zeros and the selected rows touch (solver_hipmf_solve_sparse)
+    StrError solve_sparse(std::vector<double> &x_sel, const std::vector<int32_t> &ptr, const std::vector<int32_t> &idx, const std::vector<double> &val,
+                          const std::vector<int32_t> &select, bool verbose);
+    // extension: values[e] = (A^{-1})(rows[e], cols[e]) (solver_hipmf_inverse_entries)
+    StrError inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose);
     // extension: the backend's diagnostic counters (HIPMF_COUNTER_* of include/russell_hipmf.h; -1 before the first factorize)
     int64_t get_counter(int32_t which) const;
 

@@ -510,6 +510,42 @@ int32_t solver_hipmf_solve_transpose_many_device(struct InterfaceHIPMF *h, doubl
     });
 }
 
+// Sparse right-hand sides / selected rows / entries of the inverse (Solver::solve_sparse, Solver::inverse_entries; MUMPS's ICNTL(20) and
+// ICNTL(30)): one unrefined pass pair over the marked fronts per block of 16 columns.
+static int32_t solve_sparse_body(struct InterfaceHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
+                                 const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h) return ERROR_NULL_POINTER;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_sparse(x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, on_device);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("%s: Solution completed (%d column(s), %lld pruned block(s); last block: %lld / %lld fronts forward / backward, share %.3f)\n", who, nrhs,
+               (long long)h->solver.pruned_blocks, (long long)h->solver.pruned_fwd_fronts, (long long)h->solver.pruned_bwd_fronts, h->solver.pruned_share_last);
+    return code;
+}
+
+int32_t solver_hipmf_solve_sparse(struct InterfaceHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
+                                  const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_sparse_body(h, x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, verbose, false, "solver_hipmf_solve_sparse"); });
+}
+
+int32_t solver_hipmf_solve_sparse_device(struct InterfaceHIPMF *h, double *d_x_sel, int32_t ldx, int32_t nrhs, const int32_t *d_rhs_ptr, const int32_t *d_rhs_idx,
+                                         const double *d_rhs_val, int32_t nsel, const int32_t *d_sel_idx, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_sparse_body(h, d_x_sel, ldx, nrhs, d_rhs_ptr, d_rhs_idx, d_rhs_val, nsel, d_sel_idx, verbose, true, "solver_hipmf_solve_sparse_device");
+    });
+}
+
+int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *h, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h) return (int32_t)ERROR_NULL_POINTER;
+        h->solver.opt.verbose = verbose == 1;
+        const int32_t code = h->solver.inverse_entries(nent, rows, cols, values);
+        if (verbose == 1 && code == SUCCESSFUL_EXIT)
+            printf("solver_hipmf_inverse_entries: %d entr%s completed (%lld pruned block(s))\n", nent, nent == 1 ? "y" : "ies", (long long)h->solver.pruned_blocks);
+        return code;
+    });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -607,6 +643,10 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
     case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
     case HIPMF_COUNTER_TRANSPOSED_BLOCKS: return s.transposed_blocks;
+    case HIPMF_COUNTER_PRUNED_FWD_FRONTS: return s.pruned_fwd_fronts;
+    case HIPMF_COUNTER_PRUNED_BWD_FRONTS: return s.pruned_bwd_fronts;
+    case HIPMF_COUNTER_PRUNED_BLOCKS: return s.pruned_blocks;
+    case HIPMF_COUNTER_PRUNED_BYTES: return s.pruned_bytes;
     default: return -1;
     }
 }

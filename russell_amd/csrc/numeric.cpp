@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "kernels_solve_transpose.hpp"
 #include "kernels_solve_transpose_blocked.hpp"
+#include "kernels_solve_pruned.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3880,6 +3881,356 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     transposed_solves += nrhs;
     transposed_blocks = blocks;
+    return SUCCESSFUL_EXIT;
+}
+
+// ---- sparse right-hand sides, selected solution rows, entries of the inverse (kernels_solve_pruned.hpp) ----
+// Pruning the elimination tree is exact.  The forward pass of column c starts from zeros everywhere but at the permuted positions of its
+// non-zeros: a front whose subtree holds none of them assembles zeros, eliminates zeros and hands zeros up -- only the fronts on the paths
+// from those positions' fronts to the root do anything.  The backward pass computes x1 of a front from y1 and the entries of x of its
+// ANCESTORS only: row i of x needs the fronts on the path from the root down to i's front and nothing else.
+// The maps (built once): the inverses of the entry permutation (d_rperm: row of A at permuted position i; with a matching the matched
+// one) and of the exit permutation (d_perm), read back from the device -- so whatever initialize or a re-matching factorize installed is
+// what the maps invert --; the front of a position and the parent of a front are S.sn_of and S.sn_parent.
+int32_t Solver::sp_prepare() {
+    if (sp_ready) return SUCCESSFUL_EXIT;
+    const size_t n = (size_t)S.n, ns = (size_t)S.nsuper;
+    std::vector<int32_t> rp(n), cp(n);
+    HIPC(hipMemcpy(rp.data(), d_rperm, sizeof(int32_t) * n, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpy(cp.data(), d_perm, sizeof(int32_t) * n, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+    sp_ipos_r.assign(n, 0), sp_ipos_c.assign(n, 0);
+    for (size_t i = 0; i < n; i++) sp_ipos_r[(size_t)rp[i]] = (int32_t)i, sp_ipos_c[(size_t)cp[i]] = (int32_t)i;
+    HIPC(d_sp_ipos_r.upload(sp_ipos_r), ERROR_HIP_MALLOC);
+    HIPC(d_sp_ipos_c.upload(sp_ipos_c), ERROR_HIP_MALLOC);
+    HIPC(d_sp_mark.alloc(std::max<size_t>(ns, 1)), ERROR_HIP_MALLOC);
+    HIPC(hipMemset(d_sp_mark, 0, sizeof(int32_t) * std::max<size_t>(ns, 1)), ERROR_HIP_MEMCPY);
+    HIPC(d_sp_xp.alloc(n * SP_KB), ERROR_HIP_MALLOC);
+    HIPC(d_sp_work.alloc(((size_t)std::max<int64_t>(work_up, 1) + 64) * SP_KB), ERROR_HIP_MALLOC);
+    HIPC(hipEventCreate(sp_ev0.put()), ERROR_HIPMF_NO_DEVICE);
+    HIPC(hipEventCreate(sp_ev1.put()), ERROR_HIPMF_NO_DEVICE);
+    sp_stamp_f.assign(ns, 0), sp_stamp_b.assign(ns, 0);
+    sp_epoch = 0;
+    sp_total_pf = 0.0;
+    for (int32_t s = 0; s < S.nsuper; s++) sp_total_pf += (double)S.npiv(s) * (double)S.fsize(s);
+    sp_ready = true;
+    return SUCCESSFUL_EXIT;
+}
+
+void Solver::sp_build_lists(const std::vector<int32_t> &fronts, bool forward, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const {
+    const size_t nl = (size_t)S.nlevels;
+    lv.assign(nl, SpLevel());
+    buf.clear();
+    // bucket by level (counting sort; fronts ascending within a level: the lists do not depend on the order the marking met them)
+    std::vector<int32_t> cnt(nl + 1, 0), order(fronts.size());
+    for (int32_t s : fronts) cnt[(size_t)S.sn_level[(size_t)s] + 1]++;
+    for (size_t l = 0; l < nl; l++) cnt[l + 1] += cnt[l];
+    {
+        std::vector<int32_t> at(cnt.begin(), cnt.end() - 1);
+        for (int32_t s : fronts) order[(size_t)at[(size_t)S.sn_level[(size_t)s]]++] = s;
+    }
+    for (size_t l = 0; l < nl; l++) {
+        SpLevel &L = lv[l];
+        int32_t *b = order.data() + cnt[l], *e = order.data() + cnt[l + 1];
+        std::sort(b, e);
+        L.small_off = (int32_t)buf.size();
+        for (int32_t *q = b; q < e; q++)
+            if (S.fsize(*q) <= SMALL_F) buf.push_back(*q), L.pmax = std::max(L.pmax, S.npiv(*q)), L.fmax = std::max(L.fmax, S.fsize(*q));
+        L.small_cnt = (int32_t)buf.size() - L.small_off;
+        auto task = [&](int32_t s, int32_t r0, int32_t r1) { buf.push_back(s), buf.push_back(r0), buf.push_back(r1); };
+        L.va_off = (int32_t)buf.size();
+        for (int32_t *q = b; q < e; q++)
+            if (S.fsize(*q) > SMALL_F)
+                for (int32_t r0 = 0; r0 < S.fsize(*q); r0 += TR_ROWS) task(*q, r0, std::min(S.fsize(*q), r0 + TR_ROWS)), L.va_cnt++;
+        L.pr_off = (int32_t)buf.size();
+        for (int32_t *q = b; q < e; q++)
+            if (S.fsize(*q) > SMALL_F) {
+                const int32_t p = S.npiv(*q), f = S.fsize(*q);
+                for (int32_t r0 = 0; r0 < p; r0 += SP_ROWS) task(*q, r0, std::min(p, r0 + SP_ROWS)), L.pr_cnt++;
+                if (forward) // (the tiles of the update rows start at p: no tile straddles the pivot block, whose known zeros are skipped)
+                    for (int32_t r0 = p; r0 < f; r0 += SP_ROWS) task(*q, r0, std::min(f, r0 + SP_ROWS)), L.pr_cnt++;
+            }
+    }
+}
+
+// both passes on the permuted, scaled block XP (n x SP_KB at stride n, in place) over the lists already on the device
+int32_t Solver::run_pruned(double *XP, const std::vector<SpLevel> &fl, const std::vector<SpLevel> &bl) {
+    const int64_t xs = S.n;
+    const int32_t *FB = d_sp_fwd.a, *BB = d_sp_bwd.a;
+    const int32_t ep = sp_epoch;
+    auto tasks = [](const int32_t *base, int32_t off) { return reinterpret_cast<const SolveTask *>(base + off); };
+    for (size_t l = 0; l < fl.size(); l++) {
+        const SpLevel &L = fl[l];
+        if (L.small_cnt > 0) {
+            const int32_t ldp = L.fmax | 1;
+            hipLaunchKernelGGL(k_sp_fwd_small, dim3(L.small_cnt), dim3(64), sizeof(double) * (size_t)ldp * (size_t)L.pmax, STREAM, FB + L.small_off, d_fd, d_pool,
+                               d_lperm, d_child, d_rel, d_sp_mark, ep, d_sp_work, XP, xs, ldp);
+        }
+        if (L.va_cnt > 0)
+            hipLaunchKernelGGL(k_sp_assemble, dim3(L.va_cnt), dim3(256), 0, STREAM, tasks(FB, L.va_off), d_fd, d_child, d_rel, d_sp_mark, ep, d_sp_work,
+                               (const double *)XP, xs);
+        if (L.pr_cnt > 0)
+            hipLaunchKernelGGL(k_sp_gemm<true>, dim3(L.pr_cnt), dim3(256), 0, STREAM, tasks(FB, L.pr_off), d_fd, d_pool, d_sp_work, XP, xs);
+    }
+    for (size_t l = bl.size(); l-- > 0;) {
+        const SpLevel &L = bl[l];
+        if (L.va_cnt > 0) {
+            if (S.sym_mode)
+                hipLaunchKernelGGL(k_sp_gather_sym, dim3(L.va_cnt), dim3(256), 0, STREAM, tasks(BB, L.va_off), d_fd, d_rows, d_diag, d_sp_work, (const double *)XP, xs);
+            else
+                hipLaunchKernelGGL(k_tr_gather_blk, dim3(L.va_cnt), dim3(256), 0, STREAM, tasks(BB, L.va_off), d_fd, d_rows, d_sp_work, (const double *)XP, xs);
+        }
+        if (L.pr_cnt > 0) {
+            if (S.sym_mode) // x1 = E^T [D^{-1} y1; x2]: the transposed product of the blocked transposed solves, sixteen columns of E per task
+                hipLaunchKernelGGL(k_tr_gemm_blk<false>, dim3(L.pr_cnt), dim3(256), 0, STREAM, tasks(BB, L.pr_off), d_fd, d_pool, d_sp_work, XP, xs);
+            else
+                hipLaunchKernelGGL(k_sp_gemm<false>, dim3(L.pr_cnt), dim3(256), 0, STREAM, tasks(BB, L.pr_off), d_fd, d_pool, d_sp_work, XP, xs);
+        }
+        if (L.small_cnt > 0) {
+            const int32_t ldu = L.pmax | 1;
+            hipLaunchKernelGGL(k_sp_bwd_small, dim3(L.small_cnt), dim3(64), sizeof(double) * (size_t)ldu * (size_t)L.fmax, STREAM, BB + L.small_off, d_fd, d_pool,
+                               d_rows, XP, xs, ldu);
+        }
+    }
+    return SUCCESSFUL_EXIT;
+}
+
+// x_sel(k, c) = (A^{-1} B)(sel_idx[k], c), column-major with ldx >= the number of rows returned (nsel, or n when sel_idx == nullptr).
+// Per block of up to SP_KB columns:
+//   mark     forward set = union of the root paths of the fronts of the non-zeros' permuted positions, backward set (once per call) = the
+//            same for the selected rows; a walk stops at the first front already marked: O(visited fronts)
+//   decide   share = (sum of p f over the forward set + the same over the backward set) / (2 sum over all fronts): the factor entries the
+//            pruned pass pair reads against a full one.  share > theta (HIPMF_PRUNE_MAX_SHARE, read per call; default 0.25 from the measured
+//            crossover), a one-column block on a factor whose pass pair reads less than HIPMF_PRUNE_MIN_BYTES (2e9), or
+//            a factor with replaced pivots: the columns are expanded into a dense block, solve() runs on it -- refinement and Krylov
+//            rescue as the handle has them -- and the rows are selected
+//   run      k_sp_begin (marks, zeros), k_sp_scatter_in (entry permutation and row scaling), the two passes, k_sp_gather_out (exit
+//            permutation and column scaling).  One unrefined pass pair: a residual needs all of x and all of A, which is what pruning avoids
+//            (MUMPS's ICNTL(20) / ICNTL(30) solves are unrefined too).
+// accumulate: pruned_blocks continues to count (inverse_entries calls this once per block of columns).
+int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx, const double *rhs_val, int32_t nsel,
+                             const int32_t *sel_idx, bool on_device, bool accumulate) {
+    if (!accumulate) pruned_blocks = 0;
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x_sel || !rhs_ptr) return ERROR_NULL_POINTER;
+    const int32_t n = S.n;
+    if (nrhs < 1 || (sel_idx && nsel < 1)) return ERROR_HIPMF_INVALID_VALUE;
+    const int32_t nout = sel_idx ? nsel : n;
+    if (ldx < nout) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    // host copies of the index arrays (the marking runs on the host), validated before anything reads through them
+    std::vector<int32_t> ptr_keep, idx_keep, sel_keep;
+    const int32_t *hp = rhs_ptr, *hi = rhs_idx, *hs = sel_idx;
+    if (on_device) {
+        ptr_keep.resize((size_t)nrhs + 1);
+        HIPC(hipMemcpy(ptr_keep.data(), rhs_ptr, sizeof(int32_t) * ((size_t)nrhs + 1), hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        hp = ptr_keep.data();
+    }
+    if (hp[0] < 0) return ERROR_HIPMF_INVALID_VALUE;
+    for (int32_t c = 0; c < nrhs; c++)
+        if (hp[c + 1] < hp[c]) return ERROR_HIPMF_INVALID_VALUE;
+    const int32_t e_first = hp[0], e_end = hp[nrhs];
+    const size_t nnz_b = (size_t)(e_end - e_first);
+    if (nnz_b > 0 && (!rhs_idx || !rhs_val)) return ERROR_NULL_POINTER;
+    if (on_device) {
+        idx_keep.resize(nnz_b);
+        if (nnz_b) HIPC(hipMemcpy(idx_keep.data(), rhs_idx + e_first, sizeof(int32_t) * nnz_b, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        hi = idx_keep.data() - e_first;
+        if (sel_idx) {
+            sel_keep.resize((size_t)nsel);
+            HIPC(hipMemcpy(sel_keep.data(), sel_idx, sizeof(int32_t) * (size_t)nsel, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+            hs = sel_keep.data();
+        }
+    }
+    for (int32_t c = 0; c < nrhs; c++)
+        for (int32_t e = hp[c]; e < hp[c + 1]; e++)
+            if (hi[e] < 0 || hi[e] >= n || (e > hp[c] && hi[e] <= hi[e - 1])) return ERROR_HIPMF_INVALID_VALUE;
+    if (hs)
+        for (int32_t k = 0; k < nsel; k++)
+            if (hs[k] < 0 || hs[k] >= n) return ERROR_HIPMF_INVALID_VALUE;
+    int32_t code = sp_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    HIPC(hipEventRecord((hipEvent_t)sp_ev0, STREAM), ERROR_HIP_SYNCHRONIZE);
+    // the arrays as the kernels read them: the caller's on the device, else copies in the reusable buffers (entry e of the caller at e - e_first)
+    const int32_t *d_idx = rhs_idx, *d_sel = sel_idx;
+    const double *d_val = rhs_val;
+    double *d_out = x_sel;
+    int64_t ostr = ldx;
+    int32_t shift = 0;
+    if (!on_device) {
+        HIPC(d_sp_idx.need(std::max<size_t>(nnz_b, 1)), ERROR_HIP_MALLOC);
+        HIPC(d_sp_val.need(std::max<size_t>(nnz_b, 1)), ERROR_HIP_MALLOC);
+        HIPC(d_sp_out.need((size_t)nout * (size_t)std::min<int32_t>(nrhs, SP_KB)), ERROR_HIP_MALLOC);
+        if (nnz_b) {
+            HIPC(hipMemcpyAsync(d_sp_idx.a, rhs_idx + e_first, sizeof(int32_t) * nnz_b, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipMemcpyAsync(d_sp_val.a, rhs_val + e_first, sizeof(double) * nnz_b, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        }
+        d_idx = d_sp_idx.a, d_val = d_sp_val.a, shift = e_first;
+        if (sel_idx) {
+            HIPC(d_sp_sel.need((size_t)nsel), ERROR_HIP_MALLOC);
+            HIPC(hipMemcpyAsync(d_sp_sel.a, sel_idx, sizeof(int32_t) * (size_t)nsel, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            d_sel = d_sp_sel.a;
+        }
+        ostr = nout;
+    }
+    double theta = 0.25, min_bytes_1col = 2e9; // (defaults from the measurement of profiles/r09_sparse_rhs.txt)
+    if (const char *e = getenv("HIPMF_PRUNE_MAX_SHARE")) theta = atof(e);
+    if (const char *e = getenv("HIPMF_PRUNE_MIN_BYTES")) min_bytes_1col = atof(e);
+    const bool never_pruned = n_perturbed > 0;
+    // the backward set and its lists: once per call
+    std::vector<int32_t> bset, fset, bbuf, fbuf;
+    std::vector<SpLevel> blv, flv;
+    double b_pf = 0.0;
+    bool bwd_ready = false;
+    auto prepare_bwd = [&]() -> int32_t {
+        if (bwd_ready) return SUCCESSFUL_EXIT;
+        const int32_t be = ++sp_epoch;
+        if (!hs) {
+            bset.resize((size_t)S.nsuper);
+            for (int32_t s = 0; s < S.nsuper; s++) bset[(size_t)s] = s, sp_stamp_b[(size_t)s] = be;
+            b_pf = sp_total_pf;
+        } else {
+            for (int32_t k = 0; k < nsel; k++)
+                for (int32_t s = S.sn_of[(size_t)sp_ipos_c[(size_t)hs[k]]]; s >= 0 && sp_stamp_b[(size_t)s] != be; s = S.sn_parent[(size_t)s])
+                    sp_stamp_b[(size_t)s] = be, bset.push_back(s), b_pf += (double)S.npiv(s) * (double)S.fsize(s);
+        }
+        sp_build_lists(bset, false, bbuf, blv);
+        HIPC(d_sp_bwd.need(std::max<size_t>(bbuf.size(), 1)), ERROR_HIP_MALLOC);
+        if (!bbuf.empty()) HIPC(hipMemcpyAsync(d_sp_bwd.a, bbuf.data(), sizeof(int32_t) * bbuf.size(), hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        bwd_ready = true;
+        return SUCCESSFUL_EXIT;
+    };
+    const dim3 gsel((nout + 255) / 256), b256(256);
+    for (int32_t j0 = 0; j0 < nrhs; j0 += SP_KB) {
+        const int32_t nk = std::min<int32_t>(SP_KB, nrhs - j0);
+        SpCols cols;
+        for (int32_t c = 0; c <= SP_KB; c++) cols.ptr[c] = hp[j0 + std::min(c, nk)] - shift;
+        const int32_t nz = cols.ptr[nk] - cols.ptr[0];
+        double *out_blk = on_device ? d_out + (int64_t)j0 * ostr : d_sp_out.a;
+        bool pruned = !never_pruned;
+        double f_pf = 0.0;
+        int32_t fe = 0;
+        if (pruned) {
+            code = prepare_bwd();
+            if (code != SUCCESSFUL_EXIT) return code;
+            fe = ++sp_epoch;
+            fset.clear();
+            for (int32_t e = hp[j0]; e < hp[j0 + nk]; e++)
+                for (int32_t s = S.sn_of[(size_t)sp_ipos_r[(size_t)hi[e]]]; s >= 0 && sp_stamp_f[(size_t)s] != fe; s = S.sn_parent[(size_t)s])
+                    sp_stamp_f[(size_t)s] = fe, fset.push_back(s), f_pf += (double)S.npiv(s) * (double)S.fsize(s);
+            pruned_share_last = sp_total_pf > 0.0 ? (f_pf + b_pf) / (2.0 * sp_total_pf) : 0.0;
+            if (pruned_share_last > theta) pruned = false;
+            // a block of ONE column on a factor whose full pass pair reads little: the dependency-driven single-column solve is faster than
+            // the pruned path's chain of level launches, however few fronts it visits (theta >= 1 asks for pruning regardless)
+            if (theta < 1.0 && nk == 1 && 16.0 * sp_total_pf < min_bytes_1col) pruned = false;
+        }
+        if (pruned) {
+            sp_build_lists(fset, true, fbuf, flv);
+            // k_sp_begin's list behind the forward lists: the forward set (marked), then the fronts of the backward set alone (~s)
+            const size_t begin_off = fbuf.size();
+            for (int32_t s : fset) fbuf.push_back(s);
+            for (int32_t s : bset)
+                if (sp_stamp_f[(size_t)s] != fe) fbuf.push_back(~s);
+            const size_t begin_cnt = fbuf.size() - begin_off;
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the previous block's launches read the buffer that is refilled now)
+            HIPC(d_sp_fwd.need(fbuf.size()), ERROR_HIP_MALLOC);
+            HIPC(hipMemcpyAsync(d_sp_fwd.a, fbuf.data(), sizeof(int32_t) * fbuf.size(), hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            double *XP = d_sp_xp;
+            hipLaunchKernelGGL(k_sp_begin, dim3((unsigned)begin_cnt), b256, 0, STREAM, d_sp_fwd.a + begin_off, d_fd, d_sp_mark, fe, XP, (int64_t)n);
+            if (nz > 0)
+                hipLaunchKernelGGL(k_sp_scatter_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols, nk, d_idx, d_val, (const int32_t *)d_sp_ipos_r, (const double *)d_rs, XP,
+                                   (int64_t)n);
+            code = run_pruned(XP, flv, blv);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_sp_gather_out, gsel, b256, 0, STREAM, nout, d_sel, (const int32_t *)d_sp_ipos_c, (const double *)d_cs, (const double *)XP, (int64_t)n,
+                               out_blk, ostr, nk);
+            pruned_fwd_fronts = (int64_t)fset.size(), pruned_bwd_fronts = (int64_t)bset.size();
+            pruned_bytes = (int64_t)(8.0 * (f_pf + b_pf));
+            pruned_blocks++;
+        } else {
+            // the ordinary solve on the expanded block, then the selection
+            HIPC(d_sp_dense.need(2 * (size_t)n * SP_KB), ERROR_HIP_MALLOC);
+            double *B = d_sp_dense.a, *X = B + (size_t)n * SP_KB;
+            HIPC(hipMemsetAsync(B, 0, sizeof(double) * (size_t)n * (size_t)nk, STREAM), ERROR_HIP_MEMCPY);
+            if (nz > 0)
+                hipLaunchKernelGGL(k_sp_scatter_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols, nk, d_idx, d_val, (const int32_t *)nullptr, (const double *)nullptr, B,
+                                   (int64_t)n);
+            code = solve(X, B, nk, n, true);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_sp_gather_out, gsel, b256, 0, STREAM, nout, d_sel, (const int32_t *)nullptr, (const double *)nullptr, (const double *)X, (int64_t)n, out_blk,
+                               ostr, nk);
+        }
+        if (!on_device)
+            for (int32_t c = 0; c < nk; c++)
+                HIPC(hipMemcpyAsync(x_sel + (int64_t)(j0 + c) * ldx, d_sp_out.a + (size_t)c * (size_t)nout, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, STREAM),
+                     ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    }
+    HIPC(hipEventRecord((hipEvent_t)sp_ev1, STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, (hipEvent_t)sp_ev0, (hipEvent_t)sp_ev1);
+    pruned_call_ms = accumulate ? pruned_call_ms + ms : ms;
+    times.solve_total_ms = pruned_call_ms; // (HIP events around the call's uploads, launches and copies: dstats[8])
+    return SUCCESSFUL_EXIT;
+}
+
+// values[e] = (A^{-1})(rows[e], cols[e]): the distinct columns sorted by the position their unit vector enters the elimination at
+// (neighbours share most of their root paths), blocks of at most SP_KB of them, right-hand sides = unit vectors, selected rows = the union
+// of the rows asked for in the block; one solve_sparse per block.
+int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values) {
+    pruned_blocks = 0;
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!rows || !cols || !values) return ERROR_NULL_POINTER;
+    if (nent < 1) return ERROR_HIPMF_INVALID_VALUE;
+    const int32_t n = S.n;
+    for (int32_t e = 0; e < nent; e++)
+        if (rows[e] < 0 || rows[e] >= n || cols[e] < 0 || cols[e] >= n) return ERROR_HIPMF_INVALID_VALUE;
+    {
+        DeviceScope dev_scope(device);
+        const int32_t code = sp_prepare();
+        if (code != SUCCESSFUL_EXIT) return code;
+    }
+    std::vector<int32_t> ent((size_t)nent);
+    for (int32_t e = 0; e < nent; e++) ent[(size_t)e] = e;
+    std::sort(ent.begin(), ent.end(), [&](int32_t a, int32_t b) {
+        const int32_t pa = sp_ipos_r[(size_t)cols[a]], pb = sp_ipos_r[(size_t)cols[b]];
+        return pa != pb ? pa < pb : (rows[a] != rows[b] ? rows[a] < rows[b] : a < b);
+    });
+    std::vector<int32_t> ptr, idx, sel;
+    std::vector<double> val, out;
+    pruned_call_ms = 0.0;
+    for (size_t e0 = 0; e0 < ent.size();) {
+        // entries [e0, e1): up to SP_KB distinct columns
+        ptr.assign(1, 0), idx.clear(), sel.clear();
+        size_t e1 = e0;
+        while (e1 < ent.size()) {
+            const int32_t c = cols[ent[e1]];
+            if (idx.empty() || idx.back() != c) {
+                if ((int32_t)idx.size() == SP_KB) break;
+                idx.push_back(c), ptr.push_back((int32_t)idx.size());
+            }
+            sel.push_back(rows[ent[e1]]);
+            e1++;
+        }
+        std::sort(sel.begin(), sel.end());
+        sel.erase(std::unique(sel.begin(), sel.end()), sel.end());
+        const int32_t nk = (int32_t)idx.size(), ns = (int32_t)sel.size();
+        val.assign((size_t)nk, 1.0);
+        out.assign((size_t)nk * (size_t)ns, 0.0);
+        const int32_t code = solve_sparse(out.data(), ns, nk, ptr.data(), idx.data(), val.data(), ns, sel.data(), false, true);
+        if (code != SUCCESSFUL_EXIT) return code;
+        int32_t c = -1, last = -1;
+        for (size_t e = e0; e < e1; e++) {
+            const int32_t en = ent[e];
+            if (cols[en] != last) last = cols[en], c++;
+            const int32_t k = (int32_t)(std::lower_bound(sel.begin(), sel.end(), rows[en]) - sel.begin());
+            values[en] = out[(size_t)c * (size_t)ns + (size_t)k];
+        }
+        e0 = e1;
+    }
     return SUCCESSFUL_EXIT;
 }
 

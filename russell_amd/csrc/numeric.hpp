@@ -138,10 +138,42 @@ struct SolverTransposed {
     PinnedArray<double> h_tnrm_blk;
 };
 
+// sparse right-hand sides / selected solution rows (built at the first solver_hipmf_solve_sparse; kernels_solve_pruned.hpp): the inverses
+// of the entry and exit permutations on both sides, one mark word per front, the block vector and the interleaved workspace of the pruned
+// pass pair (its own: the tagged words of d_work stay as the ordinary pass pair left them), and reusable buffers that only grow -- the
+// per-level lists of a block, the caller's compressed columns and selection, the staged result, the dense block of the fallback
+struct SolverPruned {
+    struct SpLevel {
+        int32_t small_off = 0, small_cnt = 0, pmax = 1, fmax = 1; // marked small fronts of the level (offsets in ints into the list buffer)
+        int32_t va_off = 0, va_cnt = 0;                           // SolveTasks: the big fronts' vectors (assembly forward, gather backward)
+        int32_t pr_off = 0, pr_cnt = 0;                           // SolveTasks: their products, SP_ROWS rows each
+    };
+    template <class T> struct Growing {
+        DeviceArray<T> a;
+        size_t cap = 0;
+        hipError_t need(size_t count) { // (contents are not kept)
+            if (count <= cap) return hipSuccess;
+            const hipError_t e = a.alloc(count + count / 2 + 64);
+            cap = e == hipSuccess ? count + count / 2 + 64 : 0;
+            return e;
+        }
+    };
+    bool sp_ready = false;
+    std::vector<int32_t> sp_ipos_r, sp_ipos_c; // row q of b enters at permuted position sp_ipos_r[q]; row q of x leaves from sp_ipos_c[q]
+    std::vector<int32_t> sp_stamp_f, sp_stamp_b; // per front: the epoch of the block (call) that last marked it forward (backward)
+    int32_t sp_epoch = 0;
+    double sp_total_pf = 0.0;                  // sum over the fronts of p f: what one pass reads, in entries
+    DeviceArray<int32_t> d_sp_ipos_r, d_sp_ipos_c, d_sp_mark;
+    DeviceArray<double> d_sp_xp, d_sp_work;
+    Growing<int32_t> d_sp_fwd, d_sp_bwd, d_sp_idx, d_sp_sel;
+    Growing<double> d_sp_val, d_sp_out, d_sp_dense;
+    EventOwner sp_ev0, sp_ev1; // around a call's device work (its time goes to times.solve_total_ms, dstats[8])
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed {
+struct SolverDevice : SolverTransposed, SolverPruned {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -272,6 +304,20 @@ class Solver : public SolverDevice {
     // (kernels_error_analysis_complex.hpp; the caller has checked the pairing of the even rows), see numeric.cpp
     int32_t error_analysis_complex(const double *xbar, const double *rhs, double *out, int32_t option);
     int32_t download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> &ci); // host copies of the stored CSR pattern of A
+    // Sparse right-hand sides and selected rows: x_sel(k, c) = (A^{-1} B)(sel_idx[k], c) for B (n x nrhs) in compressed-column form, 16
+    // columns per block through the pruned level-synchronous launches of kernels_solve_pruned.hpp -- one UNREFINED pass pair over the
+    // marked fronts.  sel_idx == nullptr: all n rows.  Blocks whose marked fronts read more than HIPMF_PRUNE_MAX_SHARE of what a full pass
+    // pair reads, and every block of a factor with replaced pivots, go through solve() on the expanded columns.  on_device: every array
+    // but the handle's own lives on the device.  See numeric.cpp.
+    int32_t solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx, const double *rhs_val, int32_t nsel,
+                         const int32_t *sel_idx, bool on_device, bool accumulate = false);
+    // values[e] = (A^{-1})(rows[e], cols[e]) (host arrays): blocks of at most 16 distinct columns, neighbours in the elimination order together
+    int32_t inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values);
+    int64_t pruned_fwd_fronts = 0, pruned_bwd_fronts = 0; // fronts the forward / backward pass of the last pruned block visited
+    int64_t pruned_blocks = 0;                            // blocks of the last solve_sparse / inverse_entries that ran pruned
+    int64_t pruned_bytes = 0;                             // 8 x the factor entries (p f per front and pass) those fronts hold
+    double pruned_call_ms = 0.0;                          // HIP-event time of the last solve_sparse / inverse_entries (also times.solve_total_ms)
+    double pruned_share_last = 0.0;                       // share of a full pass pair's factor entries the last block's marked fronts read
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
     int64_t krylov_iterations_t = 0; // FGMRES steps of the last transposed solve (krylov_iterations / krylov_last_relres stay the ordinary solve's)
@@ -486,6 +532,11 @@ class Solver : public SolverDevice {
     int32_t tr_rescue(double *tx, const double *tb, bool first_column); // FGMRES on one transposed column (the preconditioner: tr_pass)
     int32_t tr_prepare_blocked();
     int32_t run_transposed_blocked(double *XP);
+    int32_t sp_prepare();
+    // per-level lists of the fronts in `fronts` (any order) into `buf`, levels ascending: forward shapes (assembly + products over f rows)
+    // or backward shapes (gather + products over p rows)
+    void sp_build_lists(const std::vector<int32_t> &fronts, bool forward, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const;
+    int32_t run_pruned(double *XP, const std::vector<SpLevel> &fl, const std::vector<SpLevel> &bl);
 };
 
 } // namespace hipmf

@@ -166,6 +166,8 @@ def _L():
         "rh_linsolver_factorize": (cp, [vp, vp, pp(_RhParams)]),
         "rh_linsolver_solve": (cp, [vp, vp, i64, vp, i64, i32]),
         "rh_linsolver_solve_many": (cp, [vp, vp, vp, i64, i64]),
+        "rh_linsolver_solve_sparse": (cp, [vp, vp, i64, i64, vp, vp, vp, i64, vp, i32]),
+        "rh_linsolver_inverse_entries": (cp, [vp, vp, i64, vp, vp, i32]),
         "rh_linsolver_times": (None, [vp, pp(C.c_uint64)]),
         "rh_linsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(i32), pp(i32), pp(i32)]),
         "rh_linsolver_stats_json": (cp, [vp, vp, cp, vp, vp]),
@@ -486,6 +488,45 @@ class _Actual:
         _check(_L().rh_linsolver_solve_many(self._h, _ptr(x), _ptr(b), n, nrhs))
         return x
 
+    def solve_sparse(self, rhs_cols, select=None, verbose=False):
+        """Rows `select` (None: all) of A^{-1} B for a sparse B: `rhs_cols` is a list of (indices, values) pairs, one per column, or a
+        compressed-column triple (ptr, idx, val); row indices ascending within a column.  Returns an array of shape (ncol, nsel): row c
+        holds the selected entries of column c.  One unrefined pass pair over the fronts the non-zeros and the selected rows touch."""
+        if isinstance(rhs_cols, tuple) and len(rhs_cols) == 3 and np.ndim(rhs_cols[0]) == 1 and not isinstance(rhs_cols[0], tuple):
+            ptr, idx, val = (np.asarray(a) for a in rhs_cols)
+        else:
+            cols = [(np.asarray(i).ravel(), np.asarray(v, dtype=np.float64).ravel()) for i, v in rhs_cols]
+            for i, v in cols:
+                if i.size != v.size:
+                    raise StrError("the indices and values of a column of the sparse right-hand side must have the same length")
+            ptr = np.concatenate(([0], np.cumsum([i.size for i, _ in cols]))) if cols else np.zeros(1)
+            idx = np.concatenate([i for i, _ in cols]) if cols else np.zeros(0)
+            val = np.concatenate([v for _, v in cols]) if cols else np.zeros(0)
+        if ptr.size < 2:
+            raise StrError("the sparse right-hand side must have at least one column")
+        if idx.size != val.size or (idx.size and (np.any(idx != np.floor(idx)) or np.abs(idx).max() > 2**31 - 1)):
+            raise StrError("the dimension of the arrays of the sparse right-hand side is incorrect")
+        ptr, idx, val = np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(idx, dtype=np.int32), _vec(val)
+        sel = None if select is None else np.ascontiguousarray(select, dtype=np.int32).ravel()
+        if sel is not None and sel.size == 0:
+            raise StrError("the selection of rows must not be empty")
+        if self._ndim is None:
+            raise StrError("the function factorize must be called before solve")
+        ncol, nout = ptr.size - 1, (self._ndim if sel is None else sel.size)
+        x = np.zeros((ncol, nout))
+        _check(_L().rh_linsolver_solve_sparse(self._h, _ptr(x), x.size, ncol, _ptr(ptr), _ptr(idx), _ptr(val), 0 if sel is None else sel.size,
+                                              None if sel is None else _ptr(sel), int(verbose)))
+        return x
+
+    def inverse_entries(self, rows, cols, verbose=False):
+        """(A^{-1})[rows[e], cols[e]] for every e: any order, duplicates allowed."""
+        r, c = np.ascontiguousarray(rows, dtype=np.int32).ravel(), np.ascontiguousarray(cols, dtype=np.int32).ravel()
+        if r.size != c.size or r.size == 0:
+            raise StrError("the arrays of row and column indices must have the same, positive length")
+        v = np.zeros(r.size)
+        _check(_L().rh_linsolver_inverse_entries(self._h, _ptr(v), r.size, _ptr(r), _ptr(c), int(verbose)))
+        return v
+
     def get_ns(self):
         ns = (C.c_uint64 * 3)()
         _L().rh_linsolver_times(self._h, ns)
@@ -523,6 +564,14 @@ class LinSolver:
         h = _L().rh_linsolver_new(int(genie), C.byref(err))
         _check(err.value)
         self.actual = _Actual(h)
+
+    def solve_sparse(self, rhs_cols, select=None, verbose=False):
+        """extension of the HIPMF backend, see `actual.solve_sparse`"""
+        return self.actual.solve_sparse(rhs_cols, select, verbose)
+
+    def inverse_entries(self, rows, cols, verbose=False):
+        """extension of the HIPMF backend, see `actual.inverse_entries`"""
+        return self.actual.inverse_entries(rows, cols, verbose)
 
     @staticmethod
     def compute(genie, mat, rhs, params=None):
