@@ -46,6 +46,7 @@ extern "C" {
 #define ERROR_ALREADY_INITIALIZED 700000
 
 #define HIPMF_WARNING_SINGULAR_MATRIX 1
+#define HIPMF_WARNING_NOT_CONVERGED 2 /* solver_hipmf_solve_updated / _device only: the tolerance was not reached; x holds the best iterate */
 #define ERROR_HIP_MALLOC 100
 #define ERROR_HIP_MEMCPY 200
 #define ERROR_HIP_SYNCHRONIZE 300
@@ -184,6 +185,37 @@ int32_t solver_hipmf_solve_sparse_device(struct InterfaceHIPMF *solver, double *
  * (ERROR_HIPMF_INVALID_VALUE: nent < 1 or an index out of range); HIPMF_COUNTER_PRUNED_BLOCKS sums over the blocks. */
 int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *solver, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose);
 
+/* Solve with NEW matrix values on the KEPT factor (MKL PARDISO's "CGS/CG with the LU of a previous step", iparm[3]): solves
+ *   A_new x = rhs,  A_new = the structure given to initialize with the `values` given here,
+ * by right-preconditioned flexible GMRES started from x = 0, with the factor M of the last factorize as preconditioner.  For callers that
+ * change the values often and by little (a new step size scales the shift of gamma M - J, a Jacobian moved in a few rows) and would
+ * otherwise call solver_hipmf_factorize again.
+ *   mapped = 0: `values` in the CSR order of initialize, as for solver_hipmf_factorize (a symmetric-lower handle: its lower triangle);
+ *   mapped = 1: `values` hold the nnz_in numbers of solver_hipmf_set_value_map, as for solver_hipmf_factorize_mapped
+ *               (ERROR_HIPMF_INVALID_VALUE without a map).
+ *   rel_tol <= 0 selects 1e-12; max_steps <= 0 selects 4 x restart; steps and relres may be NULL.
+ * The values pass through the staging of a factorize (value-map gather, mirroring of an expanded symmetric-lower handle) into a buffer of
+ * their own: the values that iterative refinement and solver_hipmf_mat_vec_mul read, the factor and every statistic and counter of the
+ * ordinary solves (HIPMF_COUNTER_KRYLOV_ITERATIONS, istats[10], the timers) are the same before and after the call.
+ * Per step: z = M^{-1} v by ONE unrefined pass pair, w = A_new z by the streaming SpMV, classical Gram-Schmidt applied twice; V, Z and
+ * every vector of length ndim live on the device (HIPMF_COUNTER_UPDATED_BASIS_BYTES), the host reads 2 k + 4 doubles per step and solves
+ * the Hessenberg least-squares problem by Givens rotations.  Restart length 30, or HIPMF_UPDATED_RESTART (environment, 4 ... 200, read
+ * per call); when the bases do not fit in device memory the restart length is halved down to 4, then ERROR_HIP_MALLOC.
+ * After every cycle the TRUE residual b - A_new x is recomputed on the device: the call returns 0 once |r|_2 <= rel_tol |b|_2, and
+ * HIPMF_WARNING_NOT_CONVERGED when max_steps are used up or a cycle brought no gain (x: the best iterate).  *relres is always that
+ * recomputed residual over |b|_2, never the rotation estimate; *steps counts pass pairs.  rhs = 0 gives x = 0, 0 steps, status 0.
+ * Every real handle kind is served: general LU, matched / scaled, symmetric-lower L D L^T, symmetric-lower expanded, factors with
+ * replaced pivots (a perturbed factor is only a weaker preconditioner).  NOT covered: the complex twin, and several right-hand sides per
+ * call.  Results are bit-reproducible from call to call (no floating-point atomics).
+ * WHEN IT PAYS: NOT MEASURED yet -- no step time and no break-even against solver_hipmf_factorize_device + solver_hipmf_solve_device has been
+ * taken on an MI355X; tools/solve_updated.py produces the table (profiles/r10_solve_updated.txt).  No speed-up is claimed until it exists.
+ * _device: x, rhs and values are device pointers and no vector crosses the host link.  ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION,
+ * ERROR_NEED_FACTORIZATION in this order; ERROR_HIPMF_INVALID_VALUE for a non-finite rel_tol. */
+int32_t solver_hipmf_solve_updated(struct InterfaceHIPMF *solver, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                   int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
+int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped,
+                                          double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -284,6 +316,12 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_PRUNED_BWD_FRONTS 25 /* ... and its backward pass (sel_idx == NULL: every front) */
 #define HIPMF_COUNTER_PRUNED_BLOCKS 26     /* 16-column blocks of the last such call that ran pruned (0: everything went through the ordinary solve) */
 #define HIPMF_COUNTER_PRUNED_BYTES 27      /* bytes of factor entries (8 p f per front and pass) the marked fronts of the last pruned block hold, forward + backward */
+#define HIPMF_COUNTER_UPDATED_STEPS 28       /* steps (pass pairs) of the last solver_hipmf_solve_updated / _device */
+#define HIPMF_COUNTER_UPDATED_CYCLES 29      /* ... and its restart cycles */
+#define HIPMF_COUNTER_UPDATED_BASIS_BYTES 30 /* device bytes held for the bases V and Z of those calls (0 before the first) */
+#define HIPMF_COUNTER_UPDATED_PRECOND_US 31  /* HIPMF_UPDATED_TIMING=1 (environment, read per call; else 0): microseconds between HIP events around the pass pairs of the last such call ... */
+#define HIPMF_COUNTER_UPDATED_SPMV_US 32     /* ... its SpMVs ... */
+#define HIPMF_COUNTER_UPDATED_ARNOLDI_US 33  /* ... and its Gram-Schmidt / normalisation kernels (tools/solve_updated.py) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

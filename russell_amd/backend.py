@@ -171,6 +171,18 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_inverse_entries")
         return v
 
+    def solve_updated(self, rhs, values, mapped=False, rel_tol=0.0, max_steps=0, verbose=False):
+        """A_new x = rhs for the matrix with the structure of initialize and the `values` given here (mapped: the inputs of the installed
+        value map), by flexible GMRES on the device with the kept factor as right preconditioner.  Returns (x, steps, relres, status):
+        status 0 = converged, 2 = HIPMF_WARNING_NOT_CONVERGED (x is the best iterate); any other status raises."""
+        x = np.zeros(self.n)
+        steps, relres = C.c_int32(0), C.c_double(0.0)
+        code = self.lib.solver_hipmf_solve_updated(self.h, x, np.ascontiguousarray(rhs, dtype=np.float64), np.ascontiguousarray(values, dtype=np.float64),
+                                                   int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres), int(verbose))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_updated")
+        return x, int(steps.value), float(relres.value), code
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -194,7 +206,9 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33}
+
+    WARNING_NOT_CONVERGED = 2
 
     OPTIONS = {"matching": 0, "pivoting": 1, "hybrid_memory": 2, "error_estimates": 3, "condition_numbers": 4, "sym_recheck": 5}
 
@@ -294,3 +308,12 @@ class Hipmf:
         code = self.lib.solver_hipmf_solve_sparse_device(self.h, d_x_sel, int(ldx), int(nrhs), d_rhs_ptr, d_rhs_idx, d_rhs_val, int(nsel), d_sel_idx, 0)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_sparse_device")
+
+    def solve_updated_device(self, d_x, d_rhs, d_values, mapped=False, rel_tol=0.0, max_steps=0):
+        """solve_updated with x, rhs and values resident on the device; returns (steps, relres, status)"""
+        steps, relres = C.c_int32(0), C.c_double(0.0)
+        code = self.lib.solver_hipmf_solve_updated_device(self.h, d_x, d_rhs, d_values, int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps),
+                                                          C.byref(relres))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_updated_device")
+        return int(steps.value), float(relres.value), code

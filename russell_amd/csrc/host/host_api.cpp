@@ -746,6 +746,7 @@ struct Backend {
     decltype(&solver_hipmf_solve_many) solve_many = nullptr;
     decltype(&solver_hipmf_solve_sparse) solve_sparse = nullptr;
     decltype(&solver_hipmf_inverse_entries) inverse_entries = nullptr;
+    decltype(&solver_hipmf_solve_updated) solve_updated = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
     decltype(&solver_hipmf_factorize_mapped) factorize_mapped = nullptr;
     decltype(&solver_hipmf_get_stats) get_stats = nullptr;
@@ -803,6 +804,7 @@ bool load_backend() {
     BIND(solve_many, "solver_hipmf_solve_many")
     BIND(solve_sparse, "solver_hipmf_solve_sparse")
     BIND(inverse_entries, "solver_hipmf_inverse_entries")
+    BIND(solve_updated, "solver_hipmf_solve_updated")
     BIND(set_value_map, "solver_hipmf_set_value_map")
     BIND(factorize_mapped, "solver_hipmf_factorize_mapped")
     BIND(get_stats, "solver_hipmf_get_stats")
@@ -857,6 +859,7 @@ static int32_t hipmf_scaling(Scaling s) {
 StrError handle_hipmf_error_code(int32_t err) {
     switch (err) {
     case HIPMF_WARNING_SINGULAR_MATRIX: return "Error(1): Matrix is singular";
+    case HIPMF_WARNING_NOT_CONVERGED: return "Error(2): the iteration on the kept factorization did not converge (HIPMF solve_updated)";
     case ERROR_NULL_POINTER: return "Error: c-code returned null pointer (HIPMF)";
     case ERROR_MALLOC: return "Error: c-code failed to allocate memory (HIPMF)";
     case ERROR_VERSION: return "Error: c-code returned version error (HIPMF)";
@@ -1308,6 +1311,37 @@ StrError SolverHIPMF::inverse_entries(std::vector<double> &values, const std::ve
         if (rows[e] < 0 || (size_t)rows[e] >= initialized_ndim || cols[e] < 0 || (size_t)cols[e] >= initialized_ndim) return "an index of an entry of the inverse is outside range";
     uint64_t t0 = now_ns();
     int32_t status = g_backend.inverse_entries((InterfaceHIPMF *)solver, (int32_t)rows.size(), rows.data(), cols.data(), values.data(), verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// A_new x = rhs on the factor of the last factorize (solver_hipmf_solve_updated): `mat` has the structure of the factorised matrix and
+// new values.  Triplets in the order the value map was built from travel as they are (mapped); otherwise they are converted on the host
+// and a changed pattern is refused, as in factorize.  x is written also when the iteration did not converge (the best iterate).
+StrError SolverHIPMF::solve_updated(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps,
+                                    int32_t *steps, double *relres, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (x.size() != initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
+    if (mat.symmetric != initialized_sym) return "the updated matrix must be the factorized matrix with new values (symmetric differs)";
+    if (mat.nrow != initialized_ndim || mat.ncol != initialized_ndim) return "the updated matrix must be the factorized matrix with new values (ndim differs)";
+    if (mat.nnz != initialized_nnz) return "the updated matrix must be the factorized matrix with new values (nnz differs)";
+    if (!std::isfinite(rel_tol)) return "the relative tolerance must be a finite number";
+    const bool mapped = value_map_set && std::memcmp(map_i.data(), mat.indices_i.data(), sizeof(int32_t) * mat.nnz) == 0 &&
+                        std::memcmp(map_j.data(), mat.indices_j.data(), sizeof(int32_t) * mat.nnz) == 0;
+    CsrMatrix conv;
+    if (!mapped) {
+        conv = csr;
+        StrError e = conv.update_from_coo(mat);
+        if (e) return e;
+        const size_t nz0 = (size_t)csr.row_pointers[csr.nrow];
+        if (conv.row_pointers != csr.row_pointers || std::memcmp(conv.col_indices.data(), csr.col_indices.data(), sizeof(int32_t) * nz0) != 0)
+            return "the updated matrix must be the factorized matrix with new values (sparsity pattern differs)";
+    }
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.solve_updated((InterfaceHIPMF *)solver, x.data(), rhs.data(), mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol,
+                                             max_steps, steps, relres, verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1859,6 +1893,18 @@ const char *rh_linsolver_inverse_entries(void *h, double *values, int64_t nent, 
     std::vector<double> vv(rr.size());
     StrError e = a->inverse_entries(vv, rr, cc, verbose != 0);
     if (!e) std::copy(vv.begin(), vv.end(), values);
+    return e;
+}
+const char *rh_linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                       double *relres, int32_t verbose) {
+    RhSolver *s = (RhSolver *)h;
+    SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
+    if (!a) return "solve_updated is only available with Genie::Hipmf";
+    if (!coo || !x || !rhs) return "solve_updated needs a matrix, x and a right-hand side";
+    const std::vector<double> rr(rhs, rhs + (nr > 0 ? nr : 0));
+    std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
+    StrError e = a->solve_updated(xx, *(const CooMatrix *)coo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
+    if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
 void rh_linsolver_times(void *h, uint64_t *ns3) {

@@ -220,6 +220,11 @@ class SolverHIPMF : public LinSolTrait {
                           const std::vector<int32_t> &select, bool verbose);
     // extension: values[e] = (A^{-1})(rows[e], cols[e]) (solver_hipmf_inverse_entries)
     StrError inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose);
+    // extension: A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES on the device
+    // (solver_hipmf_solve_updated); mat: the factorised matrix's structure with new values.  Status 2 (not converged) is an error string of
+    // its own; x then holds the best iterate.  rel_tol <= 0: 1e-12, max_steps <= 0: 4 x restart; steps / relres may be null.
+    StrError solve_updated(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
+                           double *relres, bool verbose);
     // extension: the backend's diagnostic counters (HIPMF_COUNTER_* of include/russell_hipmf.h; -1 before the first factorize)
     int64_t get_counter(int32_t which) const;
 

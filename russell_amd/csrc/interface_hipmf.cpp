@@ -546,6 +546,35 @@ int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *h, int32_t nent, con
     });
 }
 
+// Solve with new matrix values on the kept factor (Solver::solve_updated): flexible GMRES on the device, the factor of the last
+// factorize as right preconditioner.  Status codes in the order of solver_hipmf_solve_sparse: NULL pointers, initialize, factorize.
+static int32_t solve_updated_body(struct InterfaceHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                  int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    int32_t st = 0;
+    double rel = 0.0;
+    const int32_t code = h->solver.solve_updated(x, rhs, values, mapped != 0, rel_tol, max_steps, &st, &rel, on_device);
+    if (steps) *steps = st;
+    if (relres) *relres = rel;
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %s after %d step(s) in %lld cycle(s), |b - A x|_2 / |b|_2 = %.3e\n", who, code == SUCCESSFUL_EXIT ? "converged" : "NOT converged", st,
+               (long long)h->solver.updated_cycles, rel);
+    return code;
+}
+
+int32_t solver_hipmf_solve_updated(struct InterfaceHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                   int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_updated_body(h, x, rhs, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "solver_hipmf_solve_updated"); });
+}
+
+int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped, double rel_tol,
+                                          int32_t max_steps, int32_t *steps, double *relres) {
+    return guarded(h, [&]() { return solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_device"); });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -647,6 +676,12 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_PRUNED_BWD_FRONTS: return s.pruned_bwd_fronts;
     case HIPMF_COUNTER_PRUNED_BLOCKS: return s.pruned_blocks;
     case HIPMF_COUNTER_PRUNED_BYTES: return s.pruned_bytes;
+    case HIPMF_COUNTER_UPDATED_STEPS: return s.updated_steps;
+    case HIPMF_COUNTER_UPDATED_CYCLES: return s.updated_cycles;
+    case HIPMF_COUNTER_UPDATED_BASIS_BYTES: return s.updated_basis_bytes();
+    case HIPMF_COUNTER_UPDATED_PRECOND_US: return (int64_t)(1e3 * s.updated_ms[0]);
+    case HIPMF_COUNTER_UPDATED_SPMV_US: return (int64_t)(1e3 * s.updated_ms[1]);
+    case HIPMF_COUNTER_UPDATED_ARNOLDI_US: return (int64_t)(1e3 * s.updated_ms[2]);
     default: return -1;
     }
 }

@@ -19,6 +19,7 @@
 #include "kernels_solve_transpose.hpp"
 #include "kernels_solve_transpose_blocked.hpp"
 #include "kernels_solve_pruned.hpp"
+#include "kernels_krylov.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3344,6 +3345,230 @@ int32_t Solver::load_values(const double *values, bool on_device) {
     }
     hipLaunchKernelGGL(k_expand_values, dim3((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), dim3(256), 0, STREAM, nnz, d_emap, src, d_vals);
     return SUCCESSFUL_EXIT;
+}
+
+// ---- solve with new matrix values on the kept factor (solver_hipmf_solve_updated) ----
+// The callers of this backend change the VALUES of the matrix often and by little (a new step size scales the shift of gamma M - J, a
+// Jacobian moves in a few rows): instead of a factorisation the old factor M serves as RIGHT preconditioner of a flexible GMRES on
+// A_new x = b, started from x = 0.  Unlike the Krylov rescue above -- which stays as it is: host vectors, rare path -- everything of
+// length n lives on the device: per step z_k = M^{-1} v_k (one unrefined pass pair: solve_core on device pointers, default schedule, the
+// device gate as in any solve), w = A_new z_k (the stream SpMV on the operator's own value buffer), classical Gram-Schmidt twice (CGS2:
+// k_kry_dots + k_kry_reduce + k_kry_update, two rounds; all coefficients stay on the device), v_{k+1} = w / |w| (k_kry_scale).  The host
+// reads back ONE small record per step through pinned memory -- both coefficient sets (it adds them: the new Hessenberg column) and the
+// two squared norms, 2 k + 4 doubles -- applies the Givens rotations, and per cycle uploads y for x += Z y (k_kry_combine) and reads the
+// two sums of the recomputed true residual (k_kry_residual).  Non-finite numbers in a step's record (a direction the factor cannot give)
+// end the cycle with the directions before it, as in the rescue.  A cycle that does not lower the true residual is taken back and ends
+// the call: x is the best iterate.
+int32_t Solver::solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
+                              double *relres_out, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
+    DeviceScope dev_scope(device);
+    const int32_t n = S.n;
+    const int64_t nnz = S.nnz_a;
+    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
+    int32_t restart = 30;
+    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
+        const int v = atoi(e);
+        if (v >= 4 && v <= 200) restart = v;
+    }
+    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
+    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
+    updated_steps = updated_cycles = 0;
+    updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
+    if (steps_out) *steps_out = 0;
+    if (relres_out) *relres_out = 0.0;
+
+    // buffers: the bases grow with the restart length; when they do not fit the restart length is halved (down to 4)
+    int32_t m = std::max(4, std::min(restart, n));
+    if (up_m < m) {
+        d_up_V.reset(), d_up_Z.reset();
+        up_m = 0;
+        int32_t mm = m;
+        for (;; mm = std::max(4, mm / 2)) {
+            if (d_up_V.alloc((size_t)(mm + 1) * n) == hipSuccess && d_up_Z.alloc((size_t)mm * n) == hipSuccess) break;
+            d_up_V.reset(), d_up_Z.reset();
+            (void)hipGetLastError();
+            if (mm == 4) {
+                last_error = "solve_updated: no device memory for the Krylov bases";
+                return ERROR_HIP_MALLOC;
+            }
+        }
+        up_m = mm;
+    }
+    m = std::min(m, up_m);
+    const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
+    const int32_t rec_m = std::max(up_m, 200);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+    if (!d_up_vec) HIPC(d_up_vec.alloc(4 * (size_t)n), ERROR_HIP_MALLOC);
+    if (!d_up_part || up_rec_m < rec_m) {
+        HIPC(d_up_part.alloc(std::max((size_t)(rec_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1))), ERROR_HIP_MALLOC);
+        HIPC(d_up_rec.alloc(3 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        HIPC(h_up.alloc(3 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        up_rec_m = rec_m;
+    }
+    if (timing)
+        for (EventOwner &e : up_ev)
+            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
+    // the record: [0, 2 m + 2) both coefficient sets of the step; then the squared norms after the two rounds; the residual's |r|^2, |b|^2; y
+    double *const d_h = d_up_rec, *const d_nrm = d_up_rec + 2 * (size_t)rec_m + 2, *const d_res = d_nrm + 2, *const d_y = d_res + 2;
+    double *const h_rec = h_up, *const h_res = h_up + 2 * (size_t)rec_m + 4, *const h_y = h_res + 2;
+    double *const d_w = d_up_vec, *const d_r = d_up_vec + (size_t)n;
+    double *const d_xx = on_device ? x : d_up_vec + 2 * (size_t)n;
+    const double *d_bb = rhs;
+    const size_t nb = sizeof(double) * (size_t)n;
+
+    // the operator's values: the staging factorize gives its own (value-map gather, expansion of a mirrored lower triangle), into d_up_vals
+    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
+    if (mapped) {
+        const double *src = values;
+        if (!on_device) {
+            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            src = d_vin;
+        }
+        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
+    } else if (!d_emap) {
+        HIPC(hipMemcpyAsync(d_up_vals, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    } else {
+        const double *src = values;
+        if (!on_device) {
+            HIPC(hipMemcpyAsync(d_vlow, values, sizeof(double) * nnz_low, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            src = d_vlow;
+        }
+        hipLaunchKernelGGL(k_expand_values, gv, b256, 0, STREAM, nnz, d_emap, src, d_up_vals);
+    }
+    if (!on_device) {
+        HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        d_bb = d_up_vec + 3 * (size_t)n;
+    }
+    HIPC(hipMemsetAsync(d_xx, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+
+    const dim3 gk((unsigned)nblk);
+    // r = b - A_new x with its two sums on the host (one synchronisation)
+    auto residual = [&](double &rr, double &bb) -> int32_t {
+        hipLaunchKernelGGL(k_kry_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, d_xx, d_bb, d_r, d_up_part);
+        hipLaunchKernelGGL(k_kry_reduce, dim3(2), b256, 0, STREAM, d_up_part, spmv_blocks, d_res);
+        HIPC(hipMemcpyAsync(h_res, d_res, 2 * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        rr = h_res[0], bb = h_res[1];
+        return SUCCESSFUL_EXIT;
+    };
+    auto combine = [&](int32_t kk, double sign) -> int32_t { // x += sign Z y
+        for (int32_t j = 0; j < kk; j++) h_y[j] = sign * h_y[j];
+        HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * kk, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_kry_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, (const double *)d_up_Z, kk, (const double *)d_y);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (h_y may be rewritten)
+        return SUCCESSFUL_EXIT;
+    };
+    auto finish = [&](int32_t code, double relres) -> int32_t {
+        if (steps_out) *steps_out = (int32_t)updated_steps;
+        if (relres_out) *relres_out = relres;
+        if (!on_device) HIPC(hipMemcpy(x, d_xx, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+        return code;
+    };
+
+    double rr = 0.0, bb = 0.0;
+    int32_t code = residual(rr, bb);
+    if (code != SUCCESSFUL_EXIT) return code;
+    if (bb == 0.0) return finish(SUCCESSFUL_EXIT, 0.0); // x = 0
+    if (!std::isfinite(bb)) return finish(WARNING_NOT_CONVERGED, NAN);
+    const double bnorm = sqrt(bb);
+    double rnorm = sqrt(rr);
+
+    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
+    const PhaseTimes keep_times = times;
+    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done;
+    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
+    const std::vector<double> keep_omega = col_omega;
+    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
+    auto restore = [&]() {
+        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
+        col_omega = keep_omega;
+    };
+
+    std::vector<double> H((size_t)(m + 1) * m), cs((size_t)m), sn((size_t)m), g((size_t)m + 1);
+    while (rnorm > tol * bnorm && updated_steps < step_limit) {
+        updated_cycles++;
+        hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (const double *)d_res, (double *)d_up_V); // v_0 = r / |r|
+        std::fill(g.begin(), g.end(), 0.0);
+        g[0] = rnorm;
+        int32_t k = 0; // directions of this cycle that entered the least-squares problem
+        while (k < m && updated_steps < step_limit) {
+            double *const zk = d_up_Z + (size_t)k * n;
+            const double *const vk = d_up_V + (size_t)k * n;
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
+            code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
+            if (code != SUCCESSFUL_EXIT) break;
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
+            hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
+                               (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
+            const int32_t nv = k + 1;
+            for (int32_t round = 0; round < 2; round++) { // CGS2
+                double *const hr = d_h + (size_t)round * nv;
+                hipLaunchKernelGGL(k_kry_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_up_V, nv, (double *)d_up_part);
+                hipLaunchKernelGGL(k_kry_reduce, dim3(nv), b256, 0, STREAM, (const double *)d_up_part, nblk, hr);
+                hipLaunchKernelGGL(k_kry_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_up_V, nv, (const double *)hr, (double *)d_up_part);
+                hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_up_part, nblk, d_h + 2 * (size_t)nv + round);
+            }
+            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)(d_h + 2 * (size_t)nv + 1), d_up_V + (size_t)(k + 1) * n);
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
+            if (hipMemcpyAsync(h_rec, d_h, sizeof(double) * (2 * (size_t)nv + 2), hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+            if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
+            if (code != SUCCESSFUL_EXIT) break;
+            if (timing)
+                for (int t = 0; t < 3; t++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
+                }
+            bool finite = true;
+            for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(h_rec[j]);
+            if (!finite) break; // (leave the cycle with what there is)
+            updated_steps++;
+            for (int32_t j = 0; j < nv; j++) H[(size_t)j * m + k] = h_rec[j] + h_rec[nv + j];
+            const double hn = sqrt(h_rec[2 * nv + 1]);
+            H[(size_t)(k + 1) * m + k] = hn;
+            for (int32_t j = 0; j < k; j++) { // the Givens rotations so far
+                const double a = H[(size_t)j * m + k], b = H[(size_t)(j + 1) * m + k];
+                H[(size_t)j * m + k] = cs[(size_t)j] * a + sn[(size_t)j] * b;
+                H[(size_t)(j + 1) * m + k] = -sn[(size_t)j] * a + cs[(size_t)j] * b;
+            }
+            const double a = H[(size_t)k * m + k], b = H[(size_t)(k + 1) * m + k], d = std::hypot(a, b);
+            cs[(size_t)k] = d > 0.0 ? a / d : 1.0, sn[(size_t)k] = d > 0.0 ? b / d : 0.0;
+            H[(size_t)k * m + k] = d, H[(size_t)(k + 1) * m + k] = 0.0;
+            g[(size_t)k + 1] = -sn[(size_t)k] * g[(size_t)k];
+            g[(size_t)k] = cs[(size_t)k] * g[(size_t)k];
+            if (keep_verbose) fprintf(stderr, "hipmf: solve_updated: cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", (long long)updated_cycles, k + 1, fabs(g[(size_t)k + 1]), bnorm);
+            k++;
+            if (fabs(g[(size_t)k]) <= tol * bnorm || !(hn > 0.0)) break;
+        }
+        if (code != SUCCESSFUL_EXIT || k == 0) break;
+        for (int32_t i = k - 1; i >= 0; i--) { // back substitution
+            double t = g[(size_t)i];
+            for (int32_t j = i + 1; j < k; j++) t -= H[(size_t)i * m + j] * h_y[j];
+            h_y[i] = H[(size_t)i * m + i] != 0.0 ? t / H[(size_t)i * m + i] : 0.0;
+        }
+        code = combine(k, 1.0);
+        if (code != SUCCESSFUL_EXIT) break;
+        const double before = rnorm;
+        code = residual(rr, bb);
+        if (code != SUCCESSFUL_EXIT) break;
+        if (keep_verbose) fprintf(stderr, "hipmf: solve_updated: cycle %lld: |r| %.3e -> %.3e\n", (long long)updated_cycles, before, sqrt(rr));
+        if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
+            code = combine(k, -1.0);
+            if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
+            if (code == SUCCESSFUL_EXIT) rnorm = sqrt(rr);
+            break;
+        }
+        rnorm = sqrt(rr);
+    }
+    restore();
+    if (code != SUCCESSFUL_EXIT) return code;
+    return finish(rnorm <= tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
 }
 
 int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap) {

@@ -45,6 +45,7 @@ enum : int32_t {
     ERROR_HIPMF_NO_DEVICE = 1000,
     // numerical status, same value UMFPACK uses for a singular matrix (solver_umfpack.rs:492)
     WARNING_SINGULAR_MATRIX = 1,
+    WARNING_NOT_CONVERGED = 2, // solve_updated only: max_steps exhausted (or no further progress) above the tolerance
 };
 
 struct NumericOptions {
@@ -170,10 +171,22 @@ struct SolverPruned {
     EventOwner sp_ev0, sp_ev1; // around a call's device work (its time goes to times.solve_total_ms, dstats[8])
 };
 
+// solver_hipmf_solve_updated (allocated at its first call; kernels_krylov.hpp): the operator's values (the staging of a factorize, into a
+// buffer of their own: d_vals stays what the last factorize left), the two bases of the flexible GMRES, four n-vectors (w, r, x, b; the
+// device form uses the caller's x and b), the per-workgroup partial sums, the small device record of a step (both coefficient sets of
+// CGS2, the squared norms, the residual's two sums, y) and its pinned mirror
+struct SolverUpdated {
+    DeviceArray<double> d_up_vals, d_up_V, d_up_Z, d_up_vec, d_up_part, d_up_rec;
+    PinnedArray<double> h_up;
+    int32_t up_m = 0;       // restart length V and Z are allocated for (0: not allocated)
+    int32_t up_rec_m = 0;   // ... and the record / its mirror
+    EventOwner up_ev[4];    // HIPMF_UPDATED_TIMING=1: around the pass pair, the SpMV and the Arnoldi kernels of a step
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed, SolverPruned {
+struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -318,6 +331,16 @@ class Solver : public SolverDevice {
     int64_t pruned_bytes = 0;                             // 8 x the factor entries (p f per front and pass) those fronts hold
     double pruned_call_ms = 0.0;                          // HIP-event time of the last solve_sparse / inverse_entries (also times.solve_total_ms)
     double pruned_share_last = 0.0;                       // share of a full pass pair's factor entries the last block's marked fronts read
+    // A x = rhs for the matrix with the structure of initialize and the values given HERE, by right-preconditioned flexible GMRES with
+    // the kept factor as preconditioner; bases, Gram-Schmidt (CGS2) and residuals on the device, the Hessenberg least-squares problem on
+    // the host.  values: CSR order of the caller (mapped = false) or the inputs of the installed value map (mapped = true); on_device:
+    // x, rhs and values are device pointers.  Returns SUCCESSFUL_EXIT (converged) or WARNING_NOT_CONVERGED.  d_vals, the factor and the
+    // statistics of the ordinary solves are left as they were.  See numeric.cpp.
+    int32_t solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
+                          bool on_device);
+    int64_t updated_steps = 0, updated_cycles = 0; // of the last solve_updated
+    int64_t updated_basis_bytes() const { return up_m > 0 ? (int64_t)(2 * (int64_t)up_m + 1) * S.n * 8 : 0; }
+    double updated_ms[3] = {0.0, 0.0, 0.0}; // HIPMF_UPDATED_TIMING=1: HIP-event time of the last call's pass pairs, SpMVs, Arnoldi kernels
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
     int64_t krylov_iterations_t = 0; // FGMRES steps of the last transposed solve (krylov_iterations / krylov_last_relres stay the ordinary solve's)

@@ -25,6 +25,10 @@ __device__ __forceinline__ i32x4 ld_i32x4(const int *p) {
     typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
     return *(const i32x4u *)p;
 }
+__device__ __forceinline__ void st_f64x2(double *p, f64x2 v) { // global store to an 8-byte aligned address
+    typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));
+    *(f64x2u *)p = v;
+}
 __device__ __forceinline__ void st_lds_f64x2(double *p, f64x2 v) { *(f64x2 *)p = v; }
 __device__ __forceinline__ void st_lds_i32x4(int *p, i32x4 v) { *(i32x4 *)p = v; }
 
@@ -80,6 +84,25 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long ke
         best = k > best ? k : best;
     }
     return best;
+}
+
+// wave-wide sum of a double, the same bits in every lane and from run to run (every lane of the wavefront must be active): the 16-lane
+// rows by the DPP butterfly of wave_max_u64 (the two operands of a step are swapped between partners: a + b = b + a bit for bit), the four
+// row sums through v_readlane in index order
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#define HIPMF_DPP_ADD_STEP(ctrl)                                                        \
+    {                                                                                    \
+        const int lo = __double2loint(v), hi = __double2hiint(v);                        \
+        const int olo = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xf, 0xf, false);      \
+        const int ohi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, 0xf, false);      \
+        v += __hiloint2double(ohi, olo);                                                 \
+    }
+    HIPMF_DPP_ADD_STEP(0xB1)  // quad_perm [1,0,3,2]
+    HIPMF_DPP_ADD_STEP(0x4E)  // quad_perm [2,3,0,1]
+    HIPMF_DPP_ADD_STEP(0x141) // row_half_mirror
+    HIPMF_DPP_ADD_STEP(0x140) // row_mirror
+#undef HIPMF_DPP_ADD_STEP
+    return (wave_bcast(v, 0) + wave_bcast(v, 16)) + (wave_bcast(v, 32) + wave_bcast(v, 48));
 }
 
 // wave-wide maximum of a 32-bit key (result wave-uniform): four DPP max steps per 16-lane row, then the

@@ -168,6 +168,7 @@ def _L():
         "rh_linsolver_solve_many": (cp, [vp, vp, vp, i64, i64]),
         "rh_linsolver_solve_sparse": (cp, [vp, vp, i64, i64, vp, vp, vp, i64, vp, i32]),
         "rh_linsolver_inverse_entries": (cp, [vp, vp, i64, vp, vp, i32]),
+        "rh_linsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
         "rh_linsolver_times": (None, [vp, pp(C.c_uint64)]),
         "rh_linsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(i32), pp(i32), pp(i32)]),
         "rh_linsolver_stats_json": (cp, [vp, vp, cp, vp, vp]),
@@ -527,6 +528,19 @@ class _Actual:
         _check(_L().rh_linsolver_inverse_entries(self._h, _ptr(v), r.size, _ptr(r), _ptr(c), int(verbose)))
         return v
 
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+        """A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES on the device: `mat` is a CooMatrix with
+        the structure of the factorised matrix and new values.  Returns (x, steps, relres); raises StrError("Error(2): ...") when the
+        tolerance was not reached."""
+        if self._ndim is None:
+            raise StrError("the function factorize must be called before solve")
+        b = _vec(rhs)
+        x = np.zeros(self._ndim)
+        steps, relres = C.c_int32(0), C.c_double(0.0)
+        _check(_L().rh_linsolver_solve_updated(self._h, _ptr(x), x.size, mat._h, _ptr(b), b.size, float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres),
+                                               int(verbose)))
+        return x, int(steps.value), float(relres.value)
+
     def get_ns(self):
         ns = (C.c_uint64 * 3)()
         _L().rh_linsolver_times(self._h, ns)
@@ -572,6 +586,10 @@ class LinSolver:
     def inverse_entries(self, rows, cols, verbose=False):
         """extension of the HIPMF backend, see `actual.inverse_entries`"""
         return self.actual.inverse_entries(rows, cols, verbose)
+
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+        """extension of the HIPMF backend, see `actual.solve_updated`"""
+        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
 
     @staticmethod
     def compute(genie, mat, rhs, params=None):

@@ -15,6 +15,7 @@ struct i32x4 {
 };
 inline f64x2 ld_f64x2(const double *p) { return {p[0], p[1]}; }
 inline i32x4 ld_i32x4(const int *p) { return {p[0], p[1], p[2], p[3]}; }
+inline void st_f64x2(double *p, f64x2 v) { p[0] = v.x, p[1] = v.y; }
 inline void st_lds_f64x2(double *p, f64x2 v) { p[0] = v.x, p[1] = v.y; }
 inline void st_lds_i32x4(int *p, i32x4 v) { p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w; }
 
@@ -54,6 +55,12 @@ inline unsigned long long wave_max_u64(unsigned long long key) {
         key = o > key ? o : key;
     }
     return key;
+}
+
+// the product's order: butterfly inside the 16-lane rows, then the four rows in index order
+inline double wave_sum_f64(double v) {
+    for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off);
+    return (__shfl(v, 0) + __shfl(v, 16)) + (__shfl(v, 32) + __shfl(v, 48));
 }
 
 template <int ROWS = 4> inline unsigned wave_max_u32(unsigned key) {

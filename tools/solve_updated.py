@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""solver_hipmf_solve_updated_device against the caller's alternative (factorize_device + solve_device on the new values): the table of
+profiles/r10_solve_updated.txt.  Needs an MI355X.
+
+    python tools/solve_updated.py [--matrix 2d|3d|both] [--reps 9] [--warmup 2] [--tol 1e-10] [--out FILE]
+
+Per matrix (the 1M-DOF 2D 5-point Poisson matrix + I, the 100^3 7-point one + I, general storage: LU) and per change of the values
+    shift s1/s0 = 1.1, 2, 10     the diagonal shift of gamma M - J after a step-size change (s0 = 1)
+    rank 16                      all entries of 16 rows rescaled by factors in [0.5, 1.5]
+the line gives the steps of the call, the median wall time of a call (host clock around the blocking call, device-resident x, rhs and
+values), the time per step, its split into pass pair / SpMV / Arnoldi kernels (HIP events inside the driver, HIPMF_UPDATED_TIMING=1, taken
+in calls of their own: the events are not part of the timed calls), and the median wall time of solver_hipmf_factorize_device +
+solver_hipmf_solve_device with the same new values on a second handle (default refinement).  Those two entry points are not touched by
+the solve_updated change, so the second column is what the parent commit does.  break-even = alternative / time per step."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from russell_amd import problems as P  # noqa: E402
+from russell_amd.backend import Hipmf  # noqa: E402
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def run(name, n, rp, ci, v, args, out):
+    diag = np.repeat(np.arange(n), np.diff(rp)) == ci
+    v0 = v + 1.0 * diag
+    rng = np.random.default_rng(5)
+    rows = rng.choice(n, 16, replace=False)
+    vr = v0.copy()
+    for i in rows:
+        vr[rp[i]:rp[i + 1]] *= rng.uniform(0.5, 1.5, rp[i + 1] - rp[i])
+    cases = [("shift 1.1", v + 1.1 * diag), ("shift 2", v + 2.0 * diag), ("shift 10", v + 10.0 * diag), ("rank 16", vr)]
+    s, alt = Hipmf(), Hipmf()
+    for h in (s, alt):
+        assert h.initialize(n, rp, ci) == 0
+    assert s.factorize(v0) == 0 and alt.factorize(v0) == 0
+    b = rng.standard_normal(n)
+    d_x, d_b, d_v = s.dev_alloc(8 * n), s.dev_alloc(8 * n), s.dev_alloc(8 * v0.size)
+    s.h2d(d_b, b)
+    st = s.stats()
+    out("%s: n = %d, nnz = %d, factor %.0f MB; tolerance %.0e, restart 30" % (name, n, v.size, 8e-6 * (st["nnz_l"] + st["nnz_u"]), args.tol))
+    out("  %-10s %5s %9s %9s | %8s %8s %8s | %12s %10s" % ("change", "steps", "ms/call", "ms/step", "passpair", "spmv", "arnoldi", "refactor+solve", "break-even"))
+    for label, v1 in cases:
+        s.h2d(d_v, v1)
+        res = {}
+
+        def call():
+            res["r"] = s.solve_updated_device(d_x, d_b, d_v, rel_tol=args.tol)
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        med, lo, hi = timed(call, args.reps, args.warmup)
+        steps, relres, status = res["r"]
+        os.environ["HIPMF_UPDATED_TIMING"] = "1"
+        parts = []
+        for _ in range(3):
+            call()
+            parts.append([s.counter(k) / 1e3 / max(steps, 1) for k in ("updated_precond_us", "updated_spmv_us", "updated_arnoldi_us")])
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        parts = np.median(np.array(parts), axis=0)
+
+        def alternative():
+            alt.factorize_device(d_v)
+            alt.solve_device(d_x, d_b)
+        amed, alo, ahi = timed(alternative, args.reps, args.warmup)
+        per_step = med / max(steps, 1)
+        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %12.3f %10.1f   (status %d, relres %.1e; call %.3f-%.3f, alternative %.3f-%.3f ms)" %
+            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, lo, hi, alo, ahi))
+    for p in (d_x, d_b, d_v):
+        s.dev_free(p)
+    s.close()
+    alt.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--matrix", default="both", choices=["2d", "3d", "both"])
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--tol", type=float, default=1e-10)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = []
+
+    def out(line):
+        print(line, flush=True)
+        lines.append(line)
+    out("solve_updated_device against factorize_device + solve_device, one MI355X; median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
+    if args.matrix in ("2d", "both"):
+        run("poisson2d 1000 x 1000 + I", *P.poisson2d(1000), args, out)
+    if args.matrix in ("3d", "both"):
+        run("poisson3d 100^3 + I", *P.poisson3d(100), args, out)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
