@@ -205,8 +205,8 @@ int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *solver, int32_t nent
  * HIPMF_WARNING_NOT_CONVERGED when max_steps are used up or a cycle brought no gain (x: the best iterate).  *relres is always that
  * recomputed residual over |b|_2, never the rotation estimate; *steps counts pass pairs.  rhs = 0 gives x = 0, 0 steps, status 0.
  * Every real handle kind is served: general LU, matched / scaled, symmetric-lower L D L^T, symmetric-lower expanded, factors with
- * replaced pivots (a perturbed factor is only a weaker preconditioner).  NOT covered: the complex twin, and several right-hand sides per
- * call.  Results are bit-reproducible from call to call (no floating-point atomics).
+ * replaced pivots (a perturbed factor is only a weaker preconditioner).  NOT covered: the complex twin.  Several right-hand sides per
+ * call: solver_hipmf_solve_updated_many below.  Results are bit-reproducible from call to call (no floating-point atomics).
  * WHEN IT PAYS: NOT MEASURED yet -- no step time and no break-even against solver_hipmf_factorize_device + solver_hipmf_solve_device has been
  * taken on an MI355X; tools/solve_updated.py produces the table (profiles/r10_solve_updated.txt).  No speed-up is claimed until it exists.
  * _device: x, rhs and values are device pointers and no vector crosses the host link.  ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION,
@@ -215,6 +215,30 @@ int32_t solver_hipmf_solve_updated(struct InterfaceHIPMF *solver, double *x, con
                                    int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
 int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped,
                                           double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
+
+/* The same for nrhs right-hand sides: x and rhs are column-major ld x nrhs with ld >= ndim, as for solver_hipmf_solve_many; entries
+ * ndim ... ld-1 of every column of x are not written.  values, mapped, rel_tol and max_steps mean what they mean above, max_steps is a
+ * limit per column; HIPMF_UPDATED_RESTART and HIPMF_UPDATED_TIMING apply unchanged.  steps and relres: nrhs entries each, or NULL.
+ * Every column gets the contract of the single form: relres[c] is the recomputed true residual over |b_c|_2, steps[c] counts the pass
+ * pairs in which column c was still iterating, b_c = 0 gives x_c = 0, 0 steps and relres 0, a non-finite |b_c| gives x_c = 0 and relres
+ * NaN.  Returns 0 when every column reached the tolerance, HIPMF_WARNING_NOT_CONVERGED when at least one did not (its x_c is its best
+ * iterate; relres tells which).  nrhs == 1 is the single form, bit for bit.
+ * Method: blocks of 16 columns (the last may be narrower).  Inside a block every column runs its OWN flexible GMRES -- own bases, own
+ * Hessenberg matrix and rotations: no Krylov space is shared and no sum is ever formed across columns -- and the columns advance in
+ * lockstep: per block step ONE blocked pass pair (the factor is read once for the block), ONE pass over the matrix values and indices,
+ * Gram-Schmidt and normalisation batched over the columns, ONE host read of 16 (2 k + 4) doubles.  A column that converged, broke down
+ * or used up its steps is masked out of every kernel and rides through the pass pair as zeros; the block goes on until its last column is
+ * finished (blocks are neither compacted nor refilled).  The bases of the block form are its own, 61 x 16 x ndim doubles at restart 30
+ * (HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES): 7.8 GB at 1M unknowns; halved restart length down to 4 when they do not fit, then
+ * ERROR_HIP_MALLOC.  The guarantee of the single form holds: refinement's values, the factor, every statistic and counter of the ordinary
+ * solves and the results of later solves are what they were.  Bit-reproducible from call to call.
+ * WHEN IT PAYS: see DESIGN.md section 13 (tools/solve_updated.py --nrhs N, profiles/r11_solve_updated_many.txt).
+ * ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order; ERROR_HIPMF_INVALID_VALUE for nrhs < 1,
+ * ld < ndim, a non-finite rel_tol, or mapped without a map. */
+int32_t solver_hipmf_solve_updated_many(struct InterfaceHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values,
+                                        int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
+int32_t solver_hipmf_solve_updated_many_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                               const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
 
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
@@ -322,6 +346,9 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_UPDATED_PRECOND_US 31  /* HIPMF_UPDATED_TIMING=1 (environment, read per call; else 0): microseconds between HIP events around the pass pairs of the last such call ... */
 #define HIPMF_COUNTER_UPDATED_SPMV_US 32     /* ... its SpMVs ... */
 #define HIPMF_COUNTER_UPDATED_ARNOLDI_US 33  /* ... and its Gram-Schmidt / normalisation kernels (tools/solve_updated.py) */
+#define HIPMF_COUNTER_UPDATED_BLOCKS 34             /* 16-column blocks of the last solver_hipmf_solve_updated_many / _device (0: it was handed to the single form) */
+#define HIPMF_COUNTER_UPDATED_COLUMN_STEPS 35       /* sum of steps[c] of that call; with UPDATED_STEPS (there: blocked pass pairs, summed over blocks) it says how full they were */
+#define HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES 36  /* device bytes held for the block bases of those calls (UPDATED_BASIS_BYTES stays the single form's) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

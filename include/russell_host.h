@@ -116,6 +116,10 @@ const char *rh_linsolver_inverse_entries(void *solver, double *values, int64_t n
  * preconditioner; coo: the factorised matrix's structure with new values; "Error(2): ..." when the tolerance was not reached (x: best iterate) */
 const char *rh_linsolver_solve_updated(void *solver, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
                                        int32_t *steps, double *relres, int32_t verbose);
+/* the same for nrhs right-hand sides (solver_hipmf_solve_updated_many): x, rhs column-major n x nrhs, steps / relres nrhs entries;
+ * "Error(2): ..." when any column did not reach the tolerance (x, steps and relres are written then too) */
+const char *rh_linsolver_solve_updated_many(void *solver, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                            int32_t *steps, double *relres, int32_t verbose);
 void rh_linsolver_times(void *solver, uint64_t *ns3);
 void rh_linsolver_outputs(void *solver, double *det_coef, double *det_exp, double *rcond, int32_t *eff_ordering, int32_t *eff_scaling, int32_t *npert);
 const char *rh_linsolver_stats_json(void *solver, void *coo, const char *name, const double *x, const double *rhs);

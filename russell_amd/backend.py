@@ -183,6 +183,24 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_updated")
         return x, int(steps.value), float(relres.value), code
 
+    def solve_updated_many(self, rhs_colmajor, values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, verbose=False):
+        """solve_updated for the right-hand sides of an array of shape (nrhs, ld) as solve_many takes it, 16 columns per blocked pass pair,
+        every column its own iteration.  Returns (x, steps, relres, status): x in the layout of solve_many, steps and relres NumPy arrays
+        of nrhs entries, status 0 = every column converged, 2 = at least one did not (relres tells which); any other status raises."""
+        b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
+        ld = self.n if ld is None else int(ld)
+        if b.ndim != 2 or b.shape[1] != ld:
+            raise ValueError("solve_updated_many expects an array of shape (nrhs, ld) with ld = %d, got %r" % (ld, b.shape))
+        nrhs = b.shape[0]
+        x = np.zeros_like(b)
+        x[:, self.n:] = b[:, self.n:]
+        steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
+        code = self.lib.solver_hipmf_solve_updated_many(self.h, x, b, nrhs, ld, np.ascontiguousarray(values, dtype=np.float64), int(bool(mapped)), float(rel_tol),
+                                                        int(max_steps), steps.ctypes.data, relres.ctypes.data, int(verbose))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_updated_many")
+        return x, steps, relres, code
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -206,7 +224,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -317,3 +335,13 @@ class Hipmf:
         if code not in (0, self.WARNING_NOT_CONVERGED):
             raise self._err(code, "solver_hipmf_solve_updated_device")
         return int(steps.value), float(relres.value), code
+
+    def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None):
+        """solve_updated_many with x, rhs (column-major ld x nrhs) and values resident on the device; returns (steps, relres, status)"""
+        nrhs = int(nrhs)
+        steps, relres = np.zeros(max(nrhs, 1), np.int32), np.zeros(max(nrhs, 1))
+        code = self.lib.solver_hipmf_solve_updated_many_device(self.h, d_x, d_rhs, nrhs, int(ld or self.n), d_values, int(bool(mapped)), float(rel_tol),
+                                                               int(max_steps), steps.ctypes.data, relres.ctypes.data)
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_updated_many_device")
+        return steps[:nrhs], relres[:nrhs], code

@@ -747,6 +747,7 @@ struct Backend {
     decltype(&solver_hipmf_solve_sparse) solve_sparse = nullptr;
     decltype(&solver_hipmf_inverse_entries) inverse_entries = nullptr;
     decltype(&solver_hipmf_solve_updated) solve_updated = nullptr;
+    decltype(&solver_hipmf_solve_updated_many) solve_updated_many = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
     decltype(&solver_hipmf_factorize_mapped) factorize_mapped = nullptr;
     decltype(&solver_hipmf_get_stats) get_stats = nullptr;
@@ -805,6 +806,7 @@ bool load_backend() {
     BIND(solve_sparse, "solver_hipmf_solve_sparse")
     BIND(inverse_entries, "solver_hipmf_inverse_entries")
     BIND(solve_updated, "solver_hipmf_solve_updated")
+    BIND(solve_updated_many, "solver_hipmf_solve_updated_many")
     BIND(set_value_map, "solver_hipmf_set_value_map")
     BIND(factorize_mapped, "solver_hipmf_factorize_mapped")
     BIND(get_stats, "solver_hipmf_get_stats")
@@ -1342,6 +1344,39 @@ StrError SolverHIPMF::solve_updated(std::vector<double> &x, const CooMatrix &mat
     uint64_t t0 = now_ns();
     int32_t status = g_backend.solve_updated((InterfaceHIPMF *)solver, x.data(), rhs.data(), mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol,
                                              max_steps, steps, relres, verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// The same for nrhs right-hand sides (solver_hipmf_solve_updated_many): x and rhs column-major ndim x nrhs, steps and relres one entry per
+// column.  The error string of status 2 when any column did not converge; x, steps and relres are written then too.
+StrError SolverHIPMF::solve_updated_many(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol,
+                                         int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (nrhs < 1) return "the number of right-hand sides must be at least one";
+    if (rhs.size() != initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
+    if (x.size() != initialized_ndim * nrhs) return "the dimension of the vector of unknown values x is incorrect";
+    if (mat.symmetric != initialized_sym) return "the updated matrix must be the factorized matrix with new values (symmetric differs)";
+    if (mat.nrow != initialized_ndim || mat.ncol != initialized_ndim) return "the updated matrix must be the factorized matrix with new values (ndim differs)";
+    if (mat.nnz != initialized_nnz) return "the updated matrix must be the factorized matrix with new values (nnz differs)";
+    if (!std::isfinite(rel_tol)) return "the relative tolerance must be a finite number";
+    const bool mapped = value_map_set && std::memcmp(map_i.data(), mat.indices_i.data(), sizeof(int32_t) * mat.nnz) == 0 &&
+                        std::memcmp(map_j.data(), mat.indices_j.data(), sizeof(int32_t) * mat.nnz) == 0;
+    CsrMatrix conv;
+    if (!mapped) {
+        conv = csr;
+        StrError e = conv.update_from_coo(mat);
+        if (e) return e;
+        const size_t nz0 = (size_t)csr.row_pointers[csr.nrow];
+        if (conv.row_pointers != csr.row_pointers || std::memcmp(conv.col_indices.data(), csr.col_indices.data(), sizeof(int32_t) * nz0) != 0)
+            return "the updated matrix must be the factorized matrix with new values (sparsity pattern differs)";
+    }
+    steps.assign(nrhs, 0), relres.assign(nrhs, 0.0);
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.solve_updated_many((InterfaceHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim,
+                                                  mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(),
+                                                  verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1905,6 +1940,24 @@ const char *rh_linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo
     std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
     StrError e = a->solve_updated(xx, *(const CooMatrix *)coo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
     if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+const char *rh_linsolver_solve_updated_many(void *h, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                            int32_t *steps, double *relres, int32_t verbose) {
+    RhSolver *s = (RhSolver *)h;
+    SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
+    if (!a) return "solve_updated_many is only available with Genie::Hipmf";
+    if (!coo || !x || !rhs || !steps || !relres) return "solve_updated_many needs a matrix, x, right-hand sides, steps and relres";
+    const size_t len = n > 0 && nrhs > 0 ? (size_t)n * (size_t)nrhs : 0;
+    const std::vector<double> rr(rhs, rhs + len);
+    std::vector<double> xx(len), rel;
+    std::vector<int32_t> st;
+    StrError e = a->solve_updated_many(xx, *(const CooMatrix *)coo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0);
+    if (st.size() == (size_t)nrhs) { // (the backend ran: the best iterates and the per-column figures go out with the error string of status 2 too)
+        std::copy(xx.begin(), xx.end(), x);
+        std::copy(st.begin(), st.end(), steps);
+        std::copy(rel.begin(), rel.end(), relres);
+    }
     return e;
 }
 void rh_linsolver_times(void *h, uint64_t *ns3) {

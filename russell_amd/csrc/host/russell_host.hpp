@@ -225,6 +225,10 @@ class SolverHIPMF : public LinSolTrait {
     // its own; x then holds the best iterate.  rel_tol <= 0: 1e-12, max_steps <= 0: 4 x restart; steps / relres may be null.
     StrError solve_updated(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
                            double *relres, bool verbose);
+    // extension: the same for nrhs right-hand sides, 16 per blocked pass pair, every column its own iteration (solver_hipmf_solve_updated_many);
+    // x, rhs: column-major ndim x nrhs; steps / relres: resized to nrhs.  The error string of status 2 when any column did not converge.
+    StrError solve_updated_many(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol, int32_t max_steps,
+                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose);
     // extension: the backend's diagnostic counters (HIPMF_COUNTER_* of include/russell_hipmf.h; -1 before the first factorize)
     int64_t get_counter(int32_t which) const;
 

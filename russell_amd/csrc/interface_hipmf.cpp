@@ -575,6 +575,35 @@ int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *h, double *d_x,
     return guarded(h, [&]() { return solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_device"); });
 }
 
+// The same for nrhs columns (Solver::solve_updated_many): blocks of 16 columns, every column its own flexible GMRES, in lockstep.
+static int32_t solve_updated_many_body(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values, int32_t mapped,
+                                       double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_updated_many(x, rhs, nrhs, ld, values, mapped != 0, rel_tol, max_steps, steps, relres, on_device);
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %d column(s) %s: %lld column step(s) in %lld blocked pass pair(s), %lld cycle(s), %lld block(s)\n", who, nrhs,
+               code == SUCCESSFUL_EXIT ? "converged" : "NOT all converged", (long long)h->solver.updated_column_steps, (long long)h->solver.updated_steps,
+               (long long)h->solver.updated_cycles, (long long)h->solver.updated_blocks);
+    return code;
+}
+
+int32_t solver_hipmf_solve_updated_many(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values, int32_t mapped,
+                                        double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_updated_many_body(h, x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "solver_hipmf_solve_updated_many");
+    });
+}
+
+int32_t solver_hipmf_solve_updated_many_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld, const double *d_values,
+                                               int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
+    return guarded(h, [&]() {
+        return solve_updated_many_body(h, d_x, d_rhs, nrhs, ld, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_many_device");
+    });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -682,6 +711,9 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_UPDATED_PRECOND_US: return (int64_t)(1e3 * s.updated_ms[0]);
     case HIPMF_COUNTER_UPDATED_SPMV_US: return (int64_t)(1e3 * s.updated_ms[1]);
     case HIPMF_COUNTER_UPDATED_ARNOLDI_US: return (int64_t)(1e3 * s.updated_ms[2]);
+    case HIPMF_COUNTER_UPDATED_BLOCKS: return s.updated_blocks;
+    case HIPMF_COUNTER_UPDATED_COLUMN_STEPS: return s.updated_column_steps;
+    case HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES: return s.updated_block_basis_bytes();
     default: return -1;
     }
 }

@@ -20,6 +20,7 @@
 #include "kernels_solve_transpose_blocked.hpp"
 #include "kernels_solve_pruned.hpp"
 #include "kernels_krylov.hpp"
+#include "kernels_krylov_blocked.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3569,6 +3570,320 @@ int32_t Solver::solve_updated(double *x, const double *rhs, const double *values
     restore();
     if (code != SUCCESSFUL_EXIT) return code;
     return finish(rnorm <= tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
+}
+
+// ---- the same for a block of right-hand sides (solver_hipmf_solve_updated_many; kernels_krylov_blocked.hpp) ----
+// Every column runs the flexible GMRES above on its own -- own basis, own Hessenberg matrix, rotations and g on the host -- and the
+// columns of a block of KRYB_COLS advance in lockstep: per block step ONE blocked pass pair Z_k = M^{-1} V_k (solve_core on the C
+// contiguous columns of step k), ONE pass over the matrix (k_kryb_spmv), CGS2 and the normalisation batched over the columns, ONE host
+// read of the block's record, C (2 k + 4) doubles.  A column that is done for the cycle (rotation estimate at the tolerance, hn not
+// positive, a non-finite record, its step limit) is "parked": its bit leaves the mask every kernel takes and its column of V_{k+1} is
+// zeros.  At the end of a cycle (k == m or every column parked) every column gets its own back substitution over its own count of
+// directions, one combine and one residual launch serve the block; a column is finished for the call when its TRUE residual meets the
+// tolerance, when the cycle brought no gain (taken back) or when its steps are used up.  The block goes on with the others.
+int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol,
+                                   int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (nrhs < 1 || ld < S.n || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
+    if (nrhs == 1) {
+        const int32_t code = solve_updated(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+        updated_blocks = 0, updated_column_steps = updated_steps;
+        return code;
+    }
+    DeviceScope dev_scope(device);
+    const int32_t n = S.n;
+    const int64_t nnz = S.nnz_a;
+    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
+    int32_t restart = 30;
+    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
+        const int v = atoi(e);
+        if (v >= 4 && v <= 200) restart = v;
+    }
+    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
+    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
+    updated_steps = updated_cycles = updated_blocks = updated_column_steps = 0;
+    updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
+    for (int32_t c = 0; c < nrhs; c++) {
+        if (steps_out) steps_out[c] = 0;
+        if (relres_out) relres_out[c] = 0.0;
+    }
+
+    // buffers: bases for min(nrhs, 16) columns, wider when a later call is; the restart length is halved (down to 4) when they do not fit
+    const int32_t CW = std::min<int32_t>(nrhs, KRYB_COLS);
+    const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
+    int32_t m = std::max(4, std::min(restart, n));
+    if (ub_m < m || ub_cols < CW) {
+        const int32_t cols = std::max(ub_cols, CW);
+        d_ub_V.reset(), d_ub_Z.reset();
+        ub_m = ub_cols = 0;
+        int32_t mm = m;
+        for (;; mm = std::max(4, mm / 2)) {
+            if (d_ub_V.alloc((size_t)(mm + 1) * cols * n) == hipSuccess && d_ub_Z.alloc((size_t)mm * cols * n) == hipSuccess) break;
+            d_ub_V.reset(), d_ub_Z.reset();
+            (void)hipGetLastError();
+            if (mm == 4) {
+                last_error = "solve_updated_many: no device memory for the Krylov bases";
+                return ERROR_HIP_MALLOC;
+            }
+        }
+        const size_t pcol_new = std::max((size_t)(mm + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1));
+        const size_t rec_new = (size_t)cols * (3 * (size_t)mm + 4);
+        if (d_ub_vec.alloc(4 * (size_t)cols * n) != hipSuccess || d_ub_part.alloc(pcol_new * cols) != hipSuccess || d_ub_rec.alloc(rec_new) != hipSuccess ||
+            h_ub.alloc(rec_new) != hipSuccess || d_ub_cnt.alloc((size_t)cols) != hipSuccess || h_ub_cnt.alloc((size_t)cols) != hipSuccess) {
+            d_ub_V.reset(), d_ub_Z.reset();
+            (void)hipGetLastError();
+            return ERROR_HIP_MALLOC;
+        }
+        ub_m = mm, ub_cols = cols;
+    }
+    m = std::min(m, ub_m);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+    if (timing)
+        for (EventOwner &e : up_ev)
+            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
+    const int64_t pcol = (int64_t)std::max((size_t)(ub_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1)); // partial-sum slots of a column
+    // device record and its pinned mirror: the step's record, C (2 nv + 2) | the residuals' sums, 2 C | y, column c at c m
+    const size_t off_res = (size_t)ub_cols * (2 * (size_t)ub_m + 2), off_y = off_res + 2 * (size_t)ub_cols;
+    double *const d_rec = d_ub_rec, *const d_res = d_ub_rec + off_res, *const d_y = d_ub_rec + off_y;
+    double *const h_rec = h_ub, *const h_res = h_ub + off_res, *const h_y = h_ub + off_y;
+    const size_t nb = sizeof(double) * (size_t)n;
+
+    // the operator's values, once per call, exactly as in solve_updated
+    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
+    if (mapped) {
+        const double *src = values;
+        if (!on_device) {
+            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            src = d_vin;
+        }
+        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
+    } else if (!d_emap) {
+        HIPC(hipMemcpyAsync(d_up_vals, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    } else {
+        const double *src = values;
+        if (!on_device) {
+            HIPC(hipMemcpyAsync(d_vlow, values, sizeof(double) * nnz_low, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            src = d_vlow;
+        }
+        hipLaunchKernelGGL(k_expand_values, gv, b256, 0, STREAM, nnz, d_emap, src, d_up_vals);
+    }
+
+    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
+    const PhaseTimes keep_times = times;
+    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done, keep_groups_last = block_groups_last;
+    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
+    const std::vector<double> keep_omega = col_omega;
+    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
+    auto restore = [&]() {
+        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
+        block_groups_last = keep_groups_last;
+        col_omega = keep_omega;
+    };
+
+    bool all_converged = true;
+    int32_t code = SUCCESSFUL_EXIT;
+    std::vector<double> H, cs, sn, g; // per column c: H at c (m + 1) m, cs / sn at c m, g at c (m + 1)
+    H.resize((size_t)KRYB_COLS * (m + 1) * m), cs.resize((size_t)KRYB_COLS * m), sn.resize((size_t)KRYB_COLS * m), g.resize((size_t)KRYB_COLS * (m + 1));
+    for (int32_t j0 = 0; j0 < nrhs && code == SUCCESSFUL_EXIT; j0 += KRYB_COLS) {
+        const int32_t C = std::min<int32_t>(KRYB_COLS, nrhs - j0);
+        const uint32_t all = (1u << C) - 1u;
+        const int64_t vstr = (int64_t)C * n; // between two basis vectors of one column
+        updated_blocks++;
+        double *const d_w = d_ub_vec, *const d_r = d_ub_vec + (size_t)C * n;
+        double *const d_xx = on_device ? x + (int64_t)j0 * ld : d_ub_vec + 2 * (size_t)ub_cols * n;
+        const double *const d_bb = on_device ? rhs + (int64_t)j0 * ld : d_ub_vec + 3 * (size_t)ub_cols * n;
+        const int64_t xstr = on_device ? ld : (int64_t)n;
+        if (!on_device)
+            for (int32_t c = 0; c < C && code == SUCCESSFUL_EXIT; c++)
+                if (hipMemcpyAsync(d_ub_vec + 3 * (size_t)ub_cols * n + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, hipMemcpyHostToDevice, STREAM) != hipSuccess)
+                    code = ERROR_HIP_MEMCPY;
+        if (code != SUCCESSFUL_EXIT) break;
+        const dim3 gk((unsigned)nblk, (unsigned)C);
+        hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, d_xx, xstr, 0u, all); // x = 0
+
+        // R_c = B_c - A_new X_c and its two sums for the columns of `mask`, on the host after one synchronisation
+        auto residual = [&](uint32_t mask) -> int32_t {
+            hipLaunchKernelGGL(k_kryb_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)d_xx,
+                               xstr, d_bb, xstr, d_r, C, mask, (double *)d_ub_part, pcol);
+            hipLaunchKernelGGL(k_kryb_reduce, dim3(2, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, spmv_blocks, mask, d_res, (int64_t)2);
+            HIPC(hipMemcpyAsync(h_res, d_res, 2 * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            return SUCCESSFUL_EXIT;
+        };
+        // X_c += Z_c y_c over the first kc[c] directions for the columns of `mask` (h_y, h_ub_cnt filled by the caller; no synchronisation:
+        // the residual that follows brings it)
+        auto combine = [&](uint32_t mask) -> int32_t {
+            HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * (size_t)C * m, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipMemcpyAsync(d_ub_cnt, h_ub_cnt, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            hipLaunchKernelGGL(k_kryb_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, xstr, (const double *)d_ub_Z, vstr, mask, (const int32_t *)d_ub_cnt, (const double *)d_y,
+                               (int64_t)m);
+            return SUCCESSFUL_EXIT;
+        };
+
+        // per column of the block
+        double bnorm[KRYB_COLS], rnorm[KRYB_COLS];
+        int32_t steps[KRYB_COLS], kc[KRYB_COLS];
+        bool nan_rhs[KRYB_COLS];
+        uint32_t done = 0; // finished for the rest of the call
+        code = residual(all);
+        if (code != SUCCESSFUL_EXIT) break;
+        for (int32_t c = 0; c < C; c++) {
+            const double rr = h_res[2 * c], bb = h_res[2 * c + 1];
+            steps[c] = 0, nan_rhs[c] = false, bnorm[c] = 0.0, rnorm[c] = 0.0;
+            if (bb == 0.0) done |= 1u << c; // x_c = 0
+            else if (!std::isfinite(bb)) done |= 1u << c, nan_rhs[c] = true;
+            else {
+                bnorm[c] = sqrt(bb), rnorm[c] = sqrt(rr);
+                if (!(rnorm[c] > tol * bnorm[c])) done |= 1u << c;
+            }
+        }
+        while (done != all) {
+            updated_cycles++;
+            // v_0 = r / |r| for the columns still at work, zeros for the others (d_res holds |r_c|^2 of every such column's last residual)
+            hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (int64_t)n, (const double *)d_res, (int64_t)2, (double *)d_ub_V, (int64_t)n,
+                               all & ~done, done);
+            uint32_t parked = done; // ... for the rest of this cycle
+            for (int32_t c = 0; c < C; c++) {
+                kc[c] = 0;
+                if ((done >> c) & 1u) continue;
+                std::fill(g.begin() + (size_t)c * (m + 1), g.begin() + (size_t)(c + 1) * (m + 1), 0.0);
+                g[(size_t)c * (m + 1)] = rnorm[c];
+            }
+            for (int32_t k = 0; k < m && parked != all; k++) {
+                const uint32_t act = all & ~parked;
+                double *const zk = d_ub_Z + (size_t)k * vstr;
+                const double *const vk = d_ub_V + (size_t)k * vstr;
+                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
+                code = solve_core(zk, vk, C, n, true); // Z_k = M^{-1} V_k: one blocked pass pair
+                if (code != SUCCESSFUL_EXIT) break;
+                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
+                hipLaunchKernelGGL(k_kryb_spmv, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)zk, d_w, C,
+                                   act); // W = A_new Z_k
+                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
+                const int32_t nv = k + 1;
+                const int64_t rstr = 2 * (int64_t)nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
+                for (int32_t round = 0; round < 2; round++) { // CGS2
+                    double *const hr = d_rec + (size_t)round * nv;
+                    hipLaunchKernelGGL(k_kryb_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_ub_V, vstr, nv, act, (double *)d_ub_part, pcol);
+                    hipLaunchKernelGGL(k_kryb_reduce, dim3((unsigned)nv, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, hr, rstr);
+                    hipLaunchKernelGGL(k_kryb_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_ub_V, vstr, nv, act, (const double *)hr, rstr, (double *)d_ub_part, pcol);
+                    hipLaunchKernelGGL(k_kryb_reduce, dim3(1, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, d_rec + 2 * (size_t)nv + round, rstr);
+                }
+                double *const vnext = d_ub_V + (size_t)(k + 1) * vstr;
+                hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (int64_t)n, (const double *)(d_rec + 2 * (size_t)nv + 1), rstr, vnext, (int64_t)n,
+                                   act, parked);
+                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
+                if (hipMemcpyAsync(h_rec, d_rec, sizeof(double) * (size_t)C * rstr, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+                if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
+                if (code != SUCCESSFUL_EXIT) break;
+                if (timing)
+                    for (int t = 0; t < 3; t++) {
+                        float ms = 0.0f;
+                        if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
+                    }
+                uint32_t newly = 0;
+                bool counted = false;
+                for (int32_t c = 0; c < C; c++) {
+                    if (!((act >> c) & 1u)) continue;
+                    const double *const rec = h_rec + (size_t)c * rstr;
+                    bool finite = true;
+                    for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(rec[j]);
+                    if (!finite) { // (the column leaves the cycle with the directions before this one; the step is not counted for it)
+                        newly |= 1u << c;
+                        continue;
+                    }
+                    steps[c]++, updated_column_steps++, counted = true;
+                    double *const Hc = H.data() + (size_t)c * (m + 1) * m, *const csc = cs.data() + (size_t)c * m, *const snc = sn.data() + (size_t)c * m;
+                    double *const gc = g.data() + (size_t)c * (m + 1);
+                    for (int32_t j = 0; j < nv; j++) Hc[(size_t)j * m + k] = rec[j] + rec[nv + j];
+                    const double hn = sqrt(rec[2 * nv + 1]);
+                    Hc[(size_t)(k + 1) * m + k] = hn;
+                    for (int32_t j = 0; j < k; j++) { // the Givens rotations so far
+                        const double a = Hc[(size_t)j * m + k], b = Hc[(size_t)(j + 1) * m + k];
+                        Hc[(size_t)j * m + k] = csc[j] * a + snc[j] * b;
+                        Hc[(size_t)(j + 1) * m + k] = -snc[j] * a + csc[j] * b;
+                    }
+                    const double a = Hc[(size_t)k * m + k], b = Hc[(size_t)(k + 1) * m + k], d = std::hypot(a, b);
+                    csc[k] = d > 0.0 ? a / d : 1.0, snc[k] = d > 0.0 ? b / d : 0.0;
+                    Hc[(size_t)k * m + k] = d, Hc[(size_t)(k + 1) * m + k] = 0.0;
+                    gc[k + 1] = -snc[k] * gc[k];
+                    gc[k] = csc[k] * gc[k];
+                    if (keep_verbose)
+                        fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", j0 + c, (long long)updated_cycles, k + 1,
+                                fabs(gc[k + 1]), bnorm[c]);
+                    kc[c] = k + 1;
+                    if (fabs(gc[k + 1]) <= tol * bnorm[c] || !(hn > 0.0) || steps[c] >= step_limit) newly |= 1u << c;
+                }
+                if (counted) updated_steps++;
+                parked |= newly;
+                // a column parked by this step: its next basis vector (written before the host knew) becomes zeros
+                if (newly && parked != all && k + 1 < m)
+                    hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, vnext, (int64_t)n, 0u, newly);
+            }
+            if (code != SUCCESSFUL_EXIT) break;
+            // the end of the cycle: per column the back substitution over its own directions
+            uint32_t moved = 0;
+            for (int32_t c = 0; c < C; c++) {
+                h_ub_cnt[c] = 0;
+                if ((done >> c) & 1u) continue;
+                if (kc[c] == 0) { // (not one usable direction: the column ends with what it has)
+                    done |= 1u << c;
+                    continue;
+                }
+                const double *const Hc = H.data() + (size_t)c * (m + 1) * m, *const gc = g.data() + (size_t)c * (m + 1);
+                double *const yc = h_y + (size_t)c * m;
+                for (int32_t i = kc[c] - 1; i >= 0; i--) {
+                    double t = gc[i];
+                    for (int32_t j = i + 1; j < kc[c]; j++) t -= Hc[(size_t)i * m + j] * yc[j];
+                    yc[i] = Hc[(size_t)i * m + i] != 0.0 ? t / Hc[(size_t)i * m + i] : 0.0;
+                }
+                h_ub_cnt[c] = kc[c];
+                moved |= 1u << c;
+            }
+            if (!moved) continue;
+            code = combine(moved);
+            if (code == SUCCESSFUL_EXIT) code = residual(moved);
+            if (code != SUCCESSFUL_EXIT) break;
+            uint32_t back = 0;
+            for (int32_t c = 0; c < C; c++) {
+                if (!((moved >> c) & 1u)) continue;
+                const double now = sqrt(h_res[2 * c]);
+                if (keep_verbose) fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld: |r| %.3e -> %.3e\n", j0 + c, (long long)updated_cycles, rnorm[c], now);
+                if (!(now < rnorm[c])) { // no gain (or not a number): the column's cycle is taken back, x_c is the best iterate
+                    back |= 1u << c, done |= 1u << c;
+                    continue;
+                }
+                rnorm[c] = now;
+                if (!(rnorm[c] > tol * bnorm[c]) || steps[c] >= step_limit) done |= 1u << c;
+            }
+            if (back) {
+                for (int32_t c = 0; c < C; c++)
+                    if ((back >> c) & 1u)
+                        for (int32_t j = 0; j < kc[c]; j++) h_y[(size_t)c * m + j] = -h_y[(size_t)c * m + j];
+                code = combine(back);
+                if (code == SUCCESSFUL_EXIT) code = residual(back);
+                if (code != SUCCESSFUL_EXIT) break;
+                for (int32_t c = 0; c < C; c++)
+                    if ((back >> c) & 1u) rnorm[c] = sqrt(h_res[2 * c]);
+            }
+        }
+        if (code != SUCCESSFUL_EXIT) break;
+        for (int32_t c = 0; c < C; c++) {
+            const double rel = nan_rhs[c] ? NAN : (bnorm[c] > 0.0 ? rnorm[c] / bnorm[c] : 0.0);
+            if (steps_out) steps_out[j0 + c] = steps[c];
+            if (relres_out) relres_out[j0 + c] = rel;
+            if (nan_rhs[c] || (bnorm[c] > 0.0 && !(rnorm[c] <= tol * bnorm[c]))) all_converged = false;
+            if (!on_device && hipMemcpyAsync(x + (int64_t)(j0 + c) * ld, d_xx + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+        }
+        if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE; // (the staging blocks are the next block's)
+    }
+    restore();
+    if (code != SUCCESSFUL_EXIT) return code;
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    return all_converged ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
 }
 
 int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap) {

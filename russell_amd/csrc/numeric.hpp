@@ -181,6 +181,14 @@ struct SolverUpdated {
     int32_t up_m = 0;       // restart length V and Z are allocated for (0: not allocated)
     int32_t up_rec_m = 0;   // ... and the record / its mirror
     EventOwner up_ev[4];    // HIPMF_UPDATED_TIMING=1: around the pass pair, the SpMV and the Arnoldi kernels of a step
+    // solver_hipmf_solve_updated_many (kernels_krylov_blocked.hpp): bases of a block of columns, V[(k C + c) n + i], of their own -- the
+    // single form's stay as they are --, four n x C blocks (W, R, X, B; the device form uses the caller's x and b), partial sums per column,
+    // the step's record C (2 k + 4), the residuals' 2 C sums and the C m coefficients of the combine with its pinned mirror, the counts k_c
+    DeviceArray<double> d_ub_V, d_ub_Z, d_ub_vec, d_ub_part, d_ub_rec;
+    DeviceArray<int32_t> d_ub_cnt;
+    PinnedArray<double> h_ub;
+    PinnedArray<int32_t> h_ub_cnt;
+    int32_t ub_m = 0, ub_cols = 0; // restart length and columns the block buffers are allocated for (0: not allocated)
 };
 
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
@@ -341,6 +349,14 @@ class Solver : public SolverDevice {
     int64_t updated_steps = 0, updated_cycles = 0; // of the last solve_updated
     int64_t updated_basis_bytes() const { return up_m > 0 ? (int64_t)(2 * (int64_t)up_m + 1) * S.n * 8 : 0; }
     double updated_ms[3] = {0.0, 0.0, 0.0}; // HIPMF_UPDATED_TIMING=1: HIP-event time of the last call's pass pairs, SpMVs, Arnoldi kernels
+    // The same for nrhs columns (x, rhs: column-major ld x nrhs) in blocks of KRYB_COLS = 16: every column runs its own flexible GMRES, the
+    // columns of a block share the blocked pass pair, one pass over the matrix and the launches of a step.  steps / relres: nrhs entries on
+    // the host or nullptr.  SUCCESSFUL_EXIT when every column converged, else WARNING_NOT_CONVERGED.  nrhs == 1 is solve_updated.  After
+    // the call updated_steps counts blocked pass pairs and updated_cycles the cycles, both summed over the blocks.
+    int32_t solve_updated_many(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps,
+                               int32_t *steps, double *relres, bool on_device);
+    int64_t updated_blocks = 0, updated_column_steps = 0; // of the last solve_updated_many: 16-column blocks (0: single form), sum of the columns' steps
+    int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
     int64_t krylov_iterations_t = 0; // FGMRES steps of the last transposed solve (krylov_iterations / krylov_last_relres stay the ordinary solve's)

@@ -169,6 +169,7 @@ def _L():
         "rh_linsolver_solve_sparse": (cp, [vp, vp, i64, i64, vp, vp, vp, i64, vp, i32]),
         "rh_linsolver_inverse_entries": (cp, [vp, vp, i64, vp, vp, i32]),
         "rh_linsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
+        "rh_linsolver_solve_updated_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
         "rh_linsolver_times": (None, [vp, pp(C.c_uint64)]),
         "rh_linsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(i32), pp(i32), pp(i32)]),
         "rh_linsolver_stats_json": (cp, [vp, vp, cp, vp, vp]),
@@ -541,6 +542,21 @@ class _Actual:
                                                int(verbose)))
         return x, int(steps.value), float(relres.value)
 
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+        """solve_updated for the right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim), as solve_many takes them), 16 per blocked
+        pass pair, every column its own iteration.  Returns (x, steps, relres) with x in the shape of rhs_rows and one entry of steps and
+        relres per right-hand side; raises StrError("Error(2): ...") when any of them did not reach the tolerance."""
+        if self._ndim is None:
+            raise StrError("the function factorize must be called before solve")
+        b = _vec(rhs_rows)
+        if b.ndim != 2:
+            raise StrError("solve_updated_many expects an array of shape (nrhs, ndim)")
+        nrhs, n = b.shape
+        x = np.zeros_like(b)
+        steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
+        _check(_L().rh_linsolver_solve_updated_many(self._h, _ptr(x), mat._h, _ptr(b), n, nrhs, float(rel_tol), int(max_steps), _ptr(steps), _ptr(relres), int(verbose)))
+        return x, steps, relres
+
     def get_ns(self):
         ns = (C.c_uint64 * 3)()
         _L().rh_linsolver_times(self._h, ns)
@@ -590,6 +606,10 @@ class LinSolver:
     def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
         """extension of the HIPMF backend, see `actual.solve_updated`"""
         return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
+
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+        """extension of the HIPMF backend, see `actual.solve_updated_many`"""
+        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose)
 
     @staticmethod
     def compute(genie, mat, rhs, params=None):

@@ -11,7 +11,17 @@ the line gives the steps of the call, the median wall time of a call (host clock
 values), the time per step, its split into pass pair / SpMV / Arnoldi kernels (HIP events inside the driver, HIPMF_UPDATED_TIMING=1, taken
 in calls of their own: the events are not part of the timed calls), and the median wall time of solver_hipmf_factorize_device +
 solver_hipmf_solve_device with the same new values on a second handle (default refinement).  Those two entry points are not touched by
-the solve_updated change, so the second column is what the parent commit does.  break-even = alternative / time per step."""
+the solve_updated change, so the second column is what the parent commit does.  break-even = alternative / time per step.
+
+    python tools/solve_updated.py --nrhs N [--matrix ...] [--out profiles/r11_solve_updated_many.txt]
+
+The block form (profiles/r11_solve_updated_many.txt): per matrix and change of the values three median wall times from the same run, on N
+random device-resident columns:
+    (a) ONE solver_hipmf_solve_updated_many_device call,
+    (b) N solver_hipmf_solve_updated_device calls on the same columns (that code is not touched by the block form: what the parent offers),
+    (c) solver_hipmf_factorize_device + solver_hipmf_solve_device(nrhs = N) on a second handle,
+with the per-column step counts, UPDATED_STEPS (blocked pass pairs), UPDATED_COLUMN_STEPS and the split of (a) into pass pair / SpMV /
+Arnoldi kernels (HIP events, calls of their own).  The figure of merit is (a)/N against (b)/N."""
 import argparse
 import os
 import sys
@@ -86,27 +96,94 @@ def run(name, n, rp, ci, v, args, out):
     alt.close()
 
 
+def run_many(name, n, rp, ci, v, args, out):
+    nrhs = args.nrhs
+    diag = np.repeat(np.arange(n), np.diff(rp)) == ci
+    v0 = v + 1.0 * diag
+    rng = np.random.default_rng(5)
+    rows = rng.choice(n, 16, replace=False)
+    vr = v0.copy()
+    for i in rows:
+        vr[rp[i]:rp[i + 1]] *= rng.uniform(0.5, 1.5, rp[i + 1] - rp[i])
+    cases = [("shift 1.1", v + 1.1 * diag), ("shift 2", v + 2.0 * diag), ("shift 10", v + 10.0 * diag), ("rank 16", vr)]
+    s, alt = Hipmf(), Hipmf()
+    for h in (s, alt):
+        assert h.initialize(n, rp, ci) == 0
+    assert s.factorize(v0) == 0 and alt.factorize(v0) == 0
+    B = rng.standard_normal((nrhs, n))
+    d_x, d_b, d_v = s.dev_alloc(8 * n * nrhs), s.dev_alloc(8 * n * nrhs), s.dev_alloc(8 * v0.size)
+    s.h2d(d_b, B)
+    st = s.stats()
+    out("%s: n = %d, nnz = %d, factor %.0f MB; %d columns, tolerance %.0e, restart 30" % (name, n, v.size, 8e-6 * (st["nnz_l"] + st["nnz_u"]), nrhs, args.tol))
+    out("  %-10s | %9s %9s | %9s %9s | %7s | %12s | %6s %8s | %8s %8s %8s" % ("change", "(a) ms", "(a)/N", "(b) ms", "(b)/N", "(a)/(b)", "(c) refac+slv", "pairs", "colsteps",
+                                                                             "passpair", "spmv", "arnoldi"))
+    for label, v1 in cases:
+        s.h2d(d_v, v1)
+        res = {}
+
+        def blocked():
+            res["a"] = s.solve_updated_many_device(d_x, d_b, nrhs, d_v, rel_tol=args.tol)
+
+        def looped():
+            res["b"] = [s.solve_updated_device(d_x + 8 * n * c, d_b + 8 * n * c, d_v, rel_tol=args.tol) for c in range(nrhs)]
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        a_med, a_lo, a_hi = timed(blocked, args.reps, args.warmup)
+        steps, relres, status = res["a"]
+        pairs, colsteps, blocks = s.counter("updated_steps"), s.counter("updated_column_steps"), s.counter("updated_blocks")
+        b_med, b_lo, b_hi = timed(looped, args.reps, args.warmup)
+        b_steps = [r[0] for r in res["b"]]
+        os.environ["HIPMF_UPDATED_TIMING"] = "1"
+        parts = []
+        for _ in range(3):
+            blocked()
+            parts.append([s.counter(k) / 1e3 for k in ("updated_precond_us", "updated_spmv_us", "updated_arnoldi_us")])
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        parts = np.median(np.array(parts), axis=0)
+
+        def alternative():
+            alt.factorize_device(d_v)
+            alt.solve_device(d_x, d_b, nrhs=nrhs)
+        c_med, c_lo, c_hi = timed(alternative, args.reps, args.warmup)
+        out("  %-10s | %9.3f %9.3f | %9.3f %9.3f | %7.3f | %12.3f | %6d %8d | %8.3f %8.3f %8.3f" %
+            (label, a_med, a_med / nrhs, b_med, b_med / nrhs, a_med / b_med, c_med, pairs, colsteps, parts[0], parts[1], parts[2]))
+        out("      status %d / %s, max relres %.1e / %.1e; %d block(s); (a) %.3f-%.3f, (b) %.3f-%.3f, (c) %.3f-%.3f ms" %
+            (status, sorted(set(r[2] for r in res["b"])), float(np.max(relres)), max(r[1] for r in res["b"]), blocks, a_lo, a_hi, b_lo, b_hi, c_lo, c_hi))
+        out("      steps per column (a): %s" % " ".join(str(int(k)) for k in steps))
+        out("      steps per column (b): %s" % " ".join(str(int(k)) for k in b_steps))
+    for p in (d_x, d_b, d_v):
+        s.dev_free(p)
+    s.close()
+    alt.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--nrhs", type=int, default=0, help="N > 0: the block form on N columns against N single calls (see the module docstring)")
     ap.add_argument("--matrix", default="both", choices=["2d", "3d", "both"])
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     args = ap.parse_args()
     lines = []
 
     def out(line):
         print(line, flush=True)
         lines.append(line)
-    out("solve_updated_device against factorize_device + solve_device, one MI355X; median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
+    if args.nrhs > 0:
+        out("(a) one solve_updated_many_device call, (b) %d solve_updated_device calls, (c) factorize_device + solve_device(nrhs = %d), one MI355X; "
+            "median of %d after %d warm-up" % (args.nrhs, args.nrhs, args.reps, args.warmup))
+    else:
+        out("solve_updated_device against factorize_device + solve_device, one MI355X; median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
+    go = run_many if args.nrhs > 0 else run
     if args.matrix in ("2d", "both"):
-        run("poisson2d 1000 x 1000 + I", *P.poisson2d(1000), args, out)
+        go("poisson2d 1000 x 1000 + I", *P.poisson2d(1000), args, out)
     if args.matrix in ("3d", "both"):
-        run("poisson3d 100^3 + I", *P.poisson3d(100), args, out)
+        go("poisson3d 100^3 + I", *P.poisson3d(100), args, out)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+        with open(args.out, "a" if args.append else "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
