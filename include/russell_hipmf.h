@@ -205,8 +205,8 @@ int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *solver, int32_t nent
  * HIPMF_WARNING_NOT_CONVERGED when max_steps are used up or a cycle brought no gain (x: the best iterate).  *relres is always that
  * recomputed residual over |b|_2, never the rotation estimate; *steps counts pass pairs.  rhs = 0 gives x = 0, 0 steps, status 0.
  * Every real handle kind is served: general LU, matched / scaled, symmetric-lower L D L^T, symmetric-lower expanded, factors with
- * replaced pivots (a perturbed factor is only a weaker preconditioner).  NOT covered: the complex twin.  Several right-hand sides per
- * call: solver_hipmf_solve_updated_many below.  Results are bit-reproducible from call to call (no floating-point atomics).
+ * replaced pivots (a perturbed factor is only a weaker preconditioner).  The complex twin has a form of its own, in complex arithmetic
+ * (complex_solver_hipmf_solve_updated, further down).  Several right-hand sides per call: solver_hipmf_solve_updated_many below.  Results are bit-reproducible from call to call (no floating-point atomics).
  * WHEN IT PAYS: NOT MEASURED yet -- no step time and no break-even against solver_hipmf_factorize_device + solver_hipmf_solve_device has been
  * taken on an MI355X; tools/solve_updated.py produces the table (profiles/r10_solve_updated.txt).  No speed-up is claimed until it exists.
  * _device: x, rhs and values are device pointers and no vector crosses the host link.  ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION,
@@ -349,6 +349,7 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_UPDATED_BLOCKS 34             /* 16-column blocks of the last solver_hipmf_solve_updated_many / _device (0: it was handed to the single form) */
 #define HIPMF_COUNTER_UPDATED_COLUMN_STEPS 35       /* sum of steps[c] of that call; with UPDATED_STEPS (there: blocked pass pairs, summed over blocks) it says how full they were */
 #define HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES 36  /* device bytes held for the block bases of those calls (UPDATED_BASIS_BYTES stays the single form's) */
+#define HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC 37 /* complex handle: 1 when its last solve_updated / _device orthogonalised in complex arithmetic (0 before the first) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -465,6 +466,37 @@ int32_t complex_solver_hipmf_factorize_mapped(struct InterfaceComplexHIPMF *solv
 int32_t complex_solver_hipmf_get_stats(struct InterfaceComplexHIPMF *solver, int64_t *istats, double *dstats); /* istats[0..1]: complex n, nnz */
 /* the HIPMF_COUNTER_* values of solver_hipmf_get_counter for the complex twin's handle (-1: unknown counter / not initialized) */
 int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *solver, int32_t which);
+/* Solve with NEW complex values on the KEPT factor: solver_hipmf_solve_updated for the complex handle, with the same contract (rel_tol <= 0
+ * selects 1e-12, max_steps <= 0 selects 4 x restart, HIPMF_UPDATED_RESTART, the halved restart length, *relres the recomputed true residual
+ * over |b|_2, *steps the pass pairs, rhs = 0, non-finite |b|, status 0 / HIPMF_WARNING_NOT_CONVERGED, a cycle without gain taken back,
+ * bit-reproducible, no floating-point atomics, no side effects on the factor, refinement's values, the determinant, the statistics and
+ * counters of the ordinary solves or the bits of a later solve).  x, rhs: interleaved complex vectors (2 n doubles); values: interleaved
+ * complex numbers,
+ *   mapped = 0: the nnz stored entries in the CSR order of initialize (a complex-symmetric handle: its lower triangle);
+ *   mapped = 1: the nnz_in triplets of the value map set for this handle.
+ * The handle always carries a value map (identity or triplets) and this call does not swap it: mapped = 0 while the triplet map is
+ * installed, or mapped = 1 without one, is ERROR_HIPMF_INVALID_VALUE (last_error says which).
+ * Method: flexible GMRES in COMPLEX arithmetic on the interleaved vectors of the real-equivalent system.  Real GMRES on [a -b; b a] would
+ * minimise over real coefficients only -- a subset of the complex Krylov space, so never fewer steps, and 20 - 40 % more on the shifted
+ * matrices of Radau5 -- and every step is one pass pair over the real-equivalent factor.  Per step: one unrefined pass pair, the
+ * real-equivalent streaming SpMV on the staged values, classical Gram-Schmidt twice with complex coefficients <v, w> = sum conj(v_i) w_i
+ * (kernels_krylov_complex.hpp: two sums per basis vector, five basis vectors per pass), real norm and scaling; the host reads 4 k + 6
+ * doubles per step and keeps a complex Hessenberg matrix with complex Givens rotations.  V and Z are those of the real form for order 2 n:
+ * HIPMF_COUNTER_UPDATED_BASIS_BYTES = 61 x 2 n x 8 at restart 30.  HIPMF_COUNTER_UPDATED_STEPS / _CYCLES / _PRECOND_US / _SPMV_US /
+ * _ARNOLDI_US as for the real form; HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC is 1 after a call.
+ * Every complex handle kind is served: general, complex-symmetric lower, matched / scaled, HIPMF_COMPLEX_PAIRS=0 and factors with replaced
+ * pivots (flexible GMRES only needs M^{-1} v to be some vector: a factor that is not exactly complex-linear is a weaker preconditioner).
+ * No form for several right-hand sides.
+ * WHEN IT PAYS (tools/solve_updated.py --complex, one MI355X, one run, profiles/r12_solve_updated_complex.txt): on the 500 x 500 complex
+ * shifted grid a step costs 0.46 - 0.47 ms (pass pair 0.37, SpMV 0.03, Arnoldi kernels 0.04 - 0.05) and complex_solver_hipmf_factorize_mapped
+ * + complex_solver_hipmf_solve on the same new values 8.1 ms: break-even at 17 steps.  h -> h/2 takes 11 steps and 5.2 ms per call,
+ * h -> h/10 17 steps and 7.8 ms.
+ * ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order, then ERROR_HIPMF_INVALID_VALUE (a non-finite
+ * rel_tol, a `mapped` that does not name the map in force). */
+int32_t complex_solver_hipmf_solve_updated(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, const double *values, int32_t mapped,
+                                           double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_updated_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values,
+                                                  int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *solver);
 
 /* plain device-memory helpers so that callers need no HIP binding of their own */

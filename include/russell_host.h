@@ -96,6 +96,11 @@ const char *rh_clinsolver_factorize(void *solver, void *ccoo, const struct RhPar
 const char *rh_clinsolver_solve(void *solver, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose);
 /* A^T x = rhs (conjugate = 0) or A^H x = rhs (conjugate = 1) with the factor of A */
 const char *rh_clinsolver_solve_transpose(void *solver, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t conjugate, int32_t verbose);
+/* extension of the HIPMF backend (complex_solver_hipmf_solve_updated of russell_hipmf.h): A_new x = rhs with the factor of the last factorize
+ * as preconditioner of a flexible GMRES in complex arithmetic; ccoo: the factorised matrix's structure with new values; x, rhs interleaved;
+ * "Error(2): ..." when the tolerance was not reached (x: best iterate) */
+const char *rh_clinsolver_solve_updated(void *solver, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
+                                        int32_t *steps, double *relres, int32_t verbose);
 /* determinant = (det_re + i det_im) x 10^det_exp (LinSolParams.compute_determinant; complex_solver_umfpack.rs:411-414) */
 void rh_clinsolver_outputs(void *solver, double *det_re, double *det_im, double *det_exp, double *rcond, int32_t *npert);
 /* the eight values of mumps_stats (RINFOG(4..11)) of the last solve when LinSolParams.compute_error_estimates (entries 0 - 4) or

@@ -764,6 +764,7 @@ struct Backend {
     decltype(&complex_solver_hipmf_get_stats) zget_stats = nullptr;
     decltype(&solver_hipmf_get_counter) get_counter = nullptr;
     decltype(&complex_solver_hipmf_get_counter) zget_counter = nullptr;
+    decltype(&complex_solver_hipmf_solve_updated) zsolve_updated = nullptr;
     bool tried = false;
 };
 Backend g_backend;
@@ -823,6 +824,7 @@ bool load_backend() {
     BIND(zget_stats, "complex_solver_hipmf_get_stats")
     BIND(get_counter, "solver_hipmf_get_counter")
     BIND(zget_counter, "complex_solver_hipmf_get_counter")
+    BIND(zsolve_updated, "complex_solver_hipmf_solve_updated")
 #undef BIND
     g_backend.dl = dl;
     return true;
@@ -1246,6 +1248,55 @@ StrError ComplexSolverHIPMF::solve_transpose(std::vector<double> &x, const std::
     if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
     uint64_t t0 = now_ns();
     int32_t status = g_backend.zsolve_t((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), conjugate ? 1 : 0, verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// A_new x = rhs on the factor of the last factorize in complex arithmetic (complex_solver_hipmf_solve_updated): the rule of
+// SolverHIPMF::solve_updated.  Triplets in the order the value map was built from travel as they are; otherwise they are summed into the
+// CSR entries on the host and a changed pattern is refused.  The backend does not swap the handle's map for this call, so with the
+// triplet map installed the summed value of a CSR entry travels in the place of the entry's first triplet, zeros in the others.
+StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps,
+                                           int32_t *steps, double *relres, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (x.size() != 2 * initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
+    if (mat.symmetric != initialized_sym) return "the updated matrix must be the factorized matrix with new values (symmetric differs)";
+    if (mat.nrow != initialized_ndim || mat.ncol != initialized_ndim) return "the updated matrix must be the factorized matrix with new values (ndim differs)";
+    if (mat.nnz != initialized_nnz) return "the updated matrix must be the factorized matrix with new values (nnz differs)";
+    if (!std::isfinite(rel_tol)) return "the relative tolerance must be a finite number";
+    const bool same_order = value_map_set && std::memcmp(map_i.data(), mat.indices_i.data(), sizeof(int32_t) * mat.nnz) == 0 &&
+                            std::memcmp(map_j.data(), mat.indices_j.data(), sizeof(int32_t) * mat.nnz) == 0;
+    std::vector<double> conv;
+    if (!same_order) {
+        const size_t nent = zci.size();
+        std::vector<double> sum(2 * nent, 0.0);
+        std::vector<char> hit(nent, 0);
+        for (size_t k = 0; k < mat.nnz; k++) { // (COO order: the order in which to_csr adds the duplicates of an entry)
+            const int32_t i = mat.indices_i[k], j = mat.indices_j[k];
+            if (i < 0 || (size_t)i >= initialized_ndim) return "COO matrix: index out of range";
+            const auto r0 = zci.begin() + zrp[(size_t)i], r1 = zci.begin() + zrp[(size_t)i + 1];
+            const auto it = std::lower_bound(r0, r1, j);
+            if (it == r1 || *it != j) return "the updated matrix must be the factorized matrix with new values (sparsity pattern differs)";
+            const size_t c = (size_t)(it - zci.begin());
+            sum[2 * c] += mat.values[2 * k], sum[2 * c + 1] += mat.values[2 * k + 1], hit[c] = 1;
+        }
+        for (size_t c = 0; c < nent; c++)
+            if (!hit[c]) return "the updated matrix must be the factorized matrix with new values (sparsity pattern differs)";
+        if (value_map_set) {
+            conv.assign(2 * mat.nnz, 0.0);
+            for (size_t c = 0; c < nent; c++) {
+                const size_t t = (size_t)seg_idx[(size_t)seg_ptr[c]];
+                conv[2 * t] = sum[2 * c], conv[2 * t + 1] = sum[2 * c + 1];
+            }
+        } else {
+            conv.swap(sum);
+        }
+    }
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_updated((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), same_order ? mat.values.data() : conv.data(), value_map_set ? 1 : 0,
+                                              rel_tol, max_steps, steps, relres, verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1850,6 +1901,16 @@ const char *rh_clinsolver_solve_transpose(void *h, double *x, int64_t nx, const 
     std::vector<double> xx((size_t)nx), rr(rhs, rhs + nr);
     StrError e = s->s->solve_transpose(xx, rr, conjugate != 0, verbose != 0);
     if (!e) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+const char *rh_clinsolver_solve_updated(void *h, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                        double *relres, int32_t verbose) {
+    RhComplexSolver *s = (RhComplexSolver *)h;
+    if (!ccoo || !x || !rhs) return "solve_updated needs a matrix, x and a right-hand side";
+    const std::vector<double> rr(rhs, rhs + (nr > 0 ? nr : 0));
+    std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
+    StrError e = s->s->solve_updated(xx, *(const ComplexCooMatrix *)ccoo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
+    if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
 const char *rh_clinsolver_solve(void *h, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose) {

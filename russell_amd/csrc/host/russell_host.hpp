@@ -279,6 +279,11 @@ class ComplexSolverHIPMF {
     StrError solve(std::vector<double> &x, const std::vector<double> &rhs, bool verbose);
     // extension: A^T x = rhs (conjugate = false) or A^H x = rhs (conjugate = true)
     StrError solve_transpose(std::vector<double> &x, const std::vector<double> &rhs, bool conjugate, bool verbose);
+    // extension: A_new x = rhs with the factor of the last factorize as right preconditioner of a flexible GMRES in complex arithmetic
+    // (complex_solver_hipmf_solve_updated); mat: the factorised matrix's structure with new values.  Status 2 (not converged) is an error
+    // string of handle_hipmf_error_code; x then holds the best iterate.
+    StrError solve_updated(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
+                           double *relres, bool verbose);
     // complex_solver_mumps.rs:262-268: compute_condition_numbers -> 1 (all eight values), compute_error_estimates -> 2 (entries 0 - 4),
     // else 0, set by every factorize; solve then goes through complex_solver_hipmf_solve_with_error_analysis, and update_stats fills
     // mumps_stats (complex_solver_mumps.rs:429-436)

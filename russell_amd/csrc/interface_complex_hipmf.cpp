@@ -287,6 +287,43 @@ int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *h, double *x, c
     return guarded(h, [&]() { return c_solve_body(h, x, rhs, verbose); });
 }
 
+// Solve with new matrix values on the kept factor in complex arithmetic (Solver::solve_updated_complex).  The handle always carries a
+// signed value map -- identity after initialize / complex_solver_hipmf_factorize, the caller's triplets after set_value_map -- and this
+// call must not swap it (that would change what a later factorize_mapped reads): `mapped` has to name the map in force.
+static int32_t c_solve_updated_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                    int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if ((mapped != 0) != h->triplet_map) {
+        h->solver.last_error = mapped != 0 ? std::string(who) + ": mapped = 1 but no triplet map is installed (complex_solver_hipmf_set_value_map)"
+                                           : std::string(who) + ": mapped = 0 but the triplet map of complex_solver_hipmf_set_value_map is installed";
+        return ERROR_HIPMF_INVALID_VALUE;
+    }
+    h->solver.opt.verbose = verbose == 1;
+    int32_t st = 0;
+    double rel = 0.0;
+    const int32_t code = h->solver.solve_updated_complex(x, rhs, values, rel_tol, max_steps, &st, &rel, on_device);
+    if (steps) *steps = st;
+    if (relres) *relres = rel;
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %s after %d step(s) in %lld cycle(s), |b - A x|_2 / |b|_2 = %.3e\n", who, code == SUCCESSFUL_EXIT ? "converged" : "NOT converged", st,
+               (long long)h->solver.updated_cycles, rel);
+    return code;
+}
+
+int32_t complex_solver_hipmf_solve_updated(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                           int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_updated_body(h, x, rhs, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "complex_solver_hipmf_solve_updated"); });
+}
+
+int32_t complex_solver_hipmf_solve_updated_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped,
+                                                  double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
+    return guarded(h, [&]() {
+        return c_solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "complex_solver_hipmf_solve_updated_device");
+    });
+}
+
 // A^T z = c (conjugate = 0) or A^H z = c (conjugate = 1): the transpose of the real-equivalent form [a -b; b a] is the real-equivalent form
 // of A^H, so the real transposed solve of the 2n system IS the A^H solve; A^T is the same solve with the imaginary parts of c and z negated
 // on the way in and out (a device kernel).  Reference: umfpack_zi_solve's UMFPACK_At / UMFPACK_Aat systems (the complex shim calls it with
@@ -380,6 +417,13 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
     case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
     case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
+    case HIPMF_COUNTER_UPDATED_STEPS: return s.updated_steps;
+    case HIPMF_COUNTER_UPDATED_CYCLES: return s.updated_cycles;
+    case HIPMF_COUNTER_UPDATED_BASIS_BYTES: return s.updated_basis_bytes();
+    case HIPMF_COUNTER_UPDATED_PRECOND_US: return (int64_t)(1e3 * s.updated_ms[0]);
+    case HIPMF_COUNTER_UPDATED_SPMV_US: return (int64_t)(1e3 * s.updated_ms[1]);
+    case HIPMF_COUNTER_UPDATED_ARNOLDI_US: return (int64_t)(1e3 * s.updated_ms[2]);
+    case HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC: return s.updated_complex ? 1 : 0;
     default: return -1;
     }
 }

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <thread>
 #include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "kernels_solve_pruned.hpp"
 #include "kernels_krylov.hpp"
 #include "kernels_krylov_blocked.hpp"
+#include "kernels_krylov_complex.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3559,6 +3561,230 @@ int32_t Solver::solve_updated(double *x, const double *rhs, const double *values
         code = residual(rr, bb);
         if (code != SUCCESSFUL_EXIT) break;
         if (keep_verbose) fprintf(stderr, "hipmf: solve_updated: cycle %lld: |r| %.3e -> %.3e\n", (long long)updated_cycles, before, sqrt(rr));
+        if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
+            code = combine(k, -1.0);
+            if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
+            if (code == SUCCESSFUL_EXIT) rnorm = sqrt(rr);
+            break;
+        }
+        rnorm = sqrt(rr);
+    }
+    restore();
+    if (code != SUCCESSFUL_EXIT) return code;
+    return finish(rnorm <= tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
+}
+
+// ---- the same in complex arithmetic (complex_solver_hipmf_solve_updated; kernels_krylov_complex.hpp) ----
+// This Solver holds the real-equivalent form of order n = 2 nc of a complex matrix; its vectors are nc interleaved (re, im) pairs.  Real
+// GMRES on that system minimises over real coefficients only: its Krylov space is a subset of the complex one, so it never needs fewer
+// pass pairs than the iteration below and usually needs 20 - 40 % more.  The steps are those of solve_updated with the same buffers --
+// z_k = M^{-1} v_k (one unrefined pass pair), w = A_new z_k (the real-equivalent stream SpMV on d_up_vals), CGS2, v_{k+1} = w / |w| --
+// but the coefficients are complex: h_j = <v_j, w> = sum conj(v_j,i) w_i (k_zkry_dots: two sums per basis vector, k_kry_reduce over
+// 2 nv columns leaves them interleaved), w -= sum h_j v_j (k_zkry_update).  |w|^2 is the real sum over the n doubles and the
+// normalisation a real scaling, the residual's 2-norm that of the real-equivalent residual: k_kry_reduce, k_kry_scale and k_kry_residual
+// as they are.  The host reads 4 k + 6 doubles per step, keeps a complex Hessenberg matrix, applies complex Givens rotations (real c,
+// complex s) and uploads at most m complex y per cycle for x += Z y (k_zkry_combine).  The preconditioner only has to give SOME vector
+// (flexible GMRES): a factor that is not exactly complex-linear (HIPMF_COMPLEX_PAIRS=0, replaced pivots) is merely a weaker one.
+// The body is a copy of solve_updated on purpose: the real path keeps its launches and its bits.
+int32_t Solver::solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps_out,
+                                      double *relres_out, bool on_device) {
+    typedef std::complex<double> cplx;
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (nnz_in < 1 || (S.n & 1) || d_emap) return ERROR_HIPMF_INVALID_VALUE; // the complex handle: a value map, pairs, a general pattern
+    DeviceScope dev_scope(device);
+    const int32_t n = S.n;
+    const int64_t nnz = S.nnz_a;
+    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
+    int32_t restart = 30;
+    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
+        const int v = atoi(e);
+        if (v >= 4 && v <= 200) restart = v;
+    }
+    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
+    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
+    updated_steps = updated_cycles = 0;
+    updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
+    updated_complex = true;
+    if (steps_out) *steps_out = 0;
+    if (relres_out) *relres_out = 0.0;
+
+    // buffers: those of solve_updated (a complex basis vector is one real vector of n doubles); the restart length is limited by the
+    // complex order -- the Krylov space of an nc x nc complex matrix has at most nc dimensions
+    int32_t m = std::max(4, std::min(restart, n / 2));
+    if (up_m < m) {
+        d_up_V.reset(), d_up_Z.reset();
+        up_m = 0;
+        int32_t mm = m;
+        for (;; mm = std::max(4, mm / 2)) {
+            if (d_up_V.alloc((size_t)(mm + 1) * n) == hipSuccess && d_up_Z.alloc((size_t)mm * n) == hipSuccess) break;
+            d_up_V.reset(), d_up_Z.reset();
+            (void)hipGetLastError();
+            if (mm == 4) {
+                last_error = "solve_updated: no device memory for the Krylov bases";
+                return ERROR_HIP_MALLOC;
+            }
+        }
+        up_m = mm;
+    }
+    m = std::min(m, up_m);
+    const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
+    const int32_t rec_m = std::max(up_m, 200);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+    if (!d_up_vec) HIPC(d_up_vec.alloc(4 * (size_t)n), ERROR_HIP_MALLOC);
+    if (!d_up_part || up_zrec_m < rec_m || up_rec_m != up_zrec_m) { // (twice the slots and coefficients of the real form, which they also serve)
+        HIPC(d_up_part.alloc(std::max((size_t)(2 * rec_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1))), ERROR_HIP_MALLOC);
+        HIPC(d_up_rec.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        HIPC(h_up.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        up_rec_m = up_zrec_m = rec_m;
+    }
+    if (timing)
+        for (EventOwner &e : up_ev)
+            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
+    // the record: [0, 4 m + 2) both sets of complex coefficients of the step, then the squared norms after the two rounds; the
+    // residual's |r|^2, |b|^2; the complex y
+    double *const d_h = d_up_rec, *const d_res = d_up_rec + 4 * (size_t)rec_m + 2, *const d_y = d_res + 2;
+    double *const h_rec = h_up, *const h_res = h_up + 4 * (size_t)rec_m + 2, *const h_y = h_res + 2;
+    double *const d_w = d_up_vec, *const d_r = d_up_vec + (size_t)n;
+    double *const d_xx = on_device ? x : d_up_vec + 2 * (size_t)n;
+    const double *d_bb = rhs;
+    const size_t nb = sizeof(double) * (size_t)n;
+
+    // the operator's values: the gather through the signed value map that factorize_mapped runs, into d_up_vals
+    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
+    {
+        const double *src = values;
+        if (!on_device) {
+            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            src = d_vin;
+        }
+        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
+    }
+    if (!on_device) {
+        HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        d_bb = d_up_vec + 3 * (size_t)n;
+    }
+    HIPC(hipMemsetAsync(d_xx, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+
+    const dim3 gk((unsigned)nblk);
+    auto residual = [&](double &rr, double &bb) -> int32_t { // r = b - A_new x with its two sums on the host (one synchronisation)
+        hipLaunchKernelGGL(k_kry_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, d_xx, d_bb, d_r, d_up_part);
+        hipLaunchKernelGGL(k_kry_reduce, dim3(2), b256, 0, STREAM, d_up_part, spmv_blocks, d_res);
+        HIPC(hipMemcpyAsync(h_res, d_res, 2 * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        rr = h_res[0], bb = h_res[1];
+        return SUCCESSFUL_EXIT;
+    };
+    auto combine = [&](int32_t kk, double sign) -> int32_t { // x += sign Z y
+        for (int32_t j = 0; j < 2 * kk; j++) h_y[j] = sign * h_y[j];
+        HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * 2 * kk, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_zkry_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, (const double *)d_up_Z, kk, (const double *)d_y);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (h_y may be rewritten)
+        return SUCCESSFUL_EXIT;
+    };
+    auto finish = [&](int32_t code, double relres) -> int32_t {
+        if (steps_out) *steps_out = (int32_t)updated_steps;
+        if (relres_out) *relres_out = relres;
+        if (!on_device) HIPC(hipMemcpy(x, d_xx, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
+        HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+        return code;
+    };
+
+    double rr = 0.0, bb = 0.0;
+    int32_t code = residual(rr, bb);
+    if (code != SUCCESSFUL_EXIT) return code;
+    if (bb == 0.0) return finish(SUCCESSFUL_EXIT, 0.0); // x = 0
+    if (!std::isfinite(bb)) return finish(WARNING_NOT_CONVERGED, NAN);
+    const double bnorm = sqrt(bb);
+    double rnorm = sqrt(rr);
+
+    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
+    const PhaseTimes keep_times = times;
+    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done;
+    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
+    const std::vector<double> keep_omega = col_omega;
+    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
+    auto restore = [&]() {
+        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
+        col_omega = keep_omega;
+    };
+
+    std::vector<cplx> H((size_t)(m + 1) * m), sn((size_t)m), g((size_t)m + 1), y((size_t)m);
+    std::vector<double> cs((size_t)m);
+    while (rnorm > tol * bnorm && updated_steps < step_limit) {
+        updated_cycles++;
+        hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (const double *)d_res, (double *)d_up_V); // v_0 = r / |r|
+        std::fill(g.begin(), g.end(), cplx(0.0, 0.0));
+        g[0] = rnorm;
+        int32_t k = 0; // directions of this cycle that entered the least-squares problem
+        while (k < m && updated_steps < step_limit) {
+            double *const zk = d_up_Z + (size_t)k * n;
+            const double *const vk = d_up_V + (size_t)k * n;
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
+            code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
+            if (code != SUCCESSFUL_EXIT) break;
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
+            hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
+                               (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
+            const int32_t nv = k + 1;
+            for (int32_t round = 0; round < 2; round++) { // CGS2 with complex coefficients
+                double *const hr = d_h + (size_t)round * 2 * nv;
+                hipLaunchKernelGGL(k_zkry_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_up_V, nv, (double *)d_up_part);
+                hipLaunchKernelGGL(k_kry_reduce, dim3(2 * nv), b256, 0, STREAM, (const double *)d_up_part, nblk, hr);
+                hipLaunchKernelGGL(k_zkry_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_up_V, nv, (const double *)hr, (double *)d_up_part);
+                hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_up_part, nblk, d_h + 4 * (size_t)nv + round);
+            }
+            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)(d_h + 4 * (size_t)nv + 1), d_up_V + (size_t)(k + 1) * n);
+            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
+            if (hipMemcpyAsync(h_rec, d_h, sizeof(double) * (4 * (size_t)nv + 2), hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+            if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
+            if (code != SUCCESSFUL_EXIT) break;
+            if (timing)
+                for (int t = 0; t < 3; t++) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
+                }
+            bool finite = true;
+            for (int32_t j = 0; j < 4 * nv + 2; j++) finite = finite && std::isfinite(h_rec[j]);
+            if (!finite) break; // (leave the cycle with what there is)
+            updated_steps++;
+            for (int32_t j = 0; j < nv; j++) H[(size_t)j * m + k] = cplx(h_rec[2 * j] + h_rec[2 * (nv + j)], h_rec[2 * j + 1] + h_rec[2 * (nv + j) + 1]);
+            const double hn = sqrt(h_rec[4 * nv + 1]);
+            H[(size_t)(k + 1) * m + k] = hn;
+            for (int32_t j = 0; j < k; j++) { // the rotations so far: [c s; -conj(s) c]
+                const cplx a = H[(size_t)j * m + k], b = H[(size_t)(j + 1) * m + k];
+                H[(size_t)j * m + k] = cs[(size_t)j] * a + sn[(size_t)j] * b;
+                H[(size_t)(j + 1) * m + k] = -std::conj(sn[(size_t)j]) * a + cs[(size_t)j] * b;
+            }
+            // the new rotation takes (a, hn), hn real and not negative, to (a / |a| d, 0): c = |a| / d, s = (a / |a|) hn / d
+            const cplx a = H[(size_t)k * m + k];
+            const double aa = std::abs(a), d = std::hypot(aa, hn);
+            const cplx phase = aa > 0.0 ? a / aa : cplx(1.0, 0.0);
+            cs[(size_t)k] = d > 0.0 ? aa / d : 1.0, sn[(size_t)k] = d > 0.0 ? phase * (hn / d) : cplx(0.0, 0.0);
+            H[(size_t)k * m + k] = phase * d, H[(size_t)(k + 1) * m + k] = 0.0;
+            g[(size_t)k + 1] = -std::conj(sn[(size_t)k]) * g[(size_t)k];
+            g[(size_t)k] = cs[(size_t)k] * g[(size_t)k];
+            if (keep_verbose)
+                fprintf(stderr, "hipmf: solve_updated (complex): cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", (long long)updated_cycles, k + 1, std::abs(g[(size_t)k + 1]), bnorm);
+            k++;
+            if (std::abs(g[(size_t)k]) <= tol * bnorm || !(hn > 0.0)) break;
+        }
+        if (code != SUCCESSFUL_EXIT || k == 0) break;
+        for (int32_t i = k - 1; i >= 0; i--) { // back substitution
+            cplx t = g[(size_t)i];
+            for (int32_t j = i + 1; j < k; j++) t -= H[(size_t)i * m + j] * y[(size_t)j];
+            y[(size_t)i] = H[(size_t)i * m + i] != cplx(0.0, 0.0) ? t / H[(size_t)i * m + i] : cplx(0.0, 0.0);
+        }
+        for (int32_t j = 0; j < k; j++) h_y[2 * j] = y[(size_t)j].real(), h_y[2 * j + 1] = y[(size_t)j].imag();
+        code = combine(k, 1.0);
+        if (code != SUCCESSFUL_EXIT) break;
+        const double before = rnorm;
+        code = residual(rr, bb);
+        if (code != SUCCESSFUL_EXIT) break;
+        if (keep_verbose) fprintf(stderr, "hipmf: solve_updated (complex): cycle %lld: |r| %.3e -> %.3e\n", (long long)updated_cycles, before, sqrt(rr));
         if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
             code = combine(k, -1.0);
             if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);

@@ -180,6 +180,7 @@ struct SolverUpdated {
     PinnedArray<double> h_up;
     int32_t up_m = 0;       // restart length V and Z are allocated for (0: not allocated)
     int32_t up_rec_m = 0;   // ... and the record / its mirror
+    int32_t up_zrec_m = 0;  // ... when the complex form sized them (twice the coefficients per step; == up_rec_m while that holds)
     EventOwner up_ev[4];    // HIPMF_UPDATED_TIMING=1: around the pass pair, the SpMV and the Arnoldi kernels of a step
     // solver_hipmf_solve_updated_many (kernels_krylov_blocked.hpp): bases of a block of columns, V[(k C + c) n + i], of their own -- the
     // single form's stay as they are --, four n x C blocks (W, R, X, B; the device form uses the caller's x and b), partial sums per column,
@@ -355,6 +356,12 @@ class Solver : public SolverDevice {
     // the call updated_steps counts blocked pass pairs and updated_cycles the cycles, both summed over the blocks.
     int32_t solve_updated_many(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps,
                                int32_t *steps, double *relres, bool on_device);
+    // The single form for the real-equivalent system of a COMPLEX matrix (S.n = 2 nc, vectors of interleaved (re, im) pairs; the
+    // complex C-ABI): the same iteration in complex arithmetic -- <v, w> = sum conj(v_i) w_i, complex Hessenberg matrix and rotations
+    // (kernels_krylov_complex.hpp) -- on the same bases and vectors.  values: always the inputs of the installed (signed) value map.
+    int32_t solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
+                                  bool on_device);
+    bool updated_complex = false; // the last solve_updated_complex orthogonalised in complex arithmetic (false before the first)
     int64_t updated_blocks = 0, updated_column_steps = 0; // of the last solve_updated_many: 16-column blocks (0: single form), sum of the columns' steps
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)

@@ -185,6 +185,7 @@ def _L():
         "rh_clinsolver_factorize": (cp, [vp, vp, pp(_RhParams)]),
         "rh_clinsolver_solve": (cp, [vp, vp, i64, vp, i64, i32]),
         "rh_clinsolver_solve_transpose": (cp, [vp, vp, i64, vp, i64, i32, i32]),
+        "rh_clinsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
         "rh_clinsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(f64), pp(i32)]),
         "rh_clinsolver_mumps_stats": (None, [vp, vp]),
         "rh_error_string": (cp, [i32]),
@@ -706,6 +707,17 @@ class _ComplexActual:
             x[:] = z
         return z
 
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+        """A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES in complex arithmetic on the device:
+        `mat` is a ComplexCooMatrix with the structure of the factorised matrix and new values.  Returns (x, steps, relres); raises
+        StrError("Error(2): ...") when the tolerance was not reached."""
+        r = np.ascontiguousarray(np.asarray(rhs, dtype=np.complex128)).view(np.float64)
+        out = np.zeros(2 * mat.nrow)
+        steps, relres = C.c_int32(0), C.c_double(0.0)
+        _check(_L().rh_clinsolver_solve_updated(self._h, _ptr(out), out.size, mat._h, _ptr(r), r.size, float(rel_tol), int(max_steps), C.byref(steps),
+                                                C.byref(relres), int(verbose)))
+        return out.view(np.complex128), int(steps.value), float(relres.value)
+
     def outputs(self):
         """determinant = determinant_coefficient x 10^determinant_exponent (complex_solver_umfpack.rs:411-414), rcond, perturbed pivots"""
         dr, di, de, rc, npv = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int32()
@@ -731,6 +743,10 @@ class ComplexLinSolver:
         h = _L().rh_clinsolver_new(C.byref(err))
         _check(err.value)
         self.actual = _ComplexActual(h)
+
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+        """extension of the HIPMF backend, see `actual.solve_updated`"""
+        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
 
 
 def handle_hipmf_error_code(code):

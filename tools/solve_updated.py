@@ -21,7 +21,16 @@ random device-resident columns:
     (b) N solver_hipmf_solve_updated_device calls on the same columns (that code is not touched by the block form: what the parent offers),
     (c) solver_hipmf_factorize_device + solver_hipmf_solve_device(nrhs = N) on a second handle,
 with the per-column step counts, UPDATED_STEPS (blocked pass pairs), UPDATED_COLUMN_STEPS and the split of (a) into pass pair / SpMV /
-Arnoldi kernels (HIP events, calls of their own).  The figure of merit is (a)/N against (b)/N."""
+Arnoldi kernels (HIP events, calls of their own).  The figure of merit is (a)/N against (b)/N.
+
+    python tools/solve_updated.py --complex [--out profiles/r12_solve_updated_complex.txt]
+
+The complex form (profiles/r12_solve_updated_complex.txt): K(h) = (alpha + i beta) / h I + L on the 500 x 500 unit-spacing grid, Radau5's
+alpha = 2.6811, beta = 3.0504, factorised at h0 = 1; per step-size change h0 -> h0/2 and h0 -> h0/10 the steps of
+complex_solver_hipmf_solve_updated_device, the median wall time of a call (device-resident x, rhs and values), the time per step and its
+split into pass pair / SpMV / Arnoldi kernels (HIP events, calls of their own), and the median wall time of
+complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve with the same new values on a second handle (host pointers: the complex
+C-ABI has no device entry points for them) -- the parent commit's only way.  All medians come from the same run."""
 import argparse
 import os
 import sys
@@ -156,8 +165,82 @@ def run_many(name, n, rp, ci, v, args, out):
     alt.close()
 
 
+def run_complex(args, out):
+    import ctypes as C
+
+    import scipy.sparse as sp
+
+    from russell_amd._capi import load
+
+    lib = load()
+    nx = ny = 500
+    alpha, beta = 2.6811, 3.0504
+    T = lambda m: sp.diags([-np.ones(m - 1), 2.0 * np.ones(m), -np.ones(m - 1)], [-1, 0, 1])
+    L = sp.csr_matrix(sp.kron(sp.identity(ny), T(nx)) + sp.kron(T(ny), sp.identity(nx)))
+    L.sort_indices()
+    n, rp, ci = L.shape[0], L.indptr.astype(np.int32), L.indices.astype(np.int32)
+    diag = np.repeat(np.arange(n), np.diff(rp)) == ci
+
+    def values(h):  # interleaved (re, im)
+        v = L.data + (alpha + 1j * beta) / h * diag
+        return np.ascontiguousarray(np.stack([v.real, v.imag], axis=1).ravel())
+    v0 = values(1.0)
+    handles = []
+    for _ in range(2):
+        h = lib.complex_solver_hipmf_new()
+        assert h
+        assert lib.complex_solver_hipmf_initialize(h, 0, 1, -1.0, -1, 0, 0, n, rp, ci, v0.ctypes.data) == 0
+        assert lib.complex_solver_hipmf_factorize(h, None, None, None, None, None, None, None, 0, 0, v0) == 0
+        handles.append(h)
+    s, alt = handles
+    counter = lambda which: int(lib.complex_solver_hipmf_get_counter(s, which))
+    rng = np.random.default_rng(5)
+    b = np.ascontiguousarray(rng.standard_normal(2 * n))
+    d_x, d_b, d_v = (lib.hipmf_device_malloc(16 * n), lib.hipmf_device_malloc(16 * n), lib.hipmf_device_malloc(8 * v0.size))
+    assert d_x and d_b and d_v
+    assert lib.hipmf_memcpy_h2d(d_b, b.ctypes.data_as(C.c_void_p), b.nbytes) == 0
+    istats, dstats = np.zeros(16, np.int64), np.zeros(16)
+    assert lib.complex_solver_hipmf_get_stats(s, istats, dstats) == 0
+    out("complex shifted grid %d x %d: n = %d complex, nnz = %d complex, real-equivalent factor %.0f MB, max_front %d; tolerance %.0e, restart 30" %
+        (nx, ny, n, L.nnz, 8e-6 * (istats[4] + istats[5]), istats[6], args.tol))
+    out("  %-10s %5s %9s %9s | %8s %8s %8s | %14s %10s" % ("change", "steps", "ms/call", "ms/step", "passpair", "spmv", "arnoldi", "refactor+solve", "break-even"))
+    xh = np.zeros(2 * n)
+    for label, h1 in (("h0 -> h0/2", 0.5), ("h0 -> h0/10", 0.1)):
+        v1 = values(h1)
+        assert lib.hipmf_memcpy_h2d(d_v, v1.ctypes.data_as(C.c_void_p), v1.nbytes) == 0
+        res = {}
+
+        def call():
+            steps, relres = C.c_int32(0), C.c_double(0.0)
+            code = lib.complex_solver_hipmf_solve_updated_device(s, d_x, d_b, d_v, 0, args.tol, 0, C.byref(steps), C.byref(relres))
+            res["r"] = (steps.value, relres.value, code)
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        med, lo, hi = timed(call, args.reps, args.warmup)
+        steps, relres, status = res["r"]
+        os.environ["HIPMF_UPDATED_TIMING"] = "1"
+        parts = []
+        for _ in range(3):
+            call()
+            parts.append([counter(k) / 1e3 / max(steps, 1) for k in (31, 32, 33)])  # HIPMF_COUNTER_UPDATED_PRECOND_US / _SPMV_US / _ARNOLDI_US
+        os.environ.pop("HIPMF_UPDATED_TIMING", None)
+        parts = np.median(np.array(parts), axis=0)
+
+        def alternative():
+            assert lib.complex_solver_hipmf_factorize_mapped(alt, None, None, None, None, 0, v1) == 0
+            assert lib.complex_solver_hipmf_solve(alt, xh, b, 0) == 0
+        amed, alo, ahi = timed(alternative, args.reps, args.warmup)
+        per_step = med / max(steps, 1)
+        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %14.3f %10.1f   (status %d, relres %.1e, complex arithmetic %d; call %.3f-%.3f, alternative %.3f-%.3f ms)" %
+            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, counter(37), lo, hi, alo, ahi))
+    for p_ in (d_x, d_b, d_v):
+        lib.hipmf_device_free(p_)
+    for h in handles:
+        lib.complex_solver_hipmf_drop(h)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--complex", action="store_true", help="the complex form on the 500 x 500 complex shifted grid (see the module docstring)")
     ap.add_argument("--nrhs", type=int, default=0, help="N > 0: the block form on N columns against N single calls (see the module docstring)")
     ap.add_argument("--matrix", default="both", choices=["2d", "3d", "both"])
     ap.add_argument("--reps", type=int, default=9)
@@ -171,15 +254,19 @@ def main():
     def out(line):
         print(line, flush=True)
         lines.append(line)
-    if args.nrhs > 0:
+    if args.complex:
+        out("complex_solver_hipmf_solve_updated_device against complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve, one MI355X; "
+            "median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
+        run_complex(args, out)
+    elif args.nrhs > 0:
         out("(a) one solve_updated_many_device call, (b) %d solve_updated_device calls, (c) factorize_device + solve_device(nrhs = %d), one MI355X; "
             "median of %d after %d warm-up" % (args.nrhs, args.nrhs, args.reps, args.warmup))
     else:
         out("solve_updated_device against factorize_device + solve_device, one MI355X; median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
     go = run_many if args.nrhs > 0 else run
-    if args.matrix in ("2d", "both"):
+    if not args.complex and args.matrix in ("2d", "both"):
         go("poisson2d 1000 x 1000 + I", *P.poisson2d(1000), args, out)
-    if args.matrix in ("3d", "both"):
+    if not args.complex and args.matrix in ("3d", "both"):
         go("poisson3d 100^3 + I", *P.poisson3d(100), args, out)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
