@@ -15,6 +15,7 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <tuple>
 
 #include "kernels.hpp"
 #include "kernels_solve_transpose.hpp"
@@ -32,6 +33,7 @@
 #include <unistd.h>
 #include <cerrno>
 #include "matching.hpp"
+#include "krylov_host.hpp"
 
 namespace hipmf {
 
@@ -1877,7 +1879,7 @@ int32_t Solver::factorize(const double *values, bool on_device) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!values) return ERROR_NULL_POINTER;
     DeviceScope dev_scope(device);
-    int32_t code = load_values(values, on_device);
+    int32_t code = stage_values(d_vals, values, false, on_device);
     if (code != SUCCESSFUL_EXIT) return code;
     code = run_factor();
     if (code != SUCCESSFUL_EXIT) return code;
@@ -1970,15 +1972,8 @@ int32_t Solver::factorize_mapped(const double *input, bool on_device) {
     if (!input) return ERROR_NULL_POINTER;
     if (nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
     DeviceScope dev_scope(device);
-    const double *src = input;
-    if (!on_device) {
-        HIPC(hipMemcpyAsync(d_vin, input, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-        src = d_vin;
-    }
-    const int64_t nnz = S.nnz_a;
-    hipLaunchKernelGGL(k_gather_values, dim3((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), dim3(256), 0, STREAM, nnz, d_seg_ptr, d_seg_idx,
-                       src, d_vals);
-    int32_t code = run_factor();
+    int32_t code = stage_values(d_vals, input, true, on_device);
+    if (code == SUCCESSFUL_EXIT) code = run_factor();
     if (code != SUCCESSFUL_EXIT) return code;
     if (n_weak_diag > 0 && !rematching && !rematch_futile) return rematch_and_factorize();
     factorized = true;
@@ -2912,13 +2907,13 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device, cons
     opt.refinement_nstep = 0, opt.verbose = false;
     in_rescue = true;
     std::vector<std::vector<double>> V, Z;
-    std::vector<double> H((size_t)(m + 1) * m), cs((size_t)m), sn((size_t)m), g((size_t)m + 1), y((size_t)m);
+    GivensLsq<double> lsq(m);
+    std::vector<double> hcol((size_t)m), y((size_t)m);
     for (int32_t cycle = 0; cycle < krylov_cycles && code == SUCCESSFUL_EXIT; cycle++) {
         V.assign(1, r);
         Z.clear();
         for (double &e : V[0]) e /= rnorm;
-        std::fill(g.begin(), g.end(), 0.0);
-        g[0] = rnorm;
+        lsq.reset(rnorm);
         int32_t k = 0;
         for (; k < m; k++) {
             Z.emplace_back((size_t)n);
@@ -2936,23 +2931,13 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device, cons
             for (int32_t j = 0; j <= k; j++) { // modified Gram-Schmidt
                 long double t = 0.0L;
                 for (int32_t i = 0; i < n; i++) t += (long double)w[(size_t)i] * V[(size_t)j][(size_t)i];
-                H[(size_t)j * m + k] = (double)t;
+                hcol[(size_t)j] = (double)t;
                 for (int32_t i = 0; i < n; i++) w[(size_t)i] -= (double)t * V[(size_t)j][(size_t)i];
             }
             const double hn = nrm2(w);
-            H[(size_t)(k + 1) * m + k] = hn;
-            for (int32_t j = 0; j < k; j++) { // the Givens rotations so far
-                const double a = H[(size_t)j * m + k], b = H[(size_t)(j + 1) * m + k];
-                H[(size_t)j * m + k] = cs[(size_t)j] * a + sn[(size_t)j] * b;
-                H[(size_t)(j + 1) * m + k] = -sn[(size_t)j] * a + cs[(size_t)j] * b;
-            }
-            const double a = H[(size_t)k * m + k], b = H[(size_t)(k + 1) * m + k], d = std::hypot(a, b);
-            cs[(size_t)k] = d > 0.0 ? a / d : 1.0, sn[(size_t)k] = d > 0.0 ? b / d : 0.0;
-            H[(size_t)k * m + k] = d, H[(size_t)(k + 1) * m + k] = 0.0;
-            g[(size_t)k + 1] = -sn[(size_t)k] * g[(size_t)k];
-            g[(size_t)k] = cs[(size_t)k] * g[(size_t)k];
-            if (saved_verbose) fprintf(stderr, "hipmf: krylov rescue: cycle %d step %d: residual estimate %.3e (|b| = %.3e)\n", cycle, k + 1, fabs(g[(size_t)k + 1]), bnorm);
-            if (fabs(g[(size_t)k + 1]) <= krylov_tol * bnorm || !(hn > 0.0)) {
+            lsq.push(k, hcol.data(), hn);
+            if (saved_verbose) fprintf(stderr, "hipmf: krylov rescue: cycle %d step %d: residual estimate %.3e (|b| = %.3e)\n", cycle, k + 1, fabs(lsq.g[(size_t)k + 1]), bnorm);
+            if (fabs(lsq.g[(size_t)k + 1]) <= krylov_tol * bnorm || !(hn > 0.0)) {
                 k++;
                 break;
             }
@@ -2961,11 +2946,7 @@ int32_t Solver::krylov_rescue(double *x, const double *rhs, bool on_device, cons
         }
         if (code != SUCCESSFUL_EXIT) break;
         const int32_t kk = std::min<int32_t>(k, (int32_t)Z.size());
-        for (int32_t i = kk - 1; i >= 0; i--) { // back substitution, x += Z y
-            double t = g[(size_t)i];
-            for (int32_t j = i + 1; j < kk; j++) t -= H[(size_t)i * m + j] * y[(size_t)j];
-            y[(size_t)i] = H[(size_t)i * m + i] != 0.0 ? t / H[(size_t)i * m + i] : 0.0;
-        }
+        lsq.solve(kk, y.data()); // x += Z y
         for (int32_t j = 0; j < kk; j++)
             for (int32_t i = 0; i < n; i++) xh[(size_t)i] += y[(size_t)j] * Z[(size_t)j][(size_t)i];
         const double before = rnorm;
@@ -3335,121 +3316,181 @@ int32_t Solver::spmv(double *y, const double *x, double alpha, bool on_device) {
     return SUCCESSFUL_EXIT;
 }
 
-int32_t Solver::load_values(const double *values, bool on_device) {
+// The matrix values a caller hands over, into dst (nnz doubles in the handle's CSR order; d_vals for a factorize, d_up_vals for the
+// solve_updated forms): through the value map (mapped: its inputs), as they are, or expanded from a mirrored lower triangle.
+int32_t Solver::stage_values(double *dst, const double *values, bool mapped, bool on_device) {
     const int64_t nnz = S.nnz_a;
-    if (!d_emap) {
-        HIPC(hipMemcpyAsync(d_vals, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
+    if (!mapped && !d_emap) {
+        HIPC(hipMemcpyAsync(dst, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
         return SUCCESSFUL_EXIT;
     }
     const double *src = values;
     if (!on_device) {
-        HIPC(hipMemcpyAsync(d_vlow, values, sizeof(double) * nnz_low, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-        src = d_vlow;
+        double *const via = mapped ? d_vin : d_vlow;
+        HIPC(hipMemcpyAsync(via, values, sizeof(double) * (mapped ? nnz_in : nnz_low), hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        src = via;
     }
-    hipLaunchKernelGGL(k_expand_values, dim3((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), dim3(256), 0, STREAM, nnz, d_emap, src, d_vals);
+    if (mapped) hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, dst);
+    else hipLaunchKernelGGL(k_expand_values, gv, b256, 0, STREAM, nnz, d_emap, src, dst);
     return SUCCESSFUL_EXIT;
 }
 
-// ---- solve with new matrix values on the kept factor (solver_hipmf_solve_updated) ----
+// ---- what the solve_updated forms share ----
+namespace {
+
+// tolerance (default 1e-12), restart length (HIPMF_UPDATED_RESTART, 4 .. 200, default 30), step limit (default: four cycles) and
+// whether the phases of a step are timed (HIPMF_UPDATED_TIMING=1)
+struct UpdatedParams {
+    double tol;
+    int32_t restart = 30, step_limit;
+    bool timing;
+    UpdatedParams(double rel_tol, int32_t max_steps) : tol(rel_tol > 0.0 ? rel_tol : 1e-12) {
+        const char *const r = getenv("HIPMF_UPDATED_RESTART"), *const t = getenv("HIPMF_UPDATED_TIMING");
+        if (r && atoi(r) >= 4 && atoi(r) <= 200) restart = atoi(r);
+        step_limit = max_steps > 0 ? max_steps : 4 * restart;
+        timing = t && atoi(t) != 0;
+    }
+};
+
+// The bases V ((m + 1) x per_step doubles) and Z (m x per_step) anew; when they do not fit the restart length is halved (down to 4).
+// Returns the restart length they hold; 0: not even 4 fit, nothing is allocated.
+int32_t grow_bases(DeviceArray<double> &V, DeviceArray<double> &Z, int32_t m, size_t per_step) {
+    V.reset(), Z.reset();
+    for (int32_t mm = m;; mm = std::max(4, mm / 2)) {
+        if (V.alloc((size_t)(mm + 1) * per_step) == hipSuccess && Z.alloc((size_t)mm * per_step) == hipSuccess) return mm;
+        V.reset(), Z.reset();
+        (void)hipGetLastError();
+        if (mm == 4) return 0;
+    }
+}
+
+// HIPMF_UPDATED_TIMING=1: events around the pass pair, the SpMV and the Arnoldi kernels of a step, summed into updated_ms
+struct StepTimer {
+    EventOwner *ev;
+    hipStream_t st;
+    bool on;
+    hipError_t create() const {
+        hipError_t e = hipSuccess;
+        for (int t = 0; on && t < 4 && e == hipSuccess; t++)
+            if (!ev[t]) e = hipEventCreate(ev[t].put());
+        return e;
+    }
+    void mark(int t) const {
+        if (on) (void)hipEventRecord((hipEvent_t)ev[t], st);
+    }
+    void add(double *ms_sum) const { // (after the step's synchronisation)
+        float ms = 0.0f;
+        for (int t = 0; on && t < 3; t++)
+            if (hipEventElapsedTime(&ms, (hipEvent_t)ev[t], (hipEvent_t)ev[t + 1]) == hipSuccess) ms_sum[t] += ms;
+    }
+};
+
+// The pass pairs of a solve_updated form or of an error analysis are ordinary unrefined solves: the statistics they leave behind and
+// the options they run under are put back when the guard goes.  (krylov_rescue PRODUCES the two krylov_ fields and does not use it.)
+struct NestedSolveGuard {
+    Solver &s;
+    const bool verbose; // as the caller set it
+    auto fields() const {
+        return std::tie(s.times, s.opt.refinement_nstep, s.opt.verbose, s.refinement_steps_done, s.in_rescue, s.col_omega, s.block_groups_last, s.last_omega,
+                        s.last_residual_inf, s.krylov_last_relres, s.krylov_iterations);
+    }
+    const std::tuple<PhaseTimes, int32_t, bool, int32_t, bool, std::vector<double>, int32_t, double, double, double, int64_t> kept;
+    explicit NestedSolveGuard(Solver &s_) : s(s_), verbose(s_.opt.verbose), kept(fields()) {}
+    ~NestedSolveGuard() { fields() = kept; }
+    void unrefined_quiet() const { s.opt.refinement_nstep = 0, s.opt.verbose = false, s.in_rescue = true; } // (and no Krylov rescue inside)
+};
+
+// The arithmetic of the single-column core: the scalar of the host's least-squares problem, doubles per coefficient (and with them
+// the restart bound), the label of the verbose lines and the three launches that differ (kernels_krylov.hpp, kernels_krylov_complex.hpp).
+struct UpdatedReal {
+    typedef double scalar;
+    static constexpr int32_t D = 1; // doubles per coefficient; the restart length is at most n / D
+    static constexpr const char *label = "solve_updated";
+    static void dots(dim3 g, hipStream_t st, int64_t n, const double *w, const double *V, int32_t nv, double *part) { hipLaunchKernelGGL(k_kry_dots, g, dim3(256), 0, st, n, w, V, nv, part); }
+    static void update(dim3 g, hipStream_t st, int64_t n, double *w, const double *V, int32_t nv, const double *h, double *part) { hipLaunchKernelGGL(k_kry_update, g, dim3(256), 0, st, n, w, V, nv, h, part); }
+    static void combine(dim3 g, hipStream_t st, int64_t n, double *x, const double *Z, int32_t nv, const double *y) { hipLaunchKernelGGL(k_kry_combine, g, dim3(256), 0, st, n, x, Z, nv, y); }
+};
+struct UpdatedComplex {
+    typedef std::complex<double> scalar;
+    static constexpr int32_t D = 2; // (the Krylov space of an nc x nc complex matrix has at most nc = n / 2 dimensions)
+    static constexpr const char *label = "solve_updated (complex)";
+    static void dots(dim3 g, hipStream_t st, int64_t n, const double *w, const double *V, int32_t nv, double *part) { hipLaunchKernelGGL(k_zkry_dots, g, dim3(256), 0, st, n, w, V, nv, part); }
+    static void update(dim3 g, hipStream_t st, int64_t n, double *w, const double *V, int32_t nv, const double *h, double *part) { hipLaunchKernelGGL(k_zkry_update, g, dim3(256), 0, st, n, w, V, nv, h, part); }
+    static void combine(dim3 g, hipStream_t st, int64_t n, double *x, const double *Z, int32_t nv, const double *y) { hipLaunchKernelGGL(k_zkry_combine, g, dim3(256), 0, st, n, x, Z, nv, y); }
+};
+
+} // namespace
+
+// ---- solve with new matrix values on the kept factor (solver_hipmf_solve_updated, complex_solver_hipmf_solve_updated) ----
 // The callers of this backend change the VALUES of the matrix often and by little (a new step size scales the shift of gamma M - J, a
 // Jacobian moves in a few rows): instead of a factorisation the old factor M serves as RIGHT preconditioner of a flexible GMRES on
-// A_new x = b, started from x = 0.  Unlike the Krylov rescue above -- which stays as it is: host vectors, rare path -- everything of
-// length n lives on the device: per step z_k = M^{-1} v_k (one unrefined pass pair: solve_core on device pointers, default schedule, the
-// device gate as in any solve), w = A_new z_k (the stream SpMV on the operator's own value buffer), classical Gram-Schmidt twice (CGS2:
-// k_kry_dots + k_kry_reduce + k_kry_update, two rounds; all coefficients stay on the device), v_{k+1} = w / |w| (k_kry_scale).  The host
-// reads back ONE small record per step through pinned memory -- both coefficient sets (it adds them: the new Hessenberg column) and the
-// two squared norms, 2 k + 4 doubles -- applies the Givens rotations, and per cycle uploads y for x += Z y (k_kry_combine) and reads the
-// two sums of the recomputed true residual (k_kry_residual).  Non-finite numbers in a step's record (a direction the factor cannot give)
-// end the cycle with the directions before it, as in the rescue.  A cycle that does not lower the true residual is taken back and ends
-// the call: x is the best iterate.
-int32_t Solver::solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
-                              double *relres_out, bool on_device) {
-    if (!initialized) return ERROR_NEED_INITIALIZATION;
-    if (!factorized) return ERROR_NEED_FACTORIZATION;
-    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
-    if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
-    if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
+// A_new x = b, started from x = 0.  Unlike the Krylov rescue above (host vectors, rare path) everything of length n lives on the device:
+// per step z_k = M^{-1} v_k (one unrefined pass pair: solve_core on device pointers, default schedule, the device gate as in any solve),
+// w = A_new z_k (the stream SpMV on the operator's own value buffer), classical Gram-Schmidt twice (CGS2: dots + k_kry_reduce + update,
+// two rounds; all coefficients stay on the device), v_{k+1} = w / |w| (k_kry_scale).  The host reads back ONE small record per step
+// through pinned memory -- both coefficient sets (it adds them: the new Hessenberg column) and the two squared norms, 2 D (k + 1) + 2
+// doubles --, pushes the column into the least-squares problem (GivensLsq, krylov_host.hpp), and per cycle uploads y for x += Z y
+// (combine) and reads the two sums of the recomputed true residual (k_kry_residual).  Non-finite numbers in a step's record (a direction
+// the factor cannot give) end the cycle with the directions before it, as in the rescue.  A cycle that does not lower the true residual
+// is taken back and ends the call: x is the best iterate.
+// One core serves both arithmetics; the policy P gives what differs.  In the COMPLEX form this Solver holds the real-equivalent form
+// of order n = 2 nc of a complex matrix, its vectors are nc interleaved (re, im) pairs.  Real GMRES on that system minimises over real
+// coefficients only and usually needs 20 - 40 % more pass pairs.  Pass pair, SpMV, |w|^2 (the real sum over n doubles), normalisation
+// and residual are the real form's launches; the coefficients are complex, D = 2 doubles each: h_j = sum conj(v_j,i) w_i (k_zkry_dots:
+// two sums per basis vector, k_kry_reduce over 2 nv columns leaves them interleaved), k_zkry_update, k_zkry_combine.  The preconditioner
+// only has to give SOME vector: a factor that is not exactly complex-linear (HIPMF_COMPLEX_PAIRS=0, replaced pivots) is merely weaker.
+template <class P>
+int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
+                                   double *relres_out, bool on_device) {
+    typedef typename P::scalar T;
+    constexpr int32_t D = P::D;
     DeviceScope dev_scope(device);
     const int32_t n = S.n;
-    const int64_t nnz = S.nnz_a;
-    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
-    int32_t restart = 30;
-    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
-        const int v = atoi(e);
-        if (v >= 4 && v <= 200) restart = v;
-    }
-    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
-    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
+    const UpdatedParams par(rel_tol, max_steps);
+    const StepTimer timer{up_ev, STREAM, par.timing};
     updated_steps = updated_cycles = 0;
     updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
     if (steps_out) *steps_out = 0;
     if (relres_out) *relres_out = 0.0;
 
-    // buffers: the bases grow with the restart length; when they do not fit the restart length is halved (down to 4)
-    int32_t m = std::max(4, std::min(restart, n));
-    if (up_m < m) {
-        d_up_V.reset(), d_up_Z.reset();
-        up_m = 0;
-        int32_t mm = m;
-        for (;; mm = std::max(4, mm / 2)) {
-            if (d_up_V.alloc((size_t)(mm + 1) * n) == hipSuccess && d_up_Z.alloc((size_t)mm * n) == hipSuccess) break;
-            d_up_V.reset(), d_up_Z.reset();
-            (void)hipGetLastError();
-            if (mm == 4) {
-                last_error = "solve_updated: no device memory for the Krylov bases";
-                return ERROR_HIP_MALLOC;
-            }
-        }
-        up_m = mm;
+    // buffers: the bases grow with the restart length (a complex basis vector is one real vector of n doubles); the partial sums, the
+    // record and its mirror are sized for D = 2 whichever form allocates them
+    int32_t m = std::max(4, std::min(par.restart, n / D));
+    if (up_m < m && (up_m = grow_bases(d_up_V, d_up_Z, m, (size_t)n)) == 0) {
+        last_error = "solve_updated: no device memory for the Krylov bases";
+        return ERROR_HIP_MALLOC;
     }
     m = std::min(m, up_m);
     const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
     const int32_t rec_m = std::max(up_m, 200);
-    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(S.nnz_a, 1)), ERROR_HIP_MALLOC);
     if (!d_up_vec) HIPC(d_up_vec.alloc(4 * (size_t)n), ERROR_HIP_MALLOC);
     if (!d_up_part || up_rec_m < rec_m) {
-        HIPC(d_up_part.alloc(std::max((size_t)(rec_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1))), ERROR_HIP_MALLOC);
-        HIPC(d_up_rec.alloc(3 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
-        HIPC(h_up.alloc(3 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        HIPC(d_up_part.alloc(std::max((size_t)(2 * rec_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1))), ERROR_HIP_MALLOC);
+        HIPC(d_up_rec.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
+        HIPC(h_up.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
         up_rec_m = rec_m;
     }
-    if (timing)
-        for (EventOwner &e : up_ev)
-            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
-    // the record: [0, 2 m + 2) both coefficient sets of the step; then the squared norms after the two rounds; the residual's |r|^2, |b|^2; y
-    double *const d_h = d_up_rec, *const d_nrm = d_up_rec + 2 * (size_t)rec_m + 2, *const d_res = d_nrm + 2, *const d_y = d_res + 2;
-    double *const h_rec = h_up, *const h_res = h_up + 2 * (size_t)rec_m + 4, *const h_y = h_res + 2;
+    HIPC(timer.create(), ERROR_HIP_SYNCHRONIZE);
+    // the record: [0, 2 D m + 2) both coefficient sets of the step, then the squared norms after the two rounds; |r|^2, |b|^2; y
+    double *const d_h = d_up_rec, *const d_res = d_up_rec + 2 * D * (size_t)rec_m + 2, *const d_y = d_res + 2;
+    double *const h_rec = h_up, *const h_res = h_up + 2 * D * (size_t)rec_m + 2, *const h_y = h_res + 2;
     double *const d_w = d_up_vec, *const d_r = d_up_vec + (size_t)n;
     double *const d_xx = on_device ? x : d_up_vec + 2 * (size_t)n;
     const double *d_bb = rhs;
     const size_t nb = sizeof(double) * (size_t)n;
 
-    // the operator's values: the staging factorize gives its own (value-map gather, expansion of a mirrored lower triangle), into d_up_vals
-    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
-    if (mapped) {
-        const double *src = values;
-        if (!on_device) {
-            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            src = d_vin;
-        }
-        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
-    } else if (!d_emap) {
-        HIPC(hipMemcpyAsync(d_up_vals, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-    } else {
-        const double *src = values;
-        if (!on_device) {
-            HIPC(hipMemcpyAsync(d_vlow, values, sizeof(double) * nnz_low, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            src = d_vlow;
-        }
-        hipLaunchKernelGGL(k_expand_values, gv, b256, 0, STREAM, nnz, d_emap, src, d_up_vals);
-    }
+    // the operator's values: the staging factorize gives its own, into d_up_vals
+    int32_t code = stage_values(d_up_vals, values, mapped, on_device);
+    if (code != SUCCESSFUL_EXIT) return code;
     if (!on_device) {
         HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
         d_bb = d_up_vec + 3 * (size_t)n;
     }
     HIPC(hipMemsetAsync(d_xx, 0, nb, STREAM), ERROR_HIP_MEMCPY);
 
-    const dim3 gk((unsigned)nblk);
+    const dim3 gk((unsigned)nblk), b256(256);
     // r = b - A_new x with its two sums on the host (one synchronisation)
     auto residual = [&](double &rr, double &bb) -> int32_t {
         hipLaunchKernelGGL(k_kry_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, d_xx, d_bb, d_r, d_up_part);
@@ -3460,9 +3501,9 @@ int32_t Solver::solve_updated(double *x, const double *rhs, const double *values
         return SUCCESSFUL_EXIT;
     };
     auto combine = [&](int32_t kk, double sign) -> int32_t { // x += sign Z y
-        for (int32_t j = 0; j < kk; j++) h_y[j] = sign * h_y[j];
-        HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * kk, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-        hipLaunchKernelGGL(k_kry_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, (const double *)d_up_Z, kk, (const double *)d_y);
+        for (int32_t j = 0; j < D * kk; j++) h_y[j] = sign * h_y[j];
+        HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * D * kk, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        P::combine(gk, STREAM, (int64_t)n, d_xx, d_up_Z, kk, d_y);
         HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (h_y may be rewritten)
         return SUCCESSFUL_EXIT;
     };
@@ -3475,327 +3516,103 @@ int32_t Solver::solve_updated(double *x, const double *rhs, const double *values
     };
 
     double rr = 0.0, bb = 0.0;
-    int32_t code = residual(rr, bb);
+    code = residual(rr, bb);
     if (code != SUCCESSFUL_EXIT) return code;
     if (bb == 0.0) return finish(SUCCESSFUL_EXIT, 0.0); // x = 0
     if (!std::isfinite(bb)) return finish(WARNING_NOT_CONVERGED, NAN);
     const double bnorm = sqrt(bb);
     double rnorm = sqrt(rr);
-
-    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
-    const PhaseTimes keep_times = times;
-    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done;
-    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
-    const std::vector<double> keep_omega = col_omega;
-    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
-    auto restore = [&]() {
-        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
-        col_omega = keep_omega;
-    };
-
-    std::vector<double> H((size_t)(m + 1) * m), cs((size_t)m), sn((size_t)m), g((size_t)m + 1);
-    while (rnorm > tol * bnorm && updated_steps < step_limit) {
-        updated_cycles++;
-        hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (const double *)d_res, (double *)d_up_V); // v_0 = r / |r|
-        std::fill(g.begin(), g.end(), 0.0);
-        g[0] = rnorm;
-        int32_t k = 0; // directions of this cycle that entered the least-squares problem
-        while (k < m && updated_steps < step_limit) {
-            double *const zk = d_up_Z + (size_t)k * n;
-            const double *const vk = d_up_V + (size_t)k * n;
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
-            code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
-            if (code != SUCCESSFUL_EXIT) break;
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
-            hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
-                               (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
-            const int32_t nv = k + 1;
-            for (int32_t round = 0; round < 2; round++) { // CGS2
-                double *const hr = d_h + (size_t)round * nv;
-                hipLaunchKernelGGL(k_kry_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_up_V, nv, (double *)d_up_part);
-                hipLaunchKernelGGL(k_kry_reduce, dim3(nv), b256, 0, STREAM, (const double *)d_up_part, nblk, hr);
-                hipLaunchKernelGGL(k_kry_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_up_V, nv, (const double *)hr, (double *)d_up_part);
-                hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_up_part, nblk, d_h + 2 * (size_t)nv + round);
-            }
-            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)(d_h + 2 * (size_t)nv + 1), d_up_V + (size_t)(k + 1) * n);
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
-            if (hipMemcpyAsync(h_rec, d_h, sizeof(double) * (2 * (size_t)nv + 2), hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
-            if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
-            if (code != SUCCESSFUL_EXIT) break;
-            if (timing)
-                for (int t = 0; t < 3; t++) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
+    {
+        const NestedSolveGuard guard(*this);
+        guard.unrefined_quiet();
+        GivensLsq<T> lsq(m);
+        std::vector<T> rec(2 * (size_t)m), hcol((size_t)m), y((size_t)m);
+        while (rnorm > par.tol * bnorm && updated_steps < par.step_limit) {
+            updated_cycles++;
+            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (const double *)d_res, (double *)d_up_V); // v_0 = r / |r|
+            lsq.reset(rnorm);
+            int32_t k = 0; // directions of this cycle that entered the least-squares problem
+            while (k < m && updated_steps < par.step_limit) {
+                double *const zk = d_up_Z + (size_t)k * n;
+                const double *const vk = d_up_V + (size_t)k * n;
+                timer.mark(0);
+                code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
+                if (code != SUCCESSFUL_EXIT) break;
+                timer.mark(1);
+                hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
+                                   (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
+                timer.mark(2);
+                const int32_t nv = k + 1;
+                double *const d_nrm = d_h + 2 * D * (size_t)nv; // the squared norms after the two rounds
+                for (int32_t round = 0; round < 2; round++) { // CGS2
+                    double *const hr = d_h + (size_t)round * D * nv;
+                    P::dots(gk, STREAM, (int64_t)n, d_w, d_up_V, nv, d_up_part);
+                    hipLaunchKernelGGL(k_kry_reduce, dim3(D * nv), b256, 0, STREAM, (const double *)d_up_part, nblk, hr);
+                    P::update(gk, STREAM, (int64_t)n, d_w, d_up_V, nv, hr, d_up_part);
+                    hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_up_part, nblk, d_nrm + round);
                 }
-            bool finite = true;
-            for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(h_rec[j]);
-            if (!finite) break; // (leave the cycle with what there is)
-            updated_steps++;
-            for (int32_t j = 0; j < nv; j++) H[(size_t)j * m + k] = h_rec[j] + h_rec[nv + j];
-            const double hn = sqrt(h_rec[2 * nv + 1]);
-            H[(size_t)(k + 1) * m + k] = hn;
-            for (int32_t j = 0; j < k; j++) { // the Givens rotations so far
-                const double a = H[(size_t)j * m + k], b = H[(size_t)(j + 1) * m + k];
-                H[(size_t)j * m + k] = cs[(size_t)j] * a + sn[(size_t)j] * b;
-                H[(size_t)(j + 1) * m + k] = -sn[(size_t)j] * a + cs[(size_t)j] * b;
+                hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)(d_nrm + 1), d_up_V + (size_t)(k + 1) * n);
+                timer.mark(3);
+                const int32_t nrec = 2 * D * nv + 2;
+                if (hipMemcpyAsync(h_rec, d_h, sizeof(double) * nrec, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+                if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
+                if (code != SUCCESSFUL_EXIT) break;
+                timer.add(updated_ms);
+                bool finite = true;
+                for (int32_t j = 0; j < nrec; j++) finite = finite && std::isfinite(h_rec[j]);
+                if (!finite) break; // (leave the cycle with what there is)
+                updated_steps++;
+                memcpy(rec.data(), h_rec, sizeof(T) * 2 * nv); // the new Hessenberg column: the coefficients of the two rounds, added
+                for (int32_t j = 0; j < nv; j++) hcol[(size_t)j] = rec[(size_t)j] + rec[(size_t)(nv + j)];
+                const double hn = sqrt(h_rec[nrec - 1]);
+                lsq.push(k, hcol.data(), hn);
+                if (guard.verbose)
+                    fprintf(stderr, "hipmf: %s: cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label, (long long)updated_cycles, k + 1, std::abs(lsq.g[(size_t)k + 1]), bnorm);
+                k++;
+                if (std::abs(lsq.g[(size_t)k]) <= par.tol * bnorm || !(hn > 0.0)) break;
             }
-            const double a = H[(size_t)k * m + k], b = H[(size_t)(k + 1) * m + k], d = std::hypot(a, b);
-            cs[(size_t)k] = d > 0.0 ? a / d : 1.0, sn[(size_t)k] = d > 0.0 ? b / d : 0.0;
-            H[(size_t)k * m + k] = d, H[(size_t)(k + 1) * m + k] = 0.0;
-            g[(size_t)k + 1] = -sn[(size_t)k] * g[(size_t)k];
-            g[(size_t)k] = cs[(size_t)k] * g[(size_t)k];
-            if (keep_verbose) fprintf(stderr, "hipmf: solve_updated: cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", (long long)updated_cycles, k + 1, fabs(g[(size_t)k + 1]), bnorm);
-            k++;
-            if (fabs(g[(size_t)k]) <= tol * bnorm || !(hn > 0.0)) break;
+            if (code != SUCCESSFUL_EXIT || k == 0) break;
+            lsq.solve(k, y.data());
+            memcpy(h_y, y.data(), sizeof(T) * (size_t)k);
+            code = combine(k, 1.0);
+            if (code != SUCCESSFUL_EXIT) break;
+            const double before = rnorm;
+            code = residual(rr, bb);
+            if (code != SUCCESSFUL_EXIT) break;
+            if (guard.verbose) fprintf(stderr, "hipmf: %s: cycle %lld: |r| %.3e -> %.3e\n", P::label, (long long)updated_cycles, before, sqrt(rr));
+            if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
+                code = combine(k, -1.0);
+                if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
+                if (code == SUCCESSFUL_EXIT) rnorm = sqrt(rr);
+                break;
+            }
+            rnorm = sqrt(rr);
         }
-        if (code != SUCCESSFUL_EXIT || k == 0) break;
-        for (int32_t i = k - 1; i >= 0; i--) { // back substitution
-            double t = g[(size_t)i];
-            for (int32_t j = i + 1; j < k; j++) t -= H[(size_t)i * m + j] * h_y[j];
-            h_y[i] = H[(size_t)i * m + i] != 0.0 ? t / H[(size_t)i * m + i] : 0.0;
-        }
-        code = combine(k, 1.0);
-        if (code != SUCCESSFUL_EXIT) break;
-        const double before = rnorm;
-        code = residual(rr, bb);
-        if (code != SUCCESSFUL_EXIT) break;
-        if (keep_verbose) fprintf(stderr, "hipmf: solve_updated: cycle %lld: |r| %.3e -> %.3e\n", (long long)updated_cycles, before, sqrt(rr));
-        if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
-            code = combine(k, -1.0);
-            if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
-            if (code == SUCCESSFUL_EXIT) rnorm = sqrt(rr);
-            break;
-        }
-        rnorm = sqrt(rr);
     }
-    restore();
     if (code != SUCCESSFUL_EXIT) return code;
-    return finish(rnorm <= tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
+    return finish(rnorm <= par.tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
 }
 
-// ---- the same in complex arithmetic (complex_solver_hipmf_solve_updated; kernels_krylov_complex.hpp) ----
-// This Solver holds the real-equivalent form of order n = 2 nc of a complex matrix; its vectors are nc interleaved (re, im) pairs.  Real
-// GMRES on that system minimises over real coefficients only: its Krylov space is a subset of the complex one, so it never needs fewer
-// pass pairs than the iteration below and usually needs 20 - 40 % more.  The steps are those of solve_updated with the same buffers --
-// z_k = M^{-1} v_k (one unrefined pass pair), w = A_new z_k (the real-equivalent stream SpMV on d_up_vals), CGS2, v_{k+1} = w / |w| --
-// but the coefficients are complex: h_j = <v_j, w> = sum conj(v_j,i) w_i (k_zkry_dots: two sums per basis vector, k_kry_reduce over
-// 2 nv columns leaves them interleaved), w -= sum h_j v_j (k_zkry_update).  |w|^2 is the real sum over the n doubles and the
-// normalisation a real scaling, the residual's 2-norm that of the real-equivalent residual: k_kry_reduce, k_kry_scale and k_kry_residual
-// as they are.  The host reads 4 k + 6 doubles per step, keeps a complex Hessenberg matrix, applies complex Givens rotations (real c,
-// complex s) and uploads at most m complex y per cycle for x += Z y (k_zkry_combine).  The preconditioner only has to give SOME vector
-// (flexible GMRES): a factor that is not exactly complex-linear (HIPMF_COMPLEX_PAIRS=0, replaced pivots) is merely a weaker one.
-// The body is a copy of solve_updated on purpose: the real path keeps its launches and its bits.
+int32_t Solver::solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
+                              double *relres_out, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
+    return solve_updated_core<UpdatedReal>(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+}
+
+// values: always the inputs of the installed (signed) value map, gathered as factorize_mapped gathers them
 int32_t Solver::solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps_out,
                                       double *relres_out, bool on_device) {
-    typedef std::complex<double> cplx;
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if (nnz_in < 1 || (S.n & 1) || d_emap) return ERROR_HIPMF_INVALID_VALUE; // the complex handle: a value map, pairs, a general pattern
-    DeviceScope dev_scope(device);
-    const int32_t n = S.n;
-    const int64_t nnz = S.nnz_a;
-    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
-    int32_t restart = 30;
-    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
-        const int v = atoi(e);
-        if (v >= 4 && v <= 200) restart = v;
-    }
-    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
-    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
-    updated_steps = updated_cycles = 0;
-    updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
     updated_complex = true;
-    if (steps_out) *steps_out = 0;
-    if (relres_out) *relres_out = 0.0;
-
-    // buffers: those of solve_updated (a complex basis vector is one real vector of n doubles); the restart length is limited by the
-    // complex order -- the Krylov space of an nc x nc complex matrix has at most nc dimensions
-    int32_t m = std::max(4, std::min(restart, n / 2));
-    if (up_m < m) {
-        d_up_V.reset(), d_up_Z.reset();
-        up_m = 0;
-        int32_t mm = m;
-        for (;; mm = std::max(4, mm / 2)) {
-            if (d_up_V.alloc((size_t)(mm + 1) * n) == hipSuccess && d_up_Z.alloc((size_t)mm * n) == hipSuccess) break;
-            d_up_V.reset(), d_up_Z.reset();
-            (void)hipGetLastError();
-            if (mm == 4) {
-                last_error = "solve_updated: no device memory for the Krylov bases";
-                return ERROR_HIP_MALLOC;
-            }
-        }
-        up_m = mm;
-    }
-    m = std::min(m, up_m);
-    const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
-    const int32_t rec_m = std::max(up_m, 200);
-    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
-    if (!d_up_vec) HIPC(d_up_vec.alloc(4 * (size_t)n), ERROR_HIP_MALLOC);
-    if (!d_up_part || up_zrec_m < rec_m || up_rec_m != up_zrec_m) { // (twice the slots and coefficients of the real form, which they also serve)
-        HIPC(d_up_part.alloc(std::max((size_t)(2 * rec_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1))), ERROR_HIP_MALLOC);
-        HIPC(d_up_rec.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
-        HIPC(h_up.alloc(6 * (size_t)rec_m + 8), ERROR_HIP_MALLOC);
-        up_rec_m = up_zrec_m = rec_m;
-    }
-    if (timing)
-        for (EventOwner &e : up_ev)
-            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
-    // the record: [0, 4 m + 2) both sets of complex coefficients of the step, then the squared norms after the two rounds; the
-    // residual's |r|^2, |b|^2; the complex y
-    double *const d_h = d_up_rec, *const d_res = d_up_rec + 4 * (size_t)rec_m + 2, *const d_y = d_res + 2;
-    double *const h_rec = h_up, *const h_res = h_up + 4 * (size_t)rec_m + 2, *const h_y = h_res + 2;
-    double *const d_w = d_up_vec, *const d_r = d_up_vec + (size_t)n;
-    double *const d_xx = on_device ? x : d_up_vec + 2 * (size_t)n;
-    const double *d_bb = rhs;
-    const size_t nb = sizeof(double) * (size_t)n;
-
-    // the operator's values: the gather through the signed value map that factorize_mapped runs, into d_up_vals
-    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
-    {
-        const double *src = values;
-        if (!on_device) {
-            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            src = d_vin;
-        }
-        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
-    }
-    if (!on_device) {
-        HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-        d_bb = d_up_vec + 3 * (size_t)n;
-    }
-    HIPC(hipMemsetAsync(d_xx, 0, nb, STREAM), ERROR_HIP_MEMCPY);
-
-    const dim3 gk((unsigned)nblk);
-    auto residual = [&](double &rr, double &bb) -> int32_t { // r = b - A_new x with its two sums on the host (one synchronisation)
-        hipLaunchKernelGGL(k_kry_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, d_xx, d_bb, d_r, d_up_part);
-        hipLaunchKernelGGL(k_kry_reduce, dim3(2), b256, 0, STREAM, d_up_part, spmv_blocks, d_res);
-        HIPC(hipMemcpyAsync(h_res, d_res, 2 * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-        rr = h_res[0], bb = h_res[1];
-        return SUCCESSFUL_EXIT;
-    };
-    auto combine = [&](int32_t kk, double sign) -> int32_t { // x += sign Z y
-        for (int32_t j = 0; j < 2 * kk; j++) h_y[j] = sign * h_y[j];
-        HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * 2 * kk, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-        hipLaunchKernelGGL(k_zkry_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, (const double *)d_up_Z, kk, (const double *)d_y);
-        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (h_y may be rewritten)
-        return SUCCESSFUL_EXIT;
-    };
-    auto finish = [&](int32_t code, double relres) -> int32_t {
-        if (steps_out) *steps_out = (int32_t)updated_steps;
-        if (relres_out) *relres_out = relres;
-        if (!on_device) HIPC(hipMemcpy(x, d_xx, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
-        HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
-        return code;
-    };
-
-    double rr = 0.0, bb = 0.0;
-    int32_t code = residual(rr, bb);
-    if (code != SUCCESSFUL_EXIT) return code;
-    if (bb == 0.0) return finish(SUCCESSFUL_EXIT, 0.0); // x = 0
-    if (!std::isfinite(bb)) return finish(WARNING_NOT_CONVERGED, NAN);
-    const double bnorm = sqrt(bb);
-    double rnorm = sqrt(rr);
-
-    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
-    const PhaseTimes keep_times = times;
-    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done;
-    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
-    const std::vector<double> keep_omega = col_omega;
-    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
-    auto restore = [&]() {
-        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
-        col_omega = keep_omega;
-    };
-
-    std::vector<cplx> H((size_t)(m + 1) * m), sn((size_t)m), g((size_t)m + 1), y((size_t)m);
-    std::vector<double> cs((size_t)m);
-    while (rnorm > tol * bnorm && updated_steps < step_limit) {
-        updated_cycles++;
-        hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (const double *)d_res, (double *)d_up_V); // v_0 = r / |r|
-        std::fill(g.begin(), g.end(), cplx(0.0, 0.0));
-        g[0] = rnorm;
-        int32_t k = 0; // directions of this cycle that entered the least-squares problem
-        while (k < m && updated_steps < step_limit) {
-            double *const zk = d_up_Z + (size_t)k * n;
-            const double *const vk = d_up_V + (size_t)k * n;
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
-            code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
-            if (code != SUCCESSFUL_EXIT) break;
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
-            hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
-                               (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
-            const int32_t nv = k + 1;
-            for (int32_t round = 0; round < 2; round++) { // CGS2 with complex coefficients
-                double *const hr = d_h + (size_t)round * 2 * nv;
-                hipLaunchKernelGGL(k_zkry_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_up_V, nv, (double *)d_up_part);
-                hipLaunchKernelGGL(k_kry_reduce, dim3(2 * nv), b256, 0, STREAM, (const double *)d_up_part, nblk, hr);
-                hipLaunchKernelGGL(k_zkry_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_up_V, nv, (const double *)hr, (double *)d_up_part);
-                hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_up_part, nblk, d_h + 4 * (size_t)nv + round);
-            }
-            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)(d_h + 4 * (size_t)nv + 1), d_up_V + (size_t)(k + 1) * n);
-            if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
-            if (hipMemcpyAsync(h_rec, d_h, sizeof(double) * (4 * (size_t)nv + 2), hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
-            if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
-            if (code != SUCCESSFUL_EXIT) break;
-            if (timing)
-                for (int t = 0; t < 3; t++) {
-                    float ms = 0.0f;
-                    if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
-                }
-            bool finite = true;
-            for (int32_t j = 0; j < 4 * nv + 2; j++) finite = finite && std::isfinite(h_rec[j]);
-            if (!finite) break; // (leave the cycle with what there is)
-            updated_steps++;
-            for (int32_t j = 0; j < nv; j++) H[(size_t)j * m + k] = cplx(h_rec[2 * j] + h_rec[2 * (nv + j)], h_rec[2 * j + 1] + h_rec[2 * (nv + j) + 1]);
-            const double hn = sqrt(h_rec[4 * nv + 1]);
-            H[(size_t)(k + 1) * m + k] = hn;
-            for (int32_t j = 0; j < k; j++) { // the rotations so far: [c s; -conj(s) c]
-                const cplx a = H[(size_t)j * m + k], b = H[(size_t)(j + 1) * m + k];
-                H[(size_t)j * m + k] = cs[(size_t)j] * a + sn[(size_t)j] * b;
-                H[(size_t)(j + 1) * m + k] = -std::conj(sn[(size_t)j]) * a + cs[(size_t)j] * b;
-            }
-            // the new rotation takes (a, hn), hn real and not negative, to (a / |a| d, 0): c = |a| / d, s = (a / |a|) hn / d
-            const cplx a = H[(size_t)k * m + k];
-            const double aa = std::abs(a), d = std::hypot(aa, hn);
-            const cplx phase = aa > 0.0 ? a / aa : cplx(1.0, 0.0);
-            cs[(size_t)k] = d > 0.0 ? aa / d : 1.0, sn[(size_t)k] = d > 0.0 ? phase * (hn / d) : cplx(0.0, 0.0);
-            H[(size_t)k * m + k] = phase * d, H[(size_t)(k + 1) * m + k] = 0.0;
-            g[(size_t)k + 1] = -std::conj(sn[(size_t)k]) * g[(size_t)k];
-            g[(size_t)k] = cs[(size_t)k] * g[(size_t)k];
-            if (keep_verbose)
-                fprintf(stderr, "hipmf: solve_updated (complex): cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", (long long)updated_cycles, k + 1, std::abs(g[(size_t)k + 1]), bnorm);
-            k++;
-            if (std::abs(g[(size_t)k]) <= tol * bnorm || !(hn > 0.0)) break;
-        }
-        if (code != SUCCESSFUL_EXIT || k == 0) break;
-        for (int32_t i = k - 1; i >= 0; i--) { // back substitution
-            cplx t = g[(size_t)i];
-            for (int32_t j = i + 1; j < k; j++) t -= H[(size_t)i * m + j] * y[(size_t)j];
-            y[(size_t)i] = H[(size_t)i * m + i] != cplx(0.0, 0.0) ? t / H[(size_t)i * m + i] : cplx(0.0, 0.0);
-        }
-        for (int32_t j = 0; j < k; j++) h_y[2 * j] = y[(size_t)j].real(), h_y[2 * j + 1] = y[(size_t)j].imag();
-        code = combine(k, 1.0);
-        if (code != SUCCESSFUL_EXIT) break;
-        const double before = rnorm;
-        code = residual(rr, bb);
-        if (code != SUCCESSFUL_EXIT) break;
-        if (keep_verbose) fprintf(stderr, "hipmf: solve_updated (complex): cycle %lld: |r| %.3e -> %.3e\n", (long long)updated_cycles, before, sqrt(rr));
-        if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
-            code = combine(k, -1.0);
-            if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
-            if (code == SUCCESSFUL_EXIT) rnorm = sqrt(rr);
-            break;
-        }
-        rnorm = sqrt(rr);
-    }
-    restore();
-    if (code != SUCCESSFUL_EXIT) return code;
-    return finish(rnorm <= tol * bnorm ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED, rnorm / bnorm);
+    return solve_updated_core<UpdatedComplex>(x, rhs, values, true, rel_tol, max_steps, steps_out, relres_out, on_device);
 }
 
 // ---- the same for a block of right-hand sides (solver_hipmf_solve_updated_many; kernels_krylov_blocked.hpp) ----
@@ -3821,15 +3638,8 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
     }
     DeviceScope dev_scope(device);
     const int32_t n = S.n;
-    const int64_t nnz = S.nnz_a;
-    const double tol = rel_tol > 0.0 ? rel_tol : 1e-12;
-    int32_t restart = 30;
-    if (const char *e = getenv("HIPMF_UPDATED_RESTART")) {
-        const int v = atoi(e);
-        if (v >= 4 && v <= 200) restart = v;
-    }
-    const int32_t step_limit = max_steps > 0 ? max_steps : 4 * restart;
-    const bool timing = getenv("HIPMF_UPDATED_TIMING") && atoi(getenv("HIPMF_UPDATED_TIMING")) != 0;
+    const UpdatedParams par(rel_tol, max_steps);
+    const StepTimer timer{up_ev, STREAM, par.timing};
     updated_steps = updated_cycles = updated_blocks = updated_column_steps = 0;
     updated_ms[0] = updated_ms[1] = updated_ms[2] = 0.0;
     for (int32_t c = 0; c < nrhs; c++) {
@@ -3840,20 +3650,14 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
     // buffers: bases for min(nrhs, 16) columns, wider when a later call is; the restart length is halved (down to 4) when they do not fit
     const int32_t CW = std::min<int32_t>(nrhs, KRYB_COLS);
     const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
-    int32_t m = std::max(4, std::min(restart, n));
+    int32_t m = std::max(4, std::min(par.restart, n));
     if (ub_m < m || ub_cols < CW) {
         const int32_t cols = std::max(ub_cols, CW);
-        d_ub_V.reset(), d_ub_Z.reset();
         ub_m = ub_cols = 0;
-        int32_t mm = m;
-        for (;; mm = std::max(4, mm / 2)) {
-            if (d_ub_V.alloc((size_t)(mm + 1) * cols * n) == hipSuccess && d_ub_Z.alloc((size_t)mm * cols * n) == hipSuccess) break;
-            d_ub_V.reset(), d_ub_Z.reset();
-            (void)hipGetLastError();
-            if (mm == 4) {
-                last_error = "solve_updated_many: no device memory for the Krylov bases";
-                return ERROR_HIP_MALLOC;
-            }
+        const int32_t mm = grow_bases(d_ub_V, d_ub_Z, m, (size_t)cols * n);
+        if (mm == 0) {
+            last_error = "solve_updated_many: no device memory for the Krylov bases";
+            return ERROR_HIP_MALLOC;
         }
         const size_t pcol_new = std::max((size_t)(mm + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1));
         const size_t rec_new = (size_t)cols * (3 * (size_t)mm + 4);
@@ -3866,10 +3670,8 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
         ub_m = mm, ub_cols = cols;
     }
     m = std::min(m, ub_m);
-    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
-    if (timing)
-        for (EventOwner &e : up_ev)
-            if (!e) HIPC(hipEventCreate(e.put()), ERROR_HIP_SYNCHRONIZE);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(S.nnz_a, 1)), ERROR_HIP_MALLOC);
+    HIPC(timer.create(), ERROR_HIP_SYNCHRONIZE);
     const int64_t pcol = (int64_t)std::max((size_t)(ub_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1)); // partial-sum slots of a column
     // device record and its pinned mirror: the step's record, C (2 nv + 2) | the residuals' sums, 2 C | y, column c at c m
     const size_t off_res = (size_t)ub_cols * (2 * (size_t)ub_m + 2), off_y = off_res + 2 * (size_t)ub_cols;
@@ -3878,235 +3680,188 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
     const size_t nb = sizeof(double) * (size_t)n;
 
     // the operator's values, once per call, exactly as in solve_updated
-    const dim3 gv((unsigned)std::min<int64_t>(4096, (nnz + 255) / 256)), b256(256);
-    if (mapped) {
-        const double *src = values;
-        if (!on_device) {
-            HIPC(hipMemcpyAsync(d_vin, values, sizeof(double) * nnz_in, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            src = d_vin;
-        }
-        hipLaunchKernelGGL(k_gather_values, gv, b256, 0, STREAM, nnz, d_seg_ptr, d_seg_idx, src, d_up_vals);
-    } else if (!d_emap) {
-        HIPC(hipMemcpyAsync(d_up_vals, values, sizeof(double) * nnz, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-    } else {
-        const double *src = values;
-        if (!on_device) {
-            HIPC(hipMemcpyAsync(d_vlow, values, sizeof(double) * nnz_low, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            src = d_vlow;
-        }
-        hipLaunchKernelGGL(k_expand_values, gv, b256, 0, STREAM, nnz, d_emap, src, d_up_vals);
-    }
-
-    // the pass pairs below are ordinary unrefined solves: what they leave in the statistics of the ordinary solves is put back
-    const PhaseTimes keep_times = times;
-    const int32_t keep_nstep = opt.refinement_nstep, keep_ref_done = refinement_steps_done, keep_groups_last = block_groups_last;
-    const bool keep_verbose = opt.verbose, keep_in_rescue = in_rescue;
-    const std::vector<double> keep_omega = col_omega;
-    opt.refinement_nstep = 0, opt.verbose = false, in_rescue = true;
-    auto restore = [&]() {
-        times = keep_times, opt.refinement_nstep = keep_nstep, refinement_steps_done = keep_ref_done, opt.verbose = keep_verbose, in_rescue = keep_in_rescue;
-        block_groups_last = keep_groups_last;
-        col_omega = keep_omega;
-    };
+    const dim3 b256(256);
+    int32_t code = stage_values(d_up_vals, values, mapped, on_device);
+    if (code != SUCCESSFUL_EXIT) return code;
 
     bool all_converged = true;
-    int32_t code = SUCCESSFUL_EXIT;
-    std::vector<double> H, cs, sn, g; // per column c: H at c (m + 1) m, cs / sn at c m, g at c (m + 1)
-    H.resize((size_t)KRYB_COLS * (m + 1) * m), cs.resize((size_t)KRYB_COLS * m), sn.resize((size_t)KRYB_COLS * m), g.resize((size_t)KRYB_COLS * (m + 1));
-    for (int32_t j0 = 0; j0 < nrhs && code == SUCCESSFUL_EXIT; j0 += KRYB_COLS) {
-        const int32_t C = std::min<int32_t>(KRYB_COLS, nrhs - j0);
-        const uint32_t all = (1u << C) - 1u;
-        const int64_t vstr = (int64_t)C * n; // between two basis vectors of one column
-        updated_blocks++;
-        double *const d_w = d_ub_vec, *const d_r = d_ub_vec + (size_t)C * n;
-        double *const d_xx = on_device ? x + (int64_t)j0 * ld : d_ub_vec + 2 * (size_t)ub_cols * n;
-        const double *const d_bb = on_device ? rhs + (int64_t)j0 * ld : d_ub_vec + 3 * (size_t)ub_cols * n;
-        const int64_t xstr = on_device ? ld : (int64_t)n;
-        if (!on_device)
-            for (int32_t c = 0; c < C && code == SUCCESSFUL_EXIT; c++)
-                if (hipMemcpyAsync(d_ub_vec + 3 * (size_t)ub_cols * n + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, hipMemcpyHostToDevice, STREAM) != hipSuccess)
-                    code = ERROR_HIP_MEMCPY;
-        if (code != SUCCESSFUL_EXIT) break;
-        const dim3 gk((unsigned)nblk, (unsigned)C);
-        hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, d_xx, xstr, 0u, all); // x = 0
+    std::vector<GivensLsq<double>> lsq((size_t)KRYB_COLS, GivensLsq<double>(m)); // per column of a block
+    std::vector<double> hcol((size_t)m);
+    {
+        const NestedSolveGuard guard(*this);
+        guard.unrefined_quiet();
+        for (int32_t j0 = 0; j0 < nrhs && code == SUCCESSFUL_EXIT; j0 += KRYB_COLS) {
+            const int32_t C = std::min<int32_t>(KRYB_COLS, nrhs - j0);
+            const uint32_t all = (1u << C) - 1u;
+            const int64_t vstr = (int64_t)C * n; // between two basis vectors of one column
+            updated_blocks++;
+            double *const d_w = d_ub_vec, *const d_r = d_ub_vec + (size_t)C * n;
+            double *const d_xx = on_device ? x + (int64_t)j0 * ld : d_ub_vec + 2 * (size_t)ub_cols * n;
+            const double *const d_bb = on_device ? rhs + (int64_t)j0 * ld : d_ub_vec + 3 * (size_t)ub_cols * n;
+            const int64_t xstr = on_device ? ld : (int64_t)n;
+            if (!on_device)
+                for (int32_t c = 0; c < C && code == SUCCESSFUL_EXIT; c++)
+                    if (hipMemcpyAsync(d_ub_vec + 3 * (size_t)ub_cols * n + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, hipMemcpyHostToDevice, STREAM) != hipSuccess)
+                        code = ERROR_HIP_MEMCPY;
+            if (code != SUCCESSFUL_EXIT) break;
+            const dim3 gk((unsigned)nblk, (unsigned)C);
+            hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, d_xx, xstr, 0u, all); // x = 0
 
-        // R_c = B_c - A_new X_c and its two sums for the columns of `mask`, on the host after one synchronisation
-        auto residual = [&](uint32_t mask) -> int32_t {
-            hipLaunchKernelGGL(k_kryb_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)d_xx,
-                               xstr, d_bb, xstr, d_r, C, mask, (double *)d_ub_part, pcol);
-            hipLaunchKernelGGL(k_kryb_reduce, dim3(2, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, spmv_blocks, mask, d_res, (int64_t)2);
-            HIPC(hipMemcpyAsync(h_res, d_res, 2 * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-            return SUCCESSFUL_EXIT;
-        };
-        // X_c += Z_c y_c over the first kc[c] directions for the columns of `mask` (h_y, h_ub_cnt filled by the caller; no synchronisation:
-        // the residual that follows brings it)
-        auto combine = [&](uint32_t mask) -> int32_t {
-            HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * (size_t)C * m, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            HIPC(hipMemcpyAsync(d_ub_cnt, h_ub_cnt, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-            hipLaunchKernelGGL(k_kryb_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, xstr, (const double *)d_ub_Z, vstr, mask, (const int32_t *)d_ub_cnt, (const double *)d_y,
-                               (int64_t)m);
-            return SUCCESSFUL_EXIT;
-        };
+            // R_c = B_c - A_new X_c and its two sums for the columns of `mask`, on the host after one synchronisation
+            auto residual = [&](uint32_t mask) -> int32_t {
+                hipLaunchKernelGGL(k_kryb_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)d_xx,
+                                   xstr, d_bb, xstr, d_r, C, mask, (double *)d_ub_part, pcol);
+                hipLaunchKernelGGL(k_kryb_reduce, dim3(2, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, spmv_blocks, mask, d_res, (int64_t)2);
+                HIPC(hipMemcpyAsync(h_res, d_res, 2 * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+                return SUCCESSFUL_EXIT;
+            };
+            // X_c += Z_c y_c over the first kc[c] directions for the columns of `mask` (h_y, h_ub_cnt filled by the caller; no synchronisation:
+            // the residual that follows brings it)
+            auto combine = [&](uint32_t mask) -> int32_t {
+                HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * (size_t)C * m, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+                HIPC(hipMemcpyAsync(d_ub_cnt, h_ub_cnt, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+                hipLaunchKernelGGL(k_kryb_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, xstr, (const double *)d_ub_Z, vstr, mask, (const int32_t *)d_ub_cnt, (const double *)d_y,
+                                   (int64_t)m);
+                return SUCCESSFUL_EXIT;
+            };
 
-        // per column of the block
-        double bnorm[KRYB_COLS], rnorm[KRYB_COLS];
-        int32_t steps[KRYB_COLS], kc[KRYB_COLS];
-        bool nan_rhs[KRYB_COLS];
-        uint32_t done = 0; // finished for the rest of the call
-        code = residual(all);
-        if (code != SUCCESSFUL_EXIT) break;
-        for (int32_t c = 0; c < C; c++) {
-            const double rr = h_res[2 * c], bb = h_res[2 * c + 1];
-            steps[c] = 0, nan_rhs[c] = false, bnorm[c] = 0.0, rnorm[c] = 0.0;
-            if (bb == 0.0) done |= 1u << c; // x_c = 0
-            else if (!std::isfinite(bb)) done |= 1u << c, nan_rhs[c] = true;
-            else {
-                bnorm[c] = sqrt(bb), rnorm[c] = sqrt(rr);
-                if (!(rnorm[c] > tol * bnorm[c])) done |= 1u << c;
-            }
-        }
-        while (done != all) {
-            updated_cycles++;
-            // v_0 = r / |r| for the columns still at work, zeros for the others (d_res holds |r_c|^2 of every such column's last residual)
-            hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (int64_t)n, (const double *)d_res, (int64_t)2, (double *)d_ub_V, (int64_t)n,
-                               all & ~done, done);
-            uint32_t parked = done; // ... for the rest of this cycle
+            // per column of the block
+            double bnorm[KRYB_COLS], rnorm[KRYB_COLS];
+            int32_t steps[KRYB_COLS], kc[KRYB_COLS];
+            bool nan_rhs[KRYB_COLS];
+            uint32_t done = 0; // finished for the rest of the call
+            code = residual(all);
+            if (code != SUCCESSFUL_EXIT) break;
             for (int32_t c = 0; c < C; c++) {
-                kc[c] = 0;
-                if ((done >> c) & 1u) continue;
-                std::fill(g.begin() + (size_t)c * (m + 1), g.begin() + (size_t)(c + 1) * (m + 1), 0.0);
-                g[(size_t)c * (m + 1)] = rnorm[c];
-            }
-            for (int32_t k = 0; k < m && parked != all; k++) {
-                const uint32_t act = all & ~parked;
-                double *const zk = d_ub_Z + (size_t)k * vstr;
-                const double *const vk = d_ub_V + (size_t)k * vstr;
-                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[0], STREAM);
-                code = solve_core(zk, vk, C, n, true); // Z_k = M^{-1} V_k: one blocked pass pair
-                if (code != SUCCESSFUL_EXIT) break;
-                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[1], STREAM);
-                hipLaunchKernelGGL(k_kryb_spmv, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)zk, d_w, C,
-                                   act); // W = A_new Z_k
-                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[2], STREAM);
-                const int32_t nv = k + 1;
-                const int64_t rstr = 2 * (int64_t)nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
-                for (int32_t round = 0; round < 2; round++) { // CGS2
-                    double *const hr = d_rec + (size_t)round * nv;
-                    hipLaunchKernelGGL(k_kryb_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_ub_V, vstr, nv, act, (double *)d_ub_part, pcol);
-                    hipLaunchKernelGGL(k_kryb_reduce, dim3((unsigned)nv, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, hr, rstr);
-                    hipLaunchKernelGGL(k_kryb_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_ub_V, vstr, nv, act, (const double *)hr, rstr, (double *)d_ub_part, pcol);
-                    hipLaunchKernelGGL(k_kryb_reduce, dim3(1, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, d_rec + 2 * (size_t)nv + round, rstr);
+                const double rr = h_res[2 * c], bb = h_res[2 * c + 1];
+                steps[c] = 0, nan_rhs[c] = false, bnorm[c] = 0.0, rnorm[c] = 0.0;
+                if (bb == 0.0) done |= 1u << c; // x_c = 0
+                else if (!std::isfinite(bb)) done |= 1u << c, nan_rhs[c] = true;
+                else {
+                    bnorm[c] = sqrt(bb), rnorm[c] = sqrt(rr);
+                    if (!(rnorm[c] > par.tol * bnorm[c])) done |= 1u << c;
                 }
-                double *const vnext = d_ub_V + (size_t)(k + 1) * vstr;
-                hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (int64_t)n, (const double *)(d_rec + 2 * (size_t)nv + 1), rstr, vnext, (int64_t)n,
-                                   act, parked);
-                if (timing) (void)hipEventRecord((hipEvent_t)up_ev[3], STREAM);
-                if (hipMemcpyAsync(h_rec, d_rec, sizeof(double) * (size_t)C * rstr, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
-                if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
-                if (code != SUCCESSFUL_EXIT) break;
-                if (timing)
-                    for (int t = 0; t < 3; t++) {
-                        float ms = 0.0f;
-                        if (hipEventElapsedTime(&ms, (hipEvent_t)up_ev[t], (hipEvent_t)up_ev[t + 1]) == hipSuccess) updated_ms[t] += ms;
-                    }
-                uint32_t newly = 0;
-                bool counted = false;
+            }
+            while (done != all) {
+                updated_cycles++;
+                // v_0 = r / |r| for the columns still at work, zeros for the others (d_res holds |r_c|^2 of every such column's last residual)
+                hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_r, (int64_t)n, (const double *)d_res, (int64_t)2, (double *)d_ub_V, (int64_t)n,
+                                   all & ~done, done);
+                uint32_t parked = done; // ... for the rest of this cycle
                 for (int32_t c = 0; c < C; c++) {
-                    if (!((act >> c) & 1u)) continue;
-                    const double *const rec = h_rec + (size_t)c * rstr;
-                    bool finite = true;
-                    for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(rec[j]);
-                    if (!finite) { // (the column leaves the cycle with the directions before this one; the step is not counted for it)
-                        newly |= 1u << c;
+                    kc[c] = 0;
+                    if ((done >> c) & 1u) continue;
+                    lsq[(size_t)c].reset(rnorm[c]);
+                }
+                for (int32_t k = 0; k < m && parked != all; k++) {
+                    const uint32_t act = all & ~parked;
+                    double *const zk = d_ub_Z + (size_t)k * vstr;
+                    const double *const vk = d_ub_V + (size_t)k * vstr;
+                    timer.mark(0);
+                    code = solve_core(zk, vk, C, n, true); // Z_k = M^{-1} V_k: one blocked pass pair
+                    if (code != SUCCESSFUL_EXIT) break;
+                    timer.mark(1);
+                    hipLaunchKernelGGL(k_kryb_spmv, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)zk, d_w, C,
+                                       act); // W = A_new Z_k
+                    timer.mark(2);
+                    const int32_t nv = k + 1;
+                    const int64_t rstr = 2 * (int64_t)nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
+                    for (int32_t round = 0; round < 2; round++) { // CGS2
+                        double *const hr = d_rec + (size_t)round * nv;
+                        hipLaunchKernelGGL(k_kryb_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_ub_V, vstr, nv, act, (double *)d_ub_part, pcol);
+                        hipLaunchKernelGGL(k_kryb_reduce, dim3((unsigned)nv, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, hr, rstr);
+                        hipLaunchKernelGGL(k_kryb_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_ub_V, vstr, nv, act, (const double *)hr, rstr, (double *)d_ub_part, pcol);
+                        hipLaunchKernelGGL(k_kryb_reduce, dim3(1, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, d_rec + 2 * (size_t)nv + round, rstr);
+                    }
+                    double *const vnext = d_ub_V + (size_t)(k + 1) * vstr;
+                    hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (int64_t)n, (const double *)(d_rec + 2 * (size_t)nv + 1), rstr, vnext, (int64_t)n,
+                                       act, parked);
+                    timer.mark(3);
+                    if (hipMemcpyAsync(h_rec, d_rec, sizeof(double) * (size_t)C * rstr, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+                    if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE;
+                    if (code != SUCCESSFUL_EXIT) break;
+                    timer.add(updated_ms);
+                    uint32_t newly = 0;
+                    bool counted = false;
+                    for (int32_t c = 0; c < C; c++) {
+                        if (!((act >> c) & 1u)) continue;
+                        const double *const rec = h_rec + (size_t)c * rstr;
+                        bool finite = true;
+                        for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(rec[j]);
+                        if (!finite) { // (the column leaves the cycle with the directions before this one; the step is not counted for it)
+                            newly |= 1u << c;
+                            continue;
+                        }
+                        steps[c]++, updated_column_steps++, counted = true;
+                        for (int32_t j = 0; j < nv; j++) hcol[(size_t)j] = rec[j] + rec[nv + j];
+                        const double hn = sqrt(rec[2 * nv + 1]);
+                        lsq[(size_t)c].push(k, hcol.data(), hn);
+                        const double *const gc = lsq[(size_t)c].g.data();
+                        if (guard.verbose)
+                            fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", j0 + c, (long long)updated_cycles, k + 1,
+                                    fabs(gc[k + 1]), bnorm[c]);
+                        kc[c] = k + 1;
+                        if (fabs(gc[k + 1]) <= par.tol * bnorm[c] || !(hn > 0.0) || steps[c] >= par.step_limit) newly |= 1u << c;
+                    }
+                    if (counted) updated_steps++;
+                    parked |= newly;
+                    // a column parked by this step: its next basis vector (written before the host knew) becomes zeros
+                    if (newly && parked != all && k + 1 < m)
+                        hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, vnext, (int64_t)n, 0u, newly);
+                }
+                if (code != SUCCESSFUL_EXIT) break;
+                // the end of the cycle: per column the back substitution over its own directions
+                uint32_t moved = 0;
+                for (int32_t c = 0; c < C; c++) {
+                    h_ub_cnt[c] = 0;
+                    if ((done >> c) & 1u) continue;
+                    if (kc[c] == 0) { // (not one usable direction: the column ends with what it has)
+                        done |= 1u << c;
                         continue;
                     }
-                    steps[c]++, updated_column_steps++, counted = true;
-                    double *const Hc = H.data() + (size_t)c * (m + 1) * m, *const csc = cs.data() + (size_t)c * m, *const snc = sn.data() + (size_t)c * m;
-                    double *const gc = g.data() + (size_t)c * (m + 1);
-                    for (int32_t j = 0; j < nv; j++) Hc[(size_t)j * m + k] = rec[j] + rec[nv + j];
-                    const double hn = sqrt(rec[2 * nv + 1]);
-                    Hc[(size_t)(k + 1) * m + k] = hn;
-                    for (int32_t j = 0; j < k; j++) { // the Givens rotations so far
-                        const double a = Hc[(size_t)j * m + k], b = Hc[(size_t)(j + 1) * m + k];
-                        Hc[(size_t)j * m + k] = csc[j] * a + snc[j] * b;
-                        Hc[(size_t)(j + 1) * m + k] = -snc[j] * a + csc[j] * b;
-                    }
-                    const double a = Hc[(size_t)k * m + k], b = Hc[(size_t)(k + 1) * m + k], d = std::hypot(a, b);
-                    csc[k] = d > 0.0 ? a / d : 1.0, snc[k] = d > 0.0 ? b / d : 0.0;
-                    Hc[(size_t)k * m + k] = d, Hc[(size_t)(k + 1) * m + k] = 0.0;
-                    gc[k + 1] = -snc[k] * gc[k];
-                    gc[k] = csc[k] * gc[k];
-                    if (keep_verbose)
-                        fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", j0 + c, (long long)updated_cycles, k + 1,
-                                fabs(gc[k + 1]), bnorm[c]);
-                    kc[c] = k + 1;
-                    if (fabs(gc[k + 1]) <= tol * bnorm[c] || !(hn > 0.0) || steps[c] >= step_limit) newly |= 1u << c;
+                    lsq[(size_t)c].solve(kc[c], h_y + (size_t)c * m);
+                    h_ub_cnt[c] = kc[c];
+                    moved |= 1u << c;
                 }
-                if (counted) updated_steps++;
-                parked |= newly;
-                // a column parked by this step: its next basis vector (written before the host knew) becomes zeros
-                if (newly && parked != all && k + 1 < m)
-                    hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, vnext, (int64_t)n, 0u, newly);
-            }
-            if (code != SUCCESSFUL_EXIT) break;
-            // the end of the cycle: per column the back substitution over its own directions
-            uint32_t moved = 0;
-            for (int32_t c = 0; c < C; c++) {
-                h_ub_cnt[c] = 0;
-                if ((done >> c) & 1u) continue;
-                if (kc[c] == 0) { // (not one usable direction: the column ends with what it has)
-                    done |= 1u << c;
-                    continue;
-                }
-                const double *const Hc = H.data() + (size_t)c * (m + 1) * m, *const gc = g.data() + (size_t)c * (m + 1);
-                double *const yc = h_y + (size_t)c * m;
-                for (int32_t i = kc[c] - 1; i >= 0; i--) {
-                    double t = gc[i];
-                    for (int32_t j = i + 1; j < kc[c]; j++) t -= Hc[(size_t)i * m + j] * yc[j];
-                    yc[i] = Hc[(size_t)i * m + i] != 0.0 ? t / Hc[(size_t)i * m + i] : 0.0;
-                }
-                h_ub_cnt[c] = kc[c];
-                moved |= 1u << c;
-            }
-            if (!moved) continue;
-            code = combine(moved);
-            if (code == SUCCESSFUL_EXIT) code = residual(moved);
-            if (code != SUCCESSFUL_EXIT) break;
-            uint32_t back = 0;
-            for (int32_t c = 0; c < C; c++) {
-                if (!((moved >> c) & 1u)) continue;
-                const double now = sqrt(h_res[2 * c]);
-                if (keep_verbose) fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld: |r| %.3e -> %.3e\n", j0 + c, (long long)updated_cycles, rnorm[c], now);
-                if (!(now < rnorm[c])) { // no gain (or not a number): the column's cycle is taken back, x_c is the best iterate
-                    back |= 1u << c, done |= 1u << c;
-                    continue;
-                }
-                rnorm[c] = now;
-                if (!(rnorm[c] > tol * bnorm[c]) || steps[c] >= step_limit) done |= 1u << c;
-            }
-            if (back) {
-                for (int32_t c = 0; c < C; c++)
-                    if ((back >> c) & 1u)
-                        for (int32_t j = 0; j < kc[c]; j++) h_y[(size_t)c * m + j] = -h_y[(size_t)c * m + j];
-                code = combine(back);
-                if (code == SUCCESSFUL_EXIT) code = residual(back);
+                if (!moved) continue;
+                code = combine(moved);
+                if (code == SUCCESSFUL_EXIT) code = residual(moved);
                 if (code != SUCCESSFUL_EXIT) break;
-                for (int32_t c = 0; c < C; c++)
-                    if ((back >> c) & 1u) rnorm[c] = sqrt(h_res[2 * c]);
+                uint32_t back = 0;
+                for (int32_t c = 0; c < C; c++) {
+                    if (!((moved >> c) & 1u)) continue;
+                    const double now = sqrt(h_res[2 * c]);
+                    if (guard.verbose) fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld: |r| %.3e -> %.3e\n", j0 + c, (long long)updated_cycles, rnorm[c], now);
+                    if (!(now < rnorm[c])) { // no gain (or not a number): the column's cycle is taken back, x_c is the best iterate
+                        back |= 1u << c, done |= 1u << c;
+                        continue;
+                    }
+                    rnorm[c] = now;
+                    if (!(rnorm[c] > par.tol * bnorm[c]) || steps[c] >= par.step_limit) done |= 1u << c;
+                }
+                if (back) {
+                    for (int32_t c = 0; c < C; c++)
+                        if ((back >> c) & 1u)
+                            for (int32_t j = 0; j < kc[c]; j++) h_y[(size_t)c * m + j] = -h_y[(size_t)c * m + j];
+                    code = combine(back);
+                    if (code == SUCCESSFUL_EXIT) code = residual(back);
+                    if (code != SUCCESSFUL_EXIT) break;
+                    for (int32_t c = 0; c < C; c++)
+                        if ((back >> c) & 1u) rnorm[c] = sqrt(h_res[2 * c]);
+                }
             }
+            if (code != SUCCESSFUL_EXIT) break;
+            for (int32_t c = 0; c < C; c++) {
+                const double rel = nan_rhs[c] ? NAN : (bnorm[c] > 0.0 ? rnorm[c] / bnorm[c] : 0.0);
+                if (steps_out) steps_out[j0 + c] = steps[c];
+                if (relres_out) relres_out[j0 + c] = rel;
+                if (nan_rhs[c] || (bnorm[c] > 0.0 && !(rnorm[c] <= par.tol * bnorm[c]))) all_converged = false;
+                if (!on_device && hipMemcpyAsync(x + (int64_t)(j0 + c) * ld, d_xx + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
+            }
+            if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE; // (the staging blocks are the next block's)
         }
-        if (code != SUCCESSFUL_EXIT) break;
-        for (int32_t c = 0; c < C; c++) {
-            const double rel = nan_rhs[c] ? NAN : (bnorm[c] > 0.0 ? rnorm[c] / bnorm[c] : 0.0);
-            if (steps_out) steps_out[j0 + c] = steps[c];
-            if (relres_out) relres_out[j0 + c] = rel;
-            if (nan_rhs[c] || (bnorm[c] > 0.0 && !(rnorm[c] <= tol * bnorm[c]))) all_converged = false;
-            if (!on_device && hipMemcpyAsync(x + (int64_t)(j0 + c) * ld, d_xx + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
-        }
-        if (code == SUCCESSFUL_EXIT && hipStreamSynchronize(STREAM) != hipSuccess) code = ERROR_HIP_SYNCHRONIZE; // (the staging blocks are the next block's)
     }
-    restore();
     if (code != SUCCESSFUL_EXIT) return code;
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     return all_converged ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
@@ -4127,7 +3882,7 @@ int32_t Solver::adopt_factor(const double *d_values) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!d_values) return ERROR_NULL_POINTER;
     DeviceScope dev_scope(device);
-    int32_t lc = load_values(d_values, true);
+    int32_t lc = stage_values(d_vals, d_values, false, true);
     if (lc != SUCCESSFUL_EXIT) return lc;
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
     n_perturbed = n_zero_pivot = 0;
@@ -5047,13 +4802,6 @@ int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *ou
     analysis_solves = 0;
     if (option != 1) return SUCCESSFUL_EXIT;
 
-    // the statistics of the caller's solve stay as that solve left them
-    const double keep_omega = last_omega, keep_res = last_residual_inf, keep_relres = krylov_last_relres;
-    const std::vector<double> keep_col = col_omega;
-    const PhaseTimes keep_times = times;
-    const int32_t keep_steps = refinement_steps_done, keep_nstep = opt.refinement_nstep;
-    const int64_t keep_kry = krylov_iterations;
-    const bool keep_verbose = opt.verbose;
     auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx) -> int32_t {
         hipLaunchKernelGGL(k_ea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, n, mode, v, pv, pi);
         hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, STREAM, mode, (const double *)pv, (const int32_t *)pi, (double *)(sc + 5), si);
@@ -5136,10 +4884,11 @@ int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *ou
         return SUCCESSFUL_EXIT;
     };
     double e1 = 0.0, e2 = 0.0;
-    if (n - n2 > 0) code = estimate(W1, &e1);
-    if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
-    last_omega = keep_omega, last_residual_inf = keep_res, krylov_last_relres = keep_relres, col_omega = keep_col, times = keep_times;
-    refinement_steps_done = keep_steps, opt.refinement_nstep = keep_nstep, krylov_iterations = keep_kry, opt.verbose = keep_verbose;
+    {
+        const NestedSolveGuard guard(*this); // the statistics of the caller's solve stay as that solve left them
+        if (n - n2 > 0) code = estimate(W1, &e1);
+        if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
+    }
     if (code != SUCCESSFUL_EXIT) return code;
     const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
     out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
@@ -5200,13 +4949,6 @@ int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, do
     analysis_solves = 0;
     if (option != 1) return SUCCESSFUL_EXIT;
 
-    // the statistics of the caller's solve stay as that solve left them
-    const double keep_omega = last_omega, keep_res = last_residual_inf, keep_relres = krylov_last_relres;
-    const std::vector<double> keep_col = col_omega;
-    const PhaseTimes keep_times = times;
-    const int32_t keep_steps = refinement_steps_done, keep_nstep = opt.refinement_nstep;
-    const int64_t keep_kry = krylov_iterations;
-    const bool keep_verbose = opt.verbose;
     // sum |v_i| (mode 0) or max |v_i| and its first index (mode 1) over the moduli; with jprev >= 0 also |v_jprev| (same arithmetic)
     auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) -> int32_t {
         hipLaunchKernelGGL(k_zea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, nc, mode, v, pv, pi);
@@ -5284,10 +5026,11 @@ int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, do
         return SUCCESSFUL_EXIT;
     };
     double e1 = 0.0, e2 = 0.0;
-    if (nc - n2 > 0) code = estimate(W1, &e1);
-    if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
-    last_omega = keep_omega, last_residual_inf = keep_res, krylov_last_relres = keep_relres, col_omega = keep_col, times = keep_times;
-    refinement_steps_done = keep_steps, opt.refinement_nstep = keep_nstep, krylov_iterations = keep_kry, opt.verbose = keep_verbose;
+    {
+        const NestedSolveGuard guard(*this); // the statistics of the caller's solve stay as that solve left them
+        if (nc - n2 > 0) code = estimate(W1, &e1);
+        if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
+    }
     if (code != SUCCESSFUL_EXIT) return code;
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;

@@ -179,8 +179,7 @@ struct SolverUpdated {
     DeviceArray<double> d_up_vals, d_up_V, d_up_Z, d_up_vec, d_up_part, d_up_rec;
     PinnedArray<double> h_up;
     int32_t up_m = 0;       // restart length V and Z are allocated for (0: not allocated)
-    int32_t up_rec_m = 0;   // ... and the record / its mirror
-    int32_t up_zrec_m = 0;  // ... when the complex form sized them (twice the coefficients per step; == up_rec_m while that holds)
+    int32_t up_rec_m = 0;   // ... and the partial sums, the record and its mirror (always sized for complex coefficients)
     EventOwner up_ev[4];    // HIPMF_UPDATED_TIMING=1: around the pass pair, the SpMV and the Arnoldi kernels of a step
     // solver_hipmf_solve_updated_many (kernels_krylov_blocked.hpp): bases of a block of columns, V[(k C + c) n + i], of their own -- the
     // single form's stay as they are --, four n x C blocks (W, R, X, B; the device form uses the caller's x and b), partial sums per column,
@@ -550,7 +549,11 @@ class Solver : public SolverDevice {
     bool slab64 = false;                    // HIPMF_SOLVE_SLAB64=1: same slab shape in both solve paths (bitwise comparable)
     int32_t sf_err[2] = {0, 0};
     std::vector<int32_t> h_emap;
-    int32_t load_values(const double *values, bool on_device); // values (CSR order of the caller) -> d_vals
+    // values (CSR order of the caller, or the inputs of the value map: mapped) -> dst, nnz doubles in the handle's CSR order
+    int32_t stage_values(double *dst, const double *values, bool mapped, bool on_device);
+    // the flexible GMRES of solve_updated and solve_updated_complex; P: the arithmetic (UpdatedReal, UpdatedComplex in numeric.cpp)
+    template <class P>
+    int32_t solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, bool on_device);
     int64_t n_lists = 0;            // entries of d_lists
     static constexpr int32_t MAX_SOLVE_LANES = 4;
     int32_t solve_lanes = 1;   // HIPMF_SOLVE_LANES (1..4).  One since late round 4: two launches full of workgroups that wait for each other's
