@@ -37,16 +37,18 @@
 
 namespace hipmf {
 
-#define HIPC(call, code)                                                                       \
+// (HIPS: the same check outside the Solver's members -- the launch policies below -- on the Solver s)
+#define HIPS(s, call, code)                                                                    \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
         if (e_ != hipSuccess) {                                                                \
-            std::lock_guard<std::mutex> lock_(err_mutex); /* (the planning thread of initialize reports through the same string) */ \
-            last_error = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            if (opt.verbose) fprintf(stderr, "hipmf: %s\n", last_error.c_str());               \
+            std::lock_guard<std::mutex> lock_((s).err_mutex); /* (the planning thread of initialize reports through the same string) */ \
+            (s).last_error = std::string(#call) + ": " + hipGetErrorString(e_);                \
+            if ((s).opt.verbose) fprintf(stderr, "hipmf: %s\n", (s).last_error.c_str());       \
             return (code);                                                                     \
         }                                                                                      \
     } while (0)
+#define HIPC(call, code) HIPS(*this, call, code)
 
 #define STREAM ((hipStream_t)stream)
 
@@ -3420,6 +3422,153 @@ struct UpdatedComplex {
     static void combine(dim3 g, hipStream_t st, int64_t n, double *x, const double *Z, int32_t nv, const double *y) { hipLaunchKernelGGL(k_zkry_combine, g, dim3(256), 0, st, n, x, Z, nv, y); }
 };
 
+// The transposed pass pair on one vector (kernels_solve_transpose.hpp) or on a block of TR_KB (kernels_solve_transpose_blocked.hpp): the
+// six kernels, the workspace, and the column stride xs of the block, which the blocked kernels take right after the vector -- their last
+// pointer (launch; the small-front kernels end with the leading dimension of their LDS panel: launch_ld).
+struct TrSingle {
+    static constexpr auto fwd_small = k_tr_fwd_small;
+    static constexpr auto assemble = k_tr_assemble;
+    static constexpr auto fwd = k_tr_gemv<true>, bwd = k_tr_gemv<false>;
+    static constexpr auto gather = k_tr_gather;
+    static constexpr auto bwd_small = k_tr_bwd_small;
+    static double *work(Solver &s) { return s.d_work_t; }
+    template <class K, class... A> static void launch(K k, dim3 g, hipStream_t st, int64_t, const A &...a) { hipLaunchKernelGGL(k, g, dim3(256), 0, st, a...); }
+    template <class K, class... A> static void launch_ld(K k, dim3 g, size_t lds, hipStream_t st, int64_t, int32_t ld, const A &...a) { hipLaunchKernelGGL(k, g, dim3(64), lds, st, a..., ld); }
+};
+struct TrBlocked {
+    static constexpr auto fwd_small = k_tr_fwd_small_blk;
+    static constexpr auto assemble = k_tr_assemble_blk;
+    static constexpr auto fwd = k_tr_gemm_blk<true>, bwd = k_tr_gemm_blk<false>;
+    static constexpr auto gather = k_tr_gather_blk;
+    static constexpr auto bwd_small = k_tr_bwd_small_blk;
+    static double *work(Solver &s) { return s.d_work_tb; }
+    template <class K, class... A> static void launch(K k, dim3 g, hipStream_t st, int64_t xs, const A &...a) { hipLaunchKernelGGL(k, g, dim3(256), 0, st, a..., xs); }
+    template <class K, class... A> static void launch_ld(K k, dim3 g, size_t lds, hipStream_t st, int64_t xs, int32_t ld, const A &...a) { hipLaunchKernelGGL(k, g, dim3(64), lds, st, a..., xs, ld); }
+};
+
+// What Solver::tr_refine launches for the columns it refines: the residual with its norm words (|r|, omega per column: words on the
+// device and their pinned mirror), the entry of the residuals into xp, the pass pair (Pass), the exit of xp into x (mode 1: x += the
+// correction, 2: x -= it).  mask: the columns a launch works on.
+struct TrColumn { // one column through the single kernels, on buffers tr_prepare() made: x, b, then r and xp in d_tvec
+    typedef TrSingle Pass;
+    static constexpr size_t words = 2;
+    Solver &s;
+    double *x;
+    const double *b;
+    const int32_t n = s.S.n;
+    const dim3 g = dim3((n + 255) / 256);
+    double *const xp = s.d_tvec + 2 * (size_t)n, *const r = s.d_tvec + 3 * (size_t)n; // (xp: after a correction step, the permuted correction)
+    unsigned long long *d_nrm() const { return s.d_tnrm; }
+    double *h_nrm() const { return s.h_tnrm; }
+    void residual(hipStream_t st, uint64_t) const { hipLaunchKernelGGL(k_tr_spmv, g, dim3(256), 0, st, n, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_vals, (const double *)x, b, r, d_nrm()); }
+    void perm_in(hipStream_t st, uint64_t) const { hipLaunchKernelGGL(k_tr_perm_in, g, dim3(256), 0, st, n, s.d_perm, s.d_cs, (const double *)r, xp); }
+    void perm_out(hipStream_t st, int32_t mode, uint64_t) const { hipLaunchKernelGGL(k_perm_out, g, dim3(256), 0, st, n, s.d_rperm, s.d_rs, (const double *)xp, x, mode); }
+};
+struct TrColumns { // nk columns of a block through the _cols kernels, on the buffers of tr_prepare_blocked(): r and xp in d_tblk
+    typedef TrBlocked Pass;
+    static constexpr size_t words = 2 * TR_KB;
+    Solver &s;
+    double *X;
+    int64_t xs;
+    const double *B;
+    int64_t bs;
+    int32_t nk;
+    const int32_t n = s.S.n;
+    const dim3 g = dim3((n + 255) / 256), gp = dim3((n + 255) / 256, TR_KB / PERM_CW);
+    double *const xp = s.d_tblk + 2 * (size_t)n * TR_KB, *const r = s.d_tblk + 3 * (size_t)n * TR_KB;
+    unsigned long long *d_nrm() const { return s.d_tnrm_blk; }
+    double *h_nrm() const { return s.h_tnrm_blk; }
+    void residual(hipStream_t st, uint64_t mask) const {
+        hipLaunchKernelGGL(k_tr_residual_cols, g, dim3(256), 0, st, n, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_vals, (const double *)X, xs, B, bs, r, (int64_t)n, d_nrm(), nk, mask);
+    }
+    void perm_in(hipStream_t st, uint64_t mask) const { hipLaunchKernelGGL(k_tr_perm_in_cols, gp, dim3(256), 0, st, n, s.d_perm, s.d_cs, (const double *)r, (int64_t)n, xp, (int64_t)n, mask, nk); }
+    void perm_out(hipStream_t st, int32_t mode, uint64_t mask) const { hipLaunchKernelGGL(k_perm_out_cols, gp, dim3(256), 0, st, n, s.d_rperm, s.d_rs, (const double *)xp, (int64_t)n, X, xs, mode, mask, nk); }
+};
+
+// The buffers and sizes the launches of an error analysis share: ne elements per vector, their grid, the partial results of a reduction
+// (values, indices), the eight scalar words (maxima as bits; [5], [6] the results of a reduction) and the integer words ([0] a count or
+// an index, [1] the flag of the real sign kernel).
+struct EaWork {
+    hipStream_t st;
+    int32_t ne;
+    dim3 g;
+    double *pv;
+    int32_t *pi;
+    unsigned long long *sc;
+    int32_t *si;
+};
+// What differs between the error analysis of a real matrix (k_ea_*, kernels_solve_transpose.hpp) and of a complex one held as its
+// real-equivalent system (k_zea_*, kernels_error_analysis_complex.hpp; |.| the modulus): the elements per vector, the launches, whether
+// the ordinary pass pair also applies A^{-T}, and two steps of the 1-norm estimator (sign, reduce).
+struct EaReal {
+    static int32_t elements(int32_t n) { return n; }
+    static bool own_transpose(const Solver &s) { return s.S.sym_mode || s.d_tptr; } // A^T = A (L D L^T fronts, symmetric storage)
+    static void rows(const Solver &s, const EaWork &w, const double *X, const double *B, double *R, double *AX, double *AR) {
+        hipLaunchKernelGGL(k_ea_rows, w.g, dim3(256), 0, w.st, w.ne, s.d_rp, s.d_ci, s.d_vals, s.d_tptr, s.d_tidx, s.d_arow, X, B, R, AX, AR, w.sc);
+    }
+    static void split(const EaWork &w, double tau_scale, double NX, const double *R, const double *AX, const double *AR, const double *B, double *W1, double *W2) {
+        hipLaunchKernelGGL(k_ea_split, w.g, dim3(256), 0, w.st, w.ne, tau_scale, NX, R, AX, AR, B, W1, W2, w.sc, w.si);
+    }
+    static void hadamard(const EaWork &w, const double *d, const double *v, double *y) { hipLaunchKernelGGL(k_ea_hadamard, w.g, dim3(256), 0, w.st, w.ne, d, v, y); }
+    static void fill(const EaWork &w, int32_t mode, int32_t j, double *v) { hipLaunchKernelGGL(k_ea_fill, w.g, dim3(256), 0, w.st, w.ne, mode, j, v); }
+    // xi = sign(y); *go_on: the iteration continues.  dlacn2: not after a repeated sign vector (the kernel's flag, not looked at the first
+    // time, when xi starts from zeros) and not without growth of the estimate
+    static int32_t sign(Solver &s, const EaWork &w, const double *y, double *xi, bool first, bool grew, bool *go_on) {
+        int32_t changed = 1;
+        if (first) HIPS(s, hipMemsetAsync(xi, 0, sizeof(double) * (size_t)w.ne, w.st), ERROR_HIP_MEMCPY);
+        else HIPS(s, hipMemsetAsync(w.si + 1, 0, sizeof(int32_t), w.st), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_ea_sign, w.g, dim3(256), 0, w.st, w.ne, y, xi, w.si + 1);
+        if (!first) {
+            HIPS(s, hipMemcpyAsync(&changed, w.si + 1, sizeof(int32_t), hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+            HIPS(s, hipStreamSynchronize(w.st), ERROR_HIP_SYNCHRONIZE);
+        }
+        *go_on = first || (changed && grew);
+        return SUCCESSFUL_EXIT;
+    }
+    // sum |v_i| (mode 0) or max |v_i| and its first index (mode 1); with jprev >= 0 also v_jprev: a copy ahead of the launches, which the
+    // synchronisation completes
+    static int32_t reduce(Solver &s, const EaWork &w, const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) {
+        if (jprev >= 0) HIPS(s, hipMemcpyAsync(vprev, v + jprev, sizeof(double), hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(k_ea_reduce1, dim3(EA_RED_WG), dim3(256), 0, w.st, w.ne, mode, v, w.pv, w.pi);
+        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, w.st, mode, (const double *)w.pv, (const int32_t *)w.pi, (double *)(w.sc + 5), w.si);
+        HIPS(s, hipMemcpyAsync(val, w.sc + 5, sizeof(double), hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+        HIPS(s, hipMemcpyAsync(idx, w.si, sizeof(int32_t), hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+        HIPS(s, hipStreamSynchronize(w.st), ERROR_HIP_SYNCHRONIZE);
+        return SUCCESSFUL_EXIT;
+    }
+};
+struct EaComplex {
+    static int32_t elements(int32_t n) { return n / 2; }
+    static bool own_transpose(const Solver &) { return false; } // (the transposed pass pair of the 2 nc system applies A^{-H})
+    static void rows(const Solver &s, const EaWork &w, const double *X, const double *B, double *R, double *AX, double *AR) {
+        hipLaunchKernelGGL(k_zea_rows, w.g, dim3(256), 0, w.st, w.ne, s.d_rp, s.d_ci, s.d_vals, X, B, R, AX, AR, w.sc);
+    }
+    static void split(const EaWork &w, double tau_scale, double NX, const double *R, const double *AX, const double *AR, const double *B, double *W1, double *W2) {
+        hipLaunchKernelGGL(k_zea_split, w.g, dim3(256), 0, w.st, w.ne, tau_scale, NX, R, AX, AR, B, W1, W2, w.sc, w.si);
+    }
+    static void hadamard(const EaWork &w, const double *d, const double *v, double *y) { hipLaunchKernelGGL(k_zea_hadamard, w.g, dim3(256), 0, w.st, w.ne, d, v, y); }
+    static void fill(const EaWork &w, int32_t mode, int32_t j, double *v) { hipLaunchKernelGGL(k_zea_fill, w.g, dim3(256), 0, w.st, w.ne, mode, j, v); }
+    // xi = y / |y|.  zlacn2 has no repeated-sign test: no flag, and nothing is launched once the estimate has stopped growing
+    static int32_t sign(Solver &, const EaWork &w, const double *y, double *xi, bool first, bool grew, bool *go_on) {
+        *go_on = first || grew;
+        if (*go_on) hipLaunchKernelGGL(k_zea_sign, w.g, dim3(256), 0, w.st, w.ne, y, xi);
+        return SUCCESSFUL_EXIT;
+    }
+    // the same over the moduli; |v_jprev| by a launch of its own behind the reduction (the same arithmetic), read with the result
+    static int32_t reduce(Solver &s, const EaWork &w, const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) {
+        hipLaunchKernelGGL(k_zea_reduce1, dim3(EA_RED_WG), dim3(256), 0, w.st, w.ne, mode, v, w.pv, w.pi);
+        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, w.st, mode, (const double *)w.pv, (const int32_t *)w.pi, (double *)(w.sc + 5), w.si);
+        if (jprev >= 0) hipLaunchKernelGGL(k_zea_abs_at, dim3(1), dim3(64), 0, w.st, v, jprev, (double *)(w.sc + 6));
+        double t[2] = {0.0, 0.0};
+        HIPS(s, hipMemcpyAsync(t, w.sc + 5, sizeof(double) * 2, hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+        HIPS(s, hipMemcpyAsync(idx, w.si, sizeof(int32_t), hipMemcpyDeviceToHost, w.st), ERROR_HIP_MEMCPY);
+        HIPS(s, hipStreamSynchronize(w.st), ERROR_HIP_SYNCHRONIZE);
+        *val = t[0];
+        if (jprev >= 0) *vprev = t[1];
+        return SUCCESSFUL_EXIT;
+    }
+};
+
 } // namespace
 
 // ---- solve with new matrix values on the kept factor (solver_hipmf_solve_updated, complex_solver_hipmf_solve_updated) ----
@@ -4097,32 +4246,30 @@ int32_t Solver::tr_prepare() {
     return SUCCESSFUL_EXIT;
 }
 
-// both passes of A^T on the permuted, scaled vector xp (in place), one launch per level and front class
+// both passes of A^T on the permuted, scaled xp (in place), one launch per level and front class.  P: TrSingle (one vector) or
+// TrBlocked (n x TR_KB at stride n)
+template <class P>
 int32_t Solver::run_transposed(double *xp) {
     const size_t nl = tr_levels.size();
+    const int64_t xs = S.n;
+    double *work = P::work(*this);
     for (size_t l = 0; l < nl; l++) {
         const TrLevel &T = tr_levels[l];
-        if (T.small_cnt > 0) {
-            const int32_t ldu = T.small_pmax | 1;
-            hipLaunchKernelGGL(k_tr_fwd_small, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_fmax * (size_t)ldu, STREAM,
-                               d_tr_list + T.small_off, d_fd, d_pool, d_child, d_rel, d_work_t, xp, ldu);
-        }
-        if (T.asm_cnt > 0)
-            hipLaunchKernelGGL(k_tr_assemble, dim3(T.asm_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.asm_off, d_fd, d_child, d_rel, d_work_t, (const double *)xp);
-        if (T.gf_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gemv<true>, dim3(T.gf_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gf_off, d_fd, d_pool, d_work_t, xp);
+        const int32_t ldu = T.small_pmax | 1;
+        if (T.small_cnt > 0)
+            P::launch_ld(P::fwd_small, dim3(T.small_cnt), sizeof(double) * (size_t)T.small_fmax * (size_t)ldu, STREAM, xs, ldu, d_tr_list + T.small_off, d_fd, d_pool,
+                         d_child, d_rel, work, xp);
+        if (T.asm_cnt > 0) P::launch(P::assemble, dim3(T.asm_cnt), STREAM, xs, d_tr_tasks + T.asm_off, d_fd, d_child, d_rel, work, (const double *)xp);
+        if (T.gf_cnt > 0) P::launch(P::fwd, dim3(T.gf_cnt), STREAM, xs, d_tr_tasks + T.gf_off, d_fd, d_pool, work, xp);
     }
     for (size_t l = nl; l-- > 0;) {
         const TrLevel &T = tr_levels[l];
-        if (T.ga_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gather, dim3(T.ga_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.ga_off, d_fd, d_rows, d_work_t, (const double *)xp);
-        if (T.gb_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gemv<false>, dim3(T.gb_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gb_off, d_fd, d_pool, d_work_t, xp);
-        if (T.small_cnt > 0) {
-            const int32_t ldl = T.small_fmax | 1;
-            hipLaunchKernelGGL(k_tr_bwd_small, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_pmax * (size_t)ldl, STREAM,
-                               d_tr_list + T.small_off, d_fd, d_pool, d_rows, d_lperm, xp, ldl);
-        }
+        const int32_t ldl = T.small_fmax | 1;
+        if (T.ga_cnt > 0) P::launch(P::gather, dim3(T.ga_cnt), STREAM, xs, d_tr_tasks + T.ga_off, d_fd, d_rows, work, (const double *)xp);
+        if (T.gb_cnt > 0) P::launch(P::bwd, dim3(T.gb_cnt), STREAM, xs, d_tr_tasks + T.gb_off, d_fd, d_pool, work, xp);
+        if (T.small_cnt > 0)
+            P::launch_ld(P::bwd_small, dim3(T.small_cnt), sizeof(double) * (size_t)T.small_pmax * (size_t)ldl, STREAM, xs, ldl, d_tr_list + T.small_off, d_fd, d_pool,
+                         d_rows, d_lperm, xp);
     }
     return SUCCESSFUL_EXIT;
 }
@@ -4134,7 +4281,7 @@ int32_t Solver::tr_pass(double *y, const double *v) {
     const dim3 g((n + 255) / 256), b(256);
     double *xp = d_tvec + 2 * (size_t)n;
     hipLaunchKernelGGL(k_tr_perm_in, g, b, 0, STREAM, n, d_perm, d_cs, v, xp);
-    int32_t code = run_transposed(xp);
+    int32_t code = run_transposed<TrSingle>(xp);
     if (code != SUCCESSFUL_EXIT) return code;
     hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, xp, y, 0);
     return SUCCESSFUL_EXIT;
@@ -4147,41 +4294,55 @@ int32_t Solver::tr_spmv(double *y, const double *x) {
     return SUCCESSFUL_EXIT;
 }
 
-// One transposed solve of device vectors with the refinement rule of solve(): omega = max_i |r_i| / (|A^T||x| + |b|)_i; stop at omega <= eps,
-// after nstep steps or when a step fails to halve omega; a step that makes omega worse is taken back; a column within 64 eps is done
-// after its correction.
-int32_t Solver::tr_core(double *x, const double *bvec, int32_t nstep, double *omega, int32_t *steps) {
-    const int32_t n = S.n;
-    const dim3 g((n + 255) / 256), b(256);
+// The refinement rule of solve() for nk <= TR_KB transposed columns that one unrefined pass pair has solved, omega = max_i |r_i| /
+// (|A^T||x| + |b|)_i per column: stop at omega <= eps, after nstep steps or when a step fails to halve omega; a step that makes omega
+// worse is taken back; a column within 64 eps is done after its correction.  One residual launch and one host look at the omegas per
+// step; columns that are done leave through the mask (they ride through the correcting passes as zeros and the exit kernel leaves them
+// alone).  P issues the launches: TrColumn (nk = 1, the single kernels) or TrColumns (a block).
+template <class P>
+int32_t Solver::tr_refine(const P &p, int32_t nk, int32_t nstep, double *omega, int32_t *steps) {
     const double EPS = 2.220446049250313e-16;
-    double *r = d_tvec + 3 * (size_t)n, *xp = d_tvec + 2 * (size_t)n; // (xp: after a correction step, the permuted correction)
-    *steps = 0;
-    *omega = INFINITY;
-    int32_t code = tr_pass(x, bvec);
-    if (code != SUCCESSFUL_EXIT || nstep <= 0) return code;
-    double prev = INFINITY;
-    for (int32_t it = 0;; it++) {
-        HIPC(hipMemsetAsync(d_tnrm, 0, sizeof(unsigned long long) * 2, STREAM), ERROR_HIP_MEMCPY);
-        hipLaunchKernelGGL(k_tr_spmv, g, b, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, (const double *)x, bvec, r, d_tnrm);
-        HIPC(hipMemcpyAsync(h_tnrm, d_tnrm, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    double prev[TR_KB];
+    for (int c = 0; c < nk; c++) omega[c] = prev[c] = INFINITY, steps[c] = 0;
+    uint64_t active = nstep > 0 ? (1ull << nk) - 1ull : 0;
+    for (int32_t it = 0; active; it++) {
+        HIPC(hipMemsetAsync(p.d_nrm(), 0, sizeof(unsigned long long) * P::words, STREAM), ERROR_HIP_MEMCPY);
+        p.residual(STREAM, active);
+        HIPC(hipMemcpyAsync(p.h_nrm(), p.d_nrm(), sizeof(double) * P::words, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
         HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-        const double om = h_tnrm[1];
-        if (it > 0 && !(om < prev)) {
-            hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, (const double *)xp, x, 2); // take the last correction back
-            *omega = prev;
-            break;
+        uint64_t back = 0, corr = 0;
+        for (int c = 0; c < nk; c++) {
+            if (!((active >> c) & 1ull)) continue;
+            const double om = p.h_nrm()[2 * c + 1];
+            if (it > 0 && !(om < prev[c])) {
+                back |= 1ull << c, omega[c] = prev[c]; // take the last correction back
+                continue;
+            }
+            omega[c] = om;
+            if (om <= EPS || it == nstep || (it > 0 && om > 0.5 * prev[c])) continue;
+            prev[c] = om, corr |= 1ull << c;
         }
-        *omega = om;
-        if (om <= EPS || it == nstep || (it > 0 && om > 0.5 * prev)) break;
-        prev = om;
-        hipLaunchKernelGGL(k_tr_perm_in, g, b, 0, STREAM, n, d_perm, d_cs, (const double *)r, xp);
-        code = run_transposed(xp);
+        if (back) p.perm_out(STREAM, 2, back);
+        if (!corr) break;
+        p.perm_in(STREAM, corr);
+        const int32_t code = run_transposed<typename P::Pass>(p.xp);
         if (code != SUCCESSFUL_EXIT) return code;
-        hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, (const double *)xp, x, 1);
-        (*steps)++;
-        if (prev <= 64.0 * EPS || it + 1 > nstep) break;
+        p.perm_out(STREAM, 1, corr);
+        active = 0;
+        for (int c = 0; c < nk; c++)
+            if ((corr >> c) & 1ull) {
+                steps[c]++;
+                if (!(prev[c] <= 64.0 * EPS || it + 1 > nstep)) active |= 1ull << c;
+            }
     }
     return SUCCESSFUL_EXIT;
+}
+
+// one transposed solve of device vectors (not d_tvec slots 2 and 3): the pass pair, then the rule
+int32_t Solver::tr_core(double *x, const double *bvec, int32_t nstep, double *omega, int32_t *steps) {
+    *omega = INFINITY, *steps = 0;
+    const int32_t code = tr_pass(x, bvec);
+    return code != SUCCESSFUL_EXIT ? code : tr_refine(TrColumn{*this, x, bvec}, 1, nstep, omega, steps);
 }
 
 // FGMRES on one transposed column (device vectors tx, tb: not d_tvec slots 2 .. 5) with A^T as the operator and the transposed pass pair as the
@@ -4273,42 +4434,9 @@ int32_t Solver::tr_prepare_blocked() {
     return SUCCESSFUL_EXIT;
 }
 
-// both passes of A^T on the permuted, scaled block XP (n x TR_KB at stride n, in place), one launch per level and front class
-int32_t Solver::run_transposed_blocked(double *XP) {
-    const size_t nl = tr_levels.size();
-    const int64_t xs = S.n;
-    for (size_t l = 0; l < nl; l++) {
-        const TrLevel &T = tr_levels[l];
-        if (T.small_cnt > 0) {
-            const int32_t ldu = T.small_pmax | 1;
-            hipLaunchKernelGGL(k_tr_fwd_small_blk, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_fmax * (size_t)ldu, STREAM,
-                               d_tr_list + T.small_off, d_fd, d_pool, d_child, d_rel, d_work_tb, XP, xs, ldu);
-        }
-        if (T.asm_cnt > 0)
-            hipLaunchKernelGGL(k_tr_assemble_blk, dim3(T.asm_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.asm_off, d_fd, d_child, d_rel, d_work_tb, (const double *)XP, xs);
-        if (T.gf_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gemm_blk<true>, dim3(T.gf_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gf_off, d_fd, d_pool, d_work_tb, XP, xs);
-    }
-    for (size_t l = nl; l-- > 0;) {
-        const TrLevel &T = tr_levels[l];
-        if (T.ga_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gather_blk, dim3(T.ga_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.ga_off, d_fd, d_rows, d_work_tb, (const double *)XP, xs);
-        if (T.gb_cnt > 0)
-            hipLaunchKernelGGL(k_tr_gemm_blk<false>, dim3(T.gb_cnt), dim3(256), 0, STREAM, d_tr_tasks + T.gb_off, d_fd, d_pool, d_work_tb, XP, xs);
-        if (T.small_cnt > 0) {
-            const int32_t ldl = T.small_fmax | 1;
-            hipLaunchKernelGGL(k_tr_bwd_small_blk, dim3(T.small_cnt), dim3(64), sizeof(double) * (size_t)T.small_pmax * (size_t)ldl, STREAM,
-                               d_tr_list + T.small_off, d_fd, d_pool, d_rows, d_lperm, XP, xs, ldl);
-        }
-    }
-    return SUCCESSFUL_EXIT;
-}
-
 // nrhs columns of A^T X = B, TR_KB at a time.  Per block: entry (column permutation and scaling), the two passes, exit (row ones), then
-// tr_core's refinement rule column by column with ONE residual launch and one host look at the block's omegas per step -- columns that are
-// done leave through the mask (they ride through the correcting passes as zeros and the exit kernel leaves them alone) --, then the
-// transposed FGMRES rescue of solve_transpose for the columns that need it.  One column, A^T = A, HIPMF_TRANSPOSE_BLOCKED=0 or no memory
-// for the block buffers: solve_transpose (transposed_blocks stays 0).
+// the refinement rule for the block's columns (tr_refine), then the transposed FGMRES rescue of solve_transpose for the columns that need
+// it.  One column, A^T = A, HIPMF_TRANSPOSE_BLOCKED=0 or no memory for the block buffers: solve_transpose (transposed_blocks stays 0).
 int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device) {
     transposed_blocks = 0;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
@@ -4324,9 +4452,8 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
     }
     const int32_t n = S.n, nstep = opt.refinement_nstep;
     const size_t nb = sizeof(double) * (size_t)n, nz = (size_t)n;
-    const double EPS = 2.220446049250313e-16;
-    const dim3 g((n + 255) / 256), gp((n + 255) / 256, TR_KB / PERM_CW), b(256);
-    double *TB = d_tblk, *TX = TB + nz * TR_KB, *XP = TX + nz * TR_KB, *R = XP + nz * TR_KB;
+    const dim3 gp((n + 255) / 256, TR_KB / PERM_CW), b(256);
+    double *TB = d_tblk, *TX = TB + nz * TR_KB, *XP = TX + nz * TR_KB; // (then the residuals: TrColumns)
     const uintptr_t xa = (uintptr_t)x, ra = (uintptr_t)rhs, span = sizeof(double) * (size_t)nrhs * (size_t)ldx;
     const bool aliased = on_device && xa < ra + span && ra < xa + span; // (x written while rhs is still read: the block's columns are staged)
     krylov_iterations_t = 0;
@@ -4344,44 +4471,13 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
         }
         if (!on_device) X = TX, xs = n;
         hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, B, bs, XP, (int64_t)n, all, nk);
-        int32_t code = run_transposed_blocked(XP);
+        int32_t code = run_transposed<TrBlocked>(XP);
         if (code != SUCCESSFUL_EXIT) return code;
         hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 0, all, nk);
-        double omega[TR_KB], prev[TR_KB];
+        double omega[TR_KB];
         int32_t steps[TR_KB];
-        for (int c = 0; c < TR_KB; c++) omega[c] = prev[c] = INFINITY, steps[c] = 0;
-        uint64_t active = nstep > 0 ? all : 0;
-        for (int32_t it = 0; active; it++) {
-            HIPC(hipMemsetAsync(d_tnrm_blk, 0, sizeof(unsigned long long) * 2 * TR_KB, STREAM), ERROR_HIP_MEMCPY);
-            hipLaunchKernelGGL(k_tr_residual_cols, g, b, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, (const double *)X, xs, B, bs, R, (int64_t)n,
-                               d_tnrm_blk, nk, active);
-            HIPC(hipMemcpyAsync(h_tnrm_blk, d_tnrm_blk, sizeof(double) * 2 * TR_KB, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-            uint64_t back = 0, corr = 0;
-            for (int c = 0; c < nk; c++) {
-                if (!((active >> c) & 1ull)) continue;
-                const double om = h_tnrm_blk[2 * c + 1];
-                if (it > 0 && !(om < prev[c])) {
-                    back |= 1ull << c, omega[c] = prev[c]; // take the last correction back
-                    continue;
-                }
-                omega[c] = om;
-                if (om <= EPS || it == nstep || (it > 0 && om > 0.5 * prev[c])) continue;
-                prev[c] = om, corr |= 1ull << c;
-            }
-            if (back) hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 2, back, nk);
-            if (!corr) break;
-            hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, (const double *)R, (int64_t)n, XP, (int64_t)n, corr, nk);
-            code = run_transposed_blocked(XP);
-            if (code != SUCCESSFUL_EXIT) return code;
-            hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, X, xs, 1, corr, nk);
-            active = 0;
-            for (int c = 0; c < nk; c++)
-                if ((corr >> c) & 1ull) {
-                    steps[c]++;
-                    if (!(prev[c] <= 64.0 * EPS || it + 1 > nstep)) active |= 1ull << c;
-                }
-        }
+        code = tr_refine(TrColumns{*this, X, xs, B, bs, nk}, nk, nstep, omega, steps);
+        if (code != SUCCESSFUL_EXIT) return code;
         if (krylov_enabled && !in_rescue && n_perturbed > 0) {
             double *tb = d_tvec, *tx = d_tvec + nz;
             for (int c = 0; c < nk; c++) {
@@ -4766,133 +4862,128 @@ int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t
 // i.e. at most 11 pass pairs per estimate.  The vector steps run on the device (only scalars come to the host), every reduction has a
 // fixed order: a repeat call gives the same bits.  (One liberty: the larger of two successive iterates' norms is kept -- both are lower
 // bounds of |C|_1 -- where dlacn2 keeps the later one.)
-int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *out, int32_t option) {
-    if (option == 0) return SUCCESSFUL_EXIT;
-    DeviceScope dev_scope(device);
-    const bool sym = S.sym_mode || d_tptr;
-    int32_t code = sym ? SUCCESSFUL_EXIT : tr_prepare();
-    if (code != SUCCESSFUL_EXIT) return code;
-    const int32_t n = S.n;
+// One core serves the real matrix and the complex twin; the policy P (EaReal, EaComplex) gives what differs.  In the COMPLEX form this
+// handle holds the real-equivalent system of order n = 2 nc, xbar and rhs are nc interleaved pairs, n above is nc and |.| the complex
+// modulus (include/russell_hipmf.h; the real analysis of the 2 nc system would sum |Re| + |Im| instead).  C = diag(w) A^{-H}: the
+// transpose of the 2 nc system IS the real-equivalent form of A^H.  The iteration is zlacn2's: the complex sign z / |z| and no repeat
+// test of the sign vector.
+template <class P>
+int32_t Solver::error_analysis_core(const double *xbar, const double *rhs, double *out, int32_t option) {
+    const int32_t n = S.n, ne = P::elements(n);
     const size_t nb = sizeof(double) * (size_t)n;
-    const dim3 g((n + 255) / 256), b(256);
-    // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t, partials, scalars
+    const bool sym = P::own_transpose(*this);
+    // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t (vectors of n doubles, ax .. w2 of ne), partials, scalars
     // (kept per handle: a hipMalloc / hipFree pair of 12 n doubles per call would cost a device-wide synchronisation every time)
     if (!d_anl) HIPC(hipMalloc((void **)d_anl.put(), nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
-    double *buf = d_anl;
-    double *X = buf, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + n, *W1 = AR + n, *W2 = W1 + n, *V = W2 + n, *Y = V + n, *Z = Y + n, *XI = Z + n, *T = XI + n;
-    double *pv = T + n, *sv = pv + EA_RED_WG;
-    unsigned long long *sc = (unsigned long long *)sv; // 8 words: maxima (bits), then the reduction result
-    int32_t *pi = (int32_t *)(sv + 8), *si = pi + EA_RED_WG;
+    double *X = d_anl, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + ne, *W1 = AR + ne, *W2 = W1 + ne, *V = W2 + ne, *Y = V + n, *Z = Y + n,
+           *XI = Z + n, *T = XI + n;
+    double *pv = d_anl + 12 * (size_t)n, *sv = pv + EA_RED_WG;
+    int32_t *pi = (int32_t *)(sv + 8);
+    const EaWork w{STREAM, ne, dim3((ne + 255) / 256), pv, pi, (unsigned long long *)sv, pi + EA_RED_WG};
     HIPC(hipMemcpyAsync(X, xbar, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemcpyAsync(B, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(sv, 0, sizeof(double) * 8 + sizeof(int32_t) * (EA_RED_WG + 8), STREAM), ERROR_HIP_MEMCPY);
-    hipLaunchKernelGGL(k_ea_rows, g, b, 0, STREAM, n, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, (const double *)X, (const double *)B, R, AX, AR, sc);
+    P::rows(*this, w, X, B, R, AX, AR);
     double h[8];
-    HIPC(hipMemcpyAsync(h, sc, sizeof(double) * 3, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(h, w.sc, sizeof(double) * 3, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
     const double NA = h[0], NX = h[1], RN = h[2];
-    const double tau_scale = 1000.0 * (double)n * 2.220446049250313e-16;
-    hipLaunchKernelGGL(k_ea_split, g, b, 0, STREAM, n, tau_scale, NX, (const double *)R, (const double *)AX, (const double *)AR, (const double *)B, W1, W2, sc, si);
+    const double tau_scale = 1000.0 * (double)ne * 2.220446049250313e-16;
+    P::split(w, tau_scale, NX, R, AX, AR, B, W1, W2);
     int32_t n2 = 0;
-    HIPC(hipMemcpyAsync(h + 3, sc + 3, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipMemcpyAsync(&n2, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(h + 3, w.sc + 3, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(&n2, w.si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     const double om1 = h[3], om2 = h[4];
     out[0] = NA, out[1] = NX, out[2] = (NA * NX > 0.0) ? RN / (NA * NX) : 0.0, out[3] = om1, out[4] = om2;
     analysis_solves = 0;
     if (option != 1) return SUCCESSFUL_EXIT;
 
-    auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx) -> int32_t {
-        hipLaunchKernelGGL(k_ea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, n, mode, v, pv, pi);
-        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, STREAM, mode, (const double *)pv, (const int32_t *)pi, (double *)(sc + 5), si);
-        double t = 0.0;
-        int32_t ti = 0;
-        HIPC(hipMemcpyAsync(&t, sc + 5, sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-        HIPC(hipMemcpyAsync(&ti, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-        *val = t;
-        if (idx) *idx = ti;
-        return SUCCESSFUL_EXIT;
-    };
+    int32_t code = SUCCESSFUL_EXIT, jx = 0;
+    auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) { return P::reduce(*this, w, v, mode, val, idx, jprev, vprev); };
     auto inv = [&](double *y, const double *v) -> int32_t { // y = A^{-1} v, one unrefined ordinary pass pair
-        opt.refinement_nstep = 0, opt.verbose = false;
-        const bool keep_rescue = in_rescue;
-        in_rescue = true; // (no Krylov rescue inside)
-        const int32_t c = solve_core(y, v, 1, n, true);
-        in_rescue = keep_rescue;
         analysis_solves++;
-        return c;
+        return solve_core(y, v, 1, n, true);
     };
     auto inv_t = [&](double *y, const double *v) -> int32_t { // y = A^{-T} v
         if (sym) return inv(y, v);
-        const int32_t c = tr_pass(y, v);
         analysis_solves++;
-        return c;
+        return tr_pass(y, v);
     };
     // C v and C^T v of C = diag(w) A^{-T}
-    auto cmul = [&](const double *w, double *y, const double *v) -> int32_t {
-        int32_t c = inv_t(T, v);
+    auto cmul = [&](const double *d, double *y, const double *v) -> int32_t {
+        const int32_t c = inv_t(T, v);
         if (c != SUCCESSFUL_EXIT) return c;
-        hipLaunchKernelGGL(k_ea_hadamard, g, b, 0, STREAM, n, w, (const double *)T, y);
+        P::hadamard(w, d, (const double *)T, y);
         return SUCCESSFUL_EXIT;
     };
-    auto ctmul = [&](const double *w, double *z, const double *v) -> int32_t {
-        hipLaunchKernelGGL(k_ea_hadamard, g, b, 0, STREAM, n, w, v, T);
+    auto ctmul = [&](const double *d, double *z, const double *v) -> int32_t {
+        P::hadamard(w, d, v, T);
         return inv(z, T);
     };
-    auto estimate = [&](const double *w, double *est) -> int32_t {
+    auto estimate = [&](const double *d, double *est) -> int32_t {
         int32_t c;
-        hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 0, 0, V);
-        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
-        if (n == 1) {
-            int32_t j0;
-            return reduce(Y, 1, est, &j0);
-        }
-        if ((c = reduce(Y, 0, est, nullptr)) != SUCCESSFUL_EXIT) return c;
-        HIPC(hipMemsetAsync(XI, 0, nb, STREAM), ERROR_HIP_MEMCPY);
-        hipLaunchKernelGGL(k_ea_sign, g, b, 0, STREAM, n, (const double *)Y, XI, (int32_t *)(si + 1));
-        if ((c = ctmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
+        bool go_on = true;
+        P::fill(w, 0, 0, V);
+        if ((c = cmul(d, Y, V)) != SUCCESSFUL_EXIT) return c;
+        if (ne == 1) return reduce(Y, 1, est, &jx, -1, nullptr);
+        if ((c = reduce(Y, 0, est, &jx, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+        if ((c = P::sign(*this, w, Y, XI, true, true, &go_on)) != SUCCESSFUL_EXIT) return c;
+        if ((c = ctmul(d, Z, XI)) != SUCCESSFUL_EXIT) return c;
         double zmax = 0.0;
         int32_t j = 0;
-        if ((c = reduce(Z, 1, &zmax, &j)) != SUCCESSFUL_EXIT) return c;
+        if ((c = reduce(Z, 1, &zmax, &j, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
         for (int32_t iter = 2;; iter++) {
-            hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 2, j, V);
-            if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+            P::fill(w, 2, j, V);
+            if ((c = cmul(d, Y, V)) != SUCCESSFUL_EXIT) return c;
             const double estold = *est;
             double e = 0.0;
-            if ((c = reduce(Y, 0, &e, nullptr)) != SUCCESSFUL_EXIT) return c;
+            if ((c = reduce(Y, 0, &e, &jx, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
             *est = std::max(e, estold);
-            int32_t changed = 0;
-            HIPC(hipMemsetAsync(si + 1, 0, sizeof(int32_t), STREAM), ERROR_HIP_MEMCPY);
-            hipLaunchKernelGGL(k_ea_sign, g, b, 0, STREAM, n, (const double *)Y, XI, (int32_t *)(si + 1));
-            HIPC(hipMemcpyAsync(&changed, si + 1, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-            if (!changed || e <= estold) break; // repeated sign vector, or no growth
-            if ((c = ctmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
-            const int32_t jlast = j;
+            if ((c = P::sign(*this, w, Y, XI, false, !(e <= estold), &go_on)) != SUCCESSFUL_EXIT) return c;
+            if (!go_on) break;
+            if ((c = ctmul(d, Z, XI)) != SUCCESSFUL_EXIT) return c;
             double zjlast = 0.0;
-            HIPC(hipMemcpyAsync(&zjlast, Z + jlast, sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-            if ((c = reduce(Z, 1, &zmax, &j)) != SUCCESSFUL_EXIT) return c;
+            if ((c = reduce(Z, 1, &zmax, &j, j, &zjlast)) != SUCCESSFUL_EXIT) return c;
             if (!(zjlast != zmax && iter < 5)) break;
         }
-        hipLaunchKernelGGL(k_ea_fill, g, b, 0, STREAM, n, 1, 0, V);
-        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
+        P::fill(w, 1, 0, V);
+        if ((c = cmul(d, Y, V)) != SUCCESSFUL_EXIT) return c;
         double e = 0.0;
-        if ((c = reduce(Y, 0, &e, nullptr)) != SUCCESSFUL_EXIT) return c;
-        const double temp = 2.0 * (e / (3.0 * (double)n));
+        if ((c = reduce(Y, 0, &e, &jx, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
+        const double temp = 2.0 * (e / (3.0 * (double)ne));
         if (temp > *est) *est = temp;
         return SUCCESSFUL_EXIT;
     };
     double e1 = 0.0, e2 = 0.0;
     {
         const NestedSolveGuard guard(*this); // the statistics of the caller's solve stay as that solve left them
-        if (n - n2 > 0) code = estimate(W1, &e1);
+        guard.unrefined_quiet();
+        if (ne - n2 > 0) code = estimate(W1, &e1);
         if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
     }
     if (code != SUCCESSFUL_EXIT) return code;
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
     out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
     return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::error_analysis(const double *xbar, const double *rhs, double *out, int32_t option) {
+    if (option == 0) return SUCCESSFUL_EXIT;
+    DeviceScope dev_scope(device);
+    const int32_t code = EaReal::own_transpose(*this) ? SUCCESSFUL_EXIT : tr_prepare(); // (A^T = A needs no transposed plan)
+    return code != SUCCESSFUL_EXIT ? code : error_analysis_core<EaReal>(xbar, rhs, out, option);
+}
+
+// the complex twin (complex_solver_hipmf_solve_with_error_analysis)
+int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, double *out, int32_t option) {
+    if (option == 0) return SUCCESSFUL_EXIT;
+    if (S.sym_mode || d_tptr || (S.n & 1)) return ERROR_HIPMF_INVALID_VALUE; // (not a real-equivalent handle)
+    DeviceScope dev_scope(device);
+    const int32_t code = tr_prepare();
+    return code != SUCCESSFUL_EXIT ? code : error_analysis_core<EaComplex>(xbar, rhs, out, option);
 }
 
 int32_t Solver::download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> &ci) {
@@ -4901,140 +4992,6 @@ int32_t Solver::download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> 
     rp.resize((size_t)S.n + 1), ci.resize((size_t)S.nnz_a);
     HIPC(hipMemcpy(rp.data(), d_rp, sizeof(int32_t) * ((size_t)S.n + 1), hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
     if (S.nnz_a > 0) HIPC(hipMemcpy(ci.data(), d_ci, sizeof(int32_t) * (size_t)S.nnz_a, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
-    return SUCCESSFUL_EXIT;
-}
-
-// ---- error analysis of the complex twin (complex_solver_hipmf_solve_with_error_analysis) ----
-// This handle holds the real-equivalent system of order n = 2 nc; xbar and rhs are interleaved complex vectors.  The definitions are the
-// real ones with |.| the complex modulus (include/russell_hipmf.h); the real analysis of the 2n system would sum |Re| + |Im| instead.
-// | |A^{-1}| w |_inf = |C|_1 with C = diag(w) A^{-H}: C v = w o (A^{-H} v) is one transposed pass pair of the 2n system (its transpose
-// IS the real-equivalent form of A^H), C^H v = A^{-1} (w o v) one ordinary pass pair, both unrefined.  The iteration is LAPACK zlacn2's:
-// the complex sign z / |z|, no repeat test of the sign vector, at most 5 iterations + the real alternating vector, i.e. at most 11 pass
-// pairs per estimate; the one liberty of the real path is kept (the larger of two successive iterates).  Vector steps on the device,
-// fixed-order reductions, only scalars come to the host.
-int32_t Solver::error_analysis_complex(const double *xbar, const double *rhs, double *out, int32_t option) {
-    if (option == 0) return SUCCESSFUL_EXIT;
-    if (S.sym_mode || d_tptr || (S.n & 1)) return ERROR_HIPMF_INVALID_VALUE; // (not a real-equivalent handle)
-    DeviceScope dev_scope(device);
-    int32_t code = tr_prepare();
-    if (code != SUCCESSFUL_EXIT) return code;
-    const int32_t n = S.n, nc = n / 2;
-    const size_t nb = sizeof(double) * (size_t)n;
-    const dim3 g((nc + 255) / 256), b(256);
-    // x | b | r | ax | arow | w1 | w2 | v | y | z | xi | t (complex vectors n doubles, ax .. w2 nc doubles), partials, scalars:
-    // the buffer of the real analysis (12 n doubles + the reduction words), allocated the same way
-    if (!d_anl) HIPC(hipMalloc((void **)d_anl.put(), nb * 12 + sizeof(double) * (EA_RED_WG + 8) + sizeof(int32_t) * (EA_RED_WG + 8)), ERROR_HIP_MALLOC);
-    double *X = d_anl, *B = X + n, *R = B + n, *AX = R + n, *AR = AX + nc, *W1 = AR + nc, *W2 = W1 + nc, *V = W2 + nc, *Y = V + n, *Z = Y + n,
-           *XI = Z + n, *T = XI + n;
-    double *pv = d_anl + 12 * (size_t)n, *sv = pv + EA_RED_WG;
-    unsigned long long *sc = (unsigned long long *)sv; // 8 words: maxima (bits), then the reduction results
-    int32_t *pi = (int32_t *)(sv + 8), *si = pi + EA_RED_WG;
-    HIPC(hipMemcpyAsync(X, xbar, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipMemcpyAsync(B, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipMemsetAsync(sv, 0, sizeof(double) * 8 + sizeof(int32_t) * (EA_RED_WG + 8), STREAM), ERROR_HIP_MEMCPY);
-    hipLaunchKernelGGL(k_zea_rows, g, b, 0, STREAM, nc, d_rp, d_ci, d_vals, (const double *)X, (const double *)B, R, AX, AR, sc);
-    double h[8];
-    HIPC(hipMemcpyAsync(h, sc, sizeof(double) * 3, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-    const double NA = h[0], NX = h[1], RN = h[2];
-    const double tau_scale = 1000.0 * (double)nc * 2.220446049250313e-16;
-    hipLaunchKernelGGL(k_zea_split, g, b, 0, STREAM, nc, tau_scale, NX, (const double *)R, (const double *)AX, (const double *)AR, (const double *)B, W1, W2, sc, si);
-    int32_t n2 = 0;
-    HIPC(hipMemcpyAsync(h + 3, sc + 3, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipMemcpyAsync(&n2, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
-    const double om1 = h[3], om2 = h[4];
-    out[0] = NA, out[1] = NX, out[2] = (NA * NX > 0.0) ? RN / (NA * NX) : 0.0, out[3] = om1, out[4] = om2;
-    analysis_solves = 0;
-    if (option != 1) return SUCCESSFUL_EXIT;
-
-    // sum |v_i| (mode 0) or max |v_i| and its first index (mode 1) over the moduli; with jprev >= 0 also |v_jprev| (same arithmetic)
-    auto reduce = [&](const double *v, int32_t mode, double *val, int32_t *idx, int32_t jprev, double *vprev) -> int32_t {
-        hipLaunchKernelGGL(k_zea_reduce1, dim3(EA_RED_WG), dim3(256), 0, STREAM, nc, mode, v, pv, pi);
-        hipLaunchKernelGGL(k_ea_reduce2, dim3(1), dim3(EA_RED_WG), 0, STREAM, mode, (const double *)pv, (const int32_t *)pi, (double *)(sc + 5), si);
-        if (jprev >= 0) hipLaunchKernelGGL(k_zea_abs_at, dim3(1), dim3(64), 0, STREAM, v, jprev, (double *)(sc + 6));
-        double t[2] = {0.0, 0.0};
-        int32_t ti = 0;
-        HIPC(hipMemcpyAsync(t, sc + 5, sizeof(double) * 2, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-        HIPC(hipMemcpyAsync(&ti, si, sizeof(int32_t), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
-        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
-        *val = t[0];
-        if (idx) *idx = ti;
-        if (vprev) *vprev = t[1];
-        return SUCCESSFUL_EXIT;
-    };
-    auto inv = [&](double *y, const double *v) -> int32_t { // y = A^{-1} v, one unrefined ordinary pass pair
-        opt.refinement_nstep = 0, opt.verbose = false;
-        const bool keep_rescue = in_rescue;
-        in_rescue = true; // (no Krylov rescue inside)
-        const int32_t c = solve_core(y, v, 1, n, true);
-        in_rescue = keep_rescue;
-        analysis_solves++;
-        return c;
-    };
-    auto inv_h = [&](double *y, const double *v) -> int32_t { // y = A^{-H} v: the transposed pass pair of the 2n system
-        const int32_t c = tr_pass(y, v);
-        analysis_solves++;
-        return c;
-    };
-    // C v and C^H v of C = diag(w) A^{-H}
-    auto cmul = [&](const double *w, double *y, const double *v) -> int32_t {
-        int32_t c = inv_h(T, v);
-        if (c != SUCCESSFUL_EXIT) return c;
-        hipLaunchKernelGGL(k_zea_hadamard, g, b, 0, STREAM, nc, w, (const double *)T, y);
-        return SUCCESSFUL_EXIT;
-    };
-    auto chmul = [&](const double *w, double *z, const double *v) -> int32_t {
-        hipLaunchKernelGGL(k_zea_hadamard, g, b, 0, STREAM, nc, w, v, T);
-        return inv(z, T);
-    };
-    auto estimate = [&](const double *w, double *est) -> int32_t {
-        int32_t c;
-        hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 0, 0, V);
-        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
-        if (nc == 1) {
-            int32_t j0;
-            return reduce(Y, 1, est, &j0, -1, nullptr);
-        }
-        if ((c = reduce(Y, 0, est, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
-        hipLaunchKernelGGL(k_zea_sign, g, b, 0, STREAM, nc, (const double *)Y, XI);
-        if ((c = chmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
-        double zmax = 0.0;
-        int32_t j = 0;
-        if ((c = reduce(Z, 1, &zmax, &j, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
-        for (int32_t iter = 2;; iter++) {
-            hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 2, j, V);
-            if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
-            const double estold = *est;
-            double e = 0.0;
-            if ((c = reduce(Y, 0, &e, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
-            *est = std::max(e, estold);
-            if (e <= estold) break; // no growth (zlacn2 has no repeated-sign test)
-            hipLaunchKernelGGL(k_zea_sign, g, b, 0, STREAM, nc, (const double *)Y, XI);
-            if ((c = chmul(w, Z, XI)) != SUCCESSFUL_EXIT) return c;
-            double zjlast = 0.0;
-            if ((c = reduce(Z, 1, &zmax, &j, j, &zjlast)) != SUCCESSFUL_EXIT) return c;
-            if (!(zjlast != zmax && iter < 5)) break;
-        }
-        hipLaunchKernelGGL(k_zea_fill, g, b, 0, STREAM, nc, 1, 0, V);
-        if ((c = cmul(w, Y, V)) != SUCCESSFUL_EXIT) return c;
-        double e = 0.0;
-        if ((c = reduce(Y, 0, &e, nullptr, -1, nullptr)) != SUCCESSFUL_EXIT) return c;
-        const double temp = 2.0 * (e / (3.0 * (double)nc));
-        if (temp > *est) *est = temp;
-        return SUCCESSFUL_EXIT;
-    };
-    double e1 = 0.0, e2 = 0.0;
-    {
-        const NestedSolveGuard guard(*this); // the statistics of the caller's solve stay as that solve left them
-        if (nc - n2 > 0) code = estimate(W1, &e1);
-        if (code == SUCCESSFUL_EXIT && n2 > 0) code = estimate(W2, &e2);
-    }
-    if (code != SUCCESSFUL_EXIT) return code;
-    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
-    const double c1 = NX > 0.0 ? e1 / NX : 0.0, c2 = NX > 0.0 ? e2 / NX : 0.0;
-    out[5] = om1 * c1 + om2 * c2, out[6] = c1, out[7] = c2;
     return SUCCESSFUL_EXIT;
 }
 

@@ -554,6 +554,9 @@ class Solver : public SolverDevice {
     // the flexible GMRES of solve_updated and solve_updated_complex; P: the arithmetic (UpdatedReal, UpdatedComplex in numeric.cpp)
     template <class P>
     int32_t solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, bool on_device);
+    // the error analysis of both forms; P: what differs (EaReal, EaComplex in numeric.cpp)
+    template <class P>
+    int32_t error_analysis_core(const double *xbar, const double *rhs, double *out, int32_t option);
     int64_t n_lists = 0;            // entries of d_lists
     static constexpr int32_t MAX_SOLVE_LANES = 4;
     int32_t solve_lanes = 1;   // HIPMF_SOLVE_LANES (1..4).  One since late round 4: two launches full of workgroups that wait for each other's
@@ -574,13 +577,16 @@ class Solver : public SolverDevice {
     bool ea_lu_active() const { return ea_lds_active() && use_ea_lu && !use_binv; }
     int32_t spmv_blocks = 0;
     int32_t tr_prepare();
-    int32_t run_transposed(double *xp);
-    int32_t tr_core(double *x, const double *b, int32_t nstep, double *omega, int32_t *steps);
+    template <class P>
+    int32_t run_transposed(double *xp); // both passes of A^T; P: one vector or a block of 16 (TrSingle, TrBlocked in numeric.cpp)
+    // the refinement rule of solve() on nk transposed columns; P issues the launches (TrColumn, TrColumns in numeric.cpp)
+    template <class P>
+    int32_t tr_refine(const P &p, int32_t nk, int32_t nstep, double *omega, int32_t *steps);
+    int32_t tr_core(double *x, const double *b, int32_t nstep, double *omega, int32_t *steps); // one column: tr_pass, then the rule
     int32_t tr_pass(double *y, const double *v); // y = A^{-T} v on the device, one unrefined pass pair
     int32_t tr_spmv(double *y, const double *x); // y = A^T x on the device
     int32_t tr_rescue(double *tx, const double *tb, bool first_column); // FGMRES on one transposed column (the preconditioner: tr_pass)
     int32_t tr_prepare_blocked();
-    int32_t run_transposed_blocked(double *XP);
     int32_t sp_prepare();
     // per-level lists of the fronts in `fronts` (any order) into `buf`, levels ascending: forward shapes (assembly + products over f rows)
     // or backward shapes (gather + products over p rows)
