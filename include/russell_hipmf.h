@@ -444,6 +444,14 @@ int32_t complex_solver_hipmf_factorize(struct InterfaceComplexHIPMF *solver, int
 int32_t complex_solver_hipmf_get_determinant(struct InterfaceComplexHIPMF *solver, double *determinant_coefficient_real,
                                              double *determinant_coefficient_imag, double *determinant_exponent);
 int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, C_BOOL verbose);
+/* nrhs right-hand sides per call, 16 columns per pass pair over the real-equivalent factor: solver_hipmf_solve_many / solver_hipmf_solve_device
+ * for the complex handle.  x, rhs: column-major ld x nrhs COMPLEX arrays, interleaved (re, im); ld counts complex elements, ld >= n, columns
+ * are 2 ld doubles apart; entries n .. ld - 1 of every column of x are not written; rhs is not changed.  Blocks of 16 columns, refinement and
+ * the Krylov rescue after replaced pivots as the handle is set up.  nrhs == 1 is complex_solver_hipmf_solve, bit for bit.  _device: device
+ * pointers, 16-byte aligned.  HIPMF_COUNTER_BLOCK_GROUPS as for the real handle.
+ * ERROR_NULL_POINTER, ERROR_NEED_FACTORIZATION in this order, then ERROR_HIPMF_INVALID_VALUE (nrhs < 1, ld < n). */
+int32_t complex_solver_hipmf_solve_many(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 /* conjugate: 1 -> A^H x = b, 0 -> A^T x = b (the real transposed solve of the real-equivalent system; umfpack_zi_solve's UMFPACK_Aat / UMFPACK_At) */
 int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose);
 /* Solves exactly as complex_solver_hipmf_solve (the same x, bit for bit), then the error analysis of solver_hipmf_solve_with_error_analysis
@@ -486,7 +494,7 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *solver, i
  * _ARNOLDI_US as for the real form; HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC is 1 after a call.
  * Every complex handle kind is served: general, complex-symmetric lower, matched / scaled, HIPMF_COMPLEX_PAIRS=0 and factors with replaced
  * pivots (flexible GMRES only needs M^{-1} v to be some vector: a factor that is not exactly complex-linear is a weaker preconditioner).
- * No form for several right-hand sides.
+ * Several right-hand sides per call: complex_solver_hipmf_solve_updated_many below.
  * WHEN IT PAYS (tools/solve_updated.py --complex, one MI355X, one run, profiles/r12_solve_updated_complex.txt): on the 500 x 500 complex
  * shifted grid a step costs 0.46 - 0.47 ms (pass pair 0.37, SpMV 0.03, Arnoldi kernels 0.04 - 0.05) and complex_solver_hipmf_factorize_mapped
  * + complex_solver_hipmf_solve on the same new values 8.1 ms: break-even at 17 steps.  h -> h/2 takes 11 steps and 5.2 ms per call,
@@ -497,6 +505,34 @@ int32_t complex_solver_hipmf_solve_updated(struct InterfaceComplexHIPMF *solver,
                                            double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
 int32_t complex_solver_hipmf_solve_updated_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values,
                                                   int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
+/* The same for nrhs right-hand sides: solver_hipmf_solve_updated_many for the complex handle, in COMPLEX arithmetic.  x, rhs: column-major
+ * ld x nrhs complex arrays, interleaved, ld in complex elements, ld >= n (entries n .. ld - 1 of a column of x are not written); steps,
+ * relres: nrhs entries on the host, or NULL.  Per column the contract is that of complex_solver_hipmf_solve_updated: rel_tol, max_steps,
+ * HIPMF_UPDATED_RESTART and the halved restart length; relres[c] the recomputed true residual over |b_c|_2; steps[c] the pass pairs in which
+ * column c was still iterating; a zero right-hand side gives a zero column, 0 steps, relres 0; a non-finite one a zero column and relres NaN;
+ * bit-reproducible; no side effects on the factor, refinement's values, the determinant, the statistics or the bits of later solves;
+ * `mapped` has to name the map in force.  Status 0 when every column converged, else HIPMF_WARNING_NOT_CONVERGED.
+ * Method: that of solver_hipmf_solve_updated_many -- blocks of 16 columns, every column its own Krylov space (no sum across columns), its
+ * own complex Hessenberg matrix and rotations on the host; per block step ONE blocked pass pair over the real-equivalent factor, ONE pass
+ * over the matrix, classical Gram-Schmidt twice batched over the columns with complex coefficients (kernels_krylov_complex_blocked.hpp: per
+ * column the sums of the single complex kernels in their order), ONE host read of C (4 k + 6) doubles; finished columns are masked out.
+ * The step counts are those of the single complex form, not of real GMRES on the 2 n system.  nrhs == 1 is the single form, bit for bit.
+ * Block bases: (2 m + 1) x min(nrhs, 16) x 2 n doubles, HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES; HIPMF_COUNTER_UPDATED_BLOCKS,
+ * _UPDATED_COLUMN_STEPS, _UPDATED_STEPS (blocked pass pairs) and _UPDATED_CYCLES as for the real block form.
+ * WHEN IT PAYS (tools/solve_updated.py --complex --nrhs N, one MI355X, one run per N, profiles/r13_solve_updated_complex_many.txt): 500 x 500
+ * complex shifted grid, h -> h/2 (11 steps per column), medians per column: N = 16: (a) this call 1.396 ms, (b) N single
+ * complex_solver_hipmf_solve_updated_device calls 5.141 ms, (c) complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve_many
+ * 0.823 ms; N = 64: (a) 1.400, (b) 4.995, (c) 0.418 ms.  The block form is 3.6 - 3.7 times faster than the loop of single calls; with 16 or
+ * more columns and 11 steps the refactorisation, whose cost the columns share, is cheaper still: by these figures the call pays against
+ * (c) for few columns or few steps (a block step of 16 columns costs 2.0 ms, (c) about 8 ms + 0.3 ms per column).
+ * ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order, then ERROR_HIPMF_INVALID_VALUE (nrhs < 1, ld < n,
+ * a non-finite rel_tol, then a `mapped` that does not name the map in force). */
+int32_t complex_solver_hipmf_solve_updated_many(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld,
+                                                const double *values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
+                                                C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_updated_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                       const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                                       double *relres);
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *solver);
 
 /* plain device-memory helpers so that callers need no HIP binding of their own */

@@ -101,6 +101,12 @@ const char *rh_clinsolver_solve_transpose(void *solver, double *x, int64_t nx, c
  * "Error(2): ..." when the tolerance was not reached (x: best iterate) */
 const char *rh_clinsolver_solve_updated(void *solver, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
                                         int32_t *steps, double *relres, int32_t verbose);
+/* extensions of the HIPMF backend for nrhs right-hand sides (complex_solver_hipmf_solve_many / complex_solver_hipmf_solve_updated_many of
+ * russell_hipmf.h): x, rhs column-major n x nrhs complex arrays, interleaved (2 n nrhs doubles), 16 columns per pass pair; steps / relres
+ * nrhs entries; "Error(2): ..." when any column did not reach the tolerance (x, steps and relres are written then too) */
+const char *rh_clinsolver_solve_many(void *solver, double *x, const double *rhs, int64_t n, int64_t nrhs);
+const char *rh_clinsolver_solve_updated_many(void *solver, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                             int32_t *steps, double *relres, int32_t verbose);
 /* determinant = (det_re + i det_im) x 10^det_exp (LinSolParams.compute_determinant; complex_solver_umfpack.rs:411-414) */
 void rh_clinsolver_outputs(void *solver, double *det_re, double *det_im, double *det_exp, double *rcond, int32_t *npert);
 /* the eight values of mumps_stats (RINFOG(4..11)) of the last solve when LinSolParams.compute_error_estimates (entries 0 - 4) or

@@ -76,6 +76,12 @@ SYMBOLS = {
                                                        C.POINTER(C.c_double), C.c_int32]),
     "complex_solver_hipmf_solve_updated_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32,
                                                               C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "complex_solver_hipmf_solve_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_updated_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, f64p, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                                            C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_solve_updated_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                                                   C.c_int32, C.c_void_p, C.c_void_p]),
     "complex_solver_hipmf_get_stats": (C.c_int32, [C.c_void_p, i64p, f64p]),
     "complex_solver_hipmf_get_counter": (C.c_int64, [C.c_void_p, C.c_int32]),
     "complex_solver_hipmf_last_error": (C.c_char_p, [C.c_void_p]),

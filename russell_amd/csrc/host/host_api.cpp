@@ -765,6 +765,8 @@ struct Backend {
     decltype(&solver_hipmf_get_counter) get_counter = nullptr;
     decltype(&complex_solver_hipmf_get_counter) zget_counter = nullptr;
     decltype(&complex_solver_hipmf_solve_updated) zsolve_updated = nullptr;
+    decltype(&complex_solver_hipmf_solve_many) zsolve_many = nullptr;
+    decltype(&complex_solver_hipmf_solve_updated_many) zsolve_updated_many = nullptr;
     bool tried = false;
 };
 Backend g_backend;
@@ -825,6 +827,8 @@ bool load_backend() {
     BIND(get_counter, "solver_hipmf_get_counter")
     BIND(zget_counter, "complex_solver_hipmf_get_counter")
     BIND(zsolve_updated, "complex_solver_hipmf_solve_updated")
+    BIND(zsolve_many, "complex_solver_hipmf_solve_many")
+    BIND(zsolve_updated_many, "complex_solver_hipmf_solve_updated_many")
 #undef BIND
     g_backend.dl = dl;
     return true;
@@ -1262,13 +1266,61 @@ StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const Complex
     if (!factorized) return "the function factorize must be called before solve";
     if (x.size() != 2 * initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
     if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
+    std::vector<double> conv;
+    const double *values = nullptr;
+    StrError e = updated_values(mat, rel_tol, conv, &values);
+    if (e) return e;
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_updated((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), values, value_map_set ? 1 : 0, rel_tol, max_steps, steps, relres,
+                                              verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// The same for nrhs right-hand sides (complex_solver_hipmf_solve_updated_many): x and rhs column-major ndim x nrhs complex, interleaved,
+// steps and relres one entry per column.  The error string of status 2 when any column did not converge; x, steps and relres are
+// written then too.
+StrError ComplexSolverHIPMF::solve_updated_many(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol,
+                                                int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (nrhs < 1) return "the number of right-hand sides must be at least one";
+    if (rhs.size() != 2 * initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
+    if (x.size() != 2 * initialized_ndim * nrhs) return "the dimension of the vector of unknown values x is incorrect";
+    std::vector<double> conv;
+    const double *values = nullptr;
+    StrError e = updated_values(mat, rel_tol, conv, &values);
+    if (e) return e;
+    steps.assign(nrhs, 0), relres.assign(nrhs, 0.0);
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_updated_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, values,
+                                                   value_map_set ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(), verbose ? 1 : 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// nrhs ordinary solves, 16 columns per pass pair (complex_solver_hipmf_solve_many): x and rhs column-major ndim x nrhs complex, interleaved
+StrError ComplexSolverHIPMF::solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (nrhs < 1 || x.size() != 2 * initialized_ndim * nrhs) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != 2 * initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// What the solve_updated forms hand to the backend for `mat`: *values points at mat's own triplet values (the order the value map was
+// built from) or at conv, the values converted on the host.
+StrError ComplexSolverHIPMF::updated_values(const ComplexCooMatrix &mat, double rel_tol, std::vector<double> &conv, const double **values) const {
     if (mat.symmetric != initialized_sym) return "the updated matrix must be the factorized matrix with new values (symmetric differs)";
     if (mat.nrow != initialized_ndim || mat.ncol != initialized_ndim) return "the updated matrix must be the factorized matrix with new values (ndim differs)";
     if (mat.nnz != initialized_nnz) return "the updated matrix must be the factorized matrix with new values (nnz differs)";
     if (!std::isfinite(rel_tol)) return "the relative tolerance must be a finite number";
     const bool same_order = value_map_set && std::memcmp(map_i.data(), mat.indices_i.data(), sizeof(int32_t) * mat.nnz) == 0 &&
                             std::memcmp(map_j.data(), mat.indices_j.data(), sizeof(int32_t) * mat.nnz) == 0;
-    std::vector<double> conv;
     if (!same_order) {
         const size_t nent = zci.size();
         std::vector<double> sum(2 * nent, 0.0);
@@ -1294,11 +1346,7 @@ StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const Complex
             conv.swap(sum);
         }
     }
-    uint64_t t0 = now_ns();
-    int32_t status = g_backend.zsolve_updated((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), same_order ? mat.values.data() : conv.data(), value_map_set ? 1 : 0,
-                                              rel_tol, max_steps, steps, relres, verbose ? 1 : 0);
-    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
-    time_solve_ns = now_ns() - t0;
+    *values = same_order ? mat.values.data() : conv.data();
     return nullptr;
 }
 
@@ -1911,6 +1959,32 @@ const char *rh_clinsolver_solve_updated(void *h, double *x, int64_t nx, void *cc
     std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
     StrError e = s->s->solve_updated(xx, *(const ComplexCooMatrix *)ccoo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
     if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+// x, rhs: column-major n x nrhs complex arrays, interleaved (2 n nrhs doubles)
+const char *rh_clinsolver_solve_many(void *h, double *x, const double *rhs, int64_t n, int64_t nrhs) {
+    RhComplexSolver *s = (RhComplexSolver *)h;
+    if (!x || !rhs) return "solve_many needs x and right-hand sides";
+    const size_t len = n > 0 && nrhs > 0 ? 2 * (size_t)n * (size_t)nrhs : 0;
+    std::vector<double> xx(len), rr(rhs, rhs + len);
+    StrError e = s->s->solve_many(xx, rr, (size_t)(nrhs > 0 ? nrhs : 0));
+    if (!e) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+const char *rh_clinsolver_solve_updated_many(void *h, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                             int32_t *steps, double *relres, int32_t verbose) {
+    RhComplexSolver *s = (RhComplexSolver *)h;
+    if (!ccoo || !x || !rhs || !steps || !relres) return "solve_updated_many needs a matrix, x, right-hand sides, steps and relres";
+    const size_t len = n > 0 && nrhs > 0 ? 2 * (size_t)n * (size_t)nrhs : 0;
+    const std::vector<double> rr(rhs, rhs + len);
+    std::vector<double> xx(len), rel;
+    std::vector<int32_t> st;
+    StrError e = s->s->solve_updated_many(xx, *(const ComplexCooMatrix *)ccoo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0);
+    if (st.size() == (size_t)nrhs) { // (the backend ran: the best iterates and the per-column figures go out with the error string of status 2 too)
+        std::copy(xx.begin(), xx.end(), x);
+        std::copy(st.begin(), st.end(), steps);
+        std::copy(rel.begin(), rel.end(), relres);
+    }
     return e;
 }
 const char *rh_clinsolver_solve(void *h, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose) {

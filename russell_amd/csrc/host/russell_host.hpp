@@ -284,6 +284,13 @@ class ComplexSolverHIPMF {
     // string of handle_hipmf_error_code; x then holds the best iterate.
     StrError solve_updated(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
                            double *relres, bool verbose);
+    // extension: nrhs right-hand sides, 16 columns per pass pair over the factor (complex_solver_hipmf_solve_many); x, rhs: column-major
+    // n x nrhs complex arrays, interleaved (2 n nrhs doubles)
+    StrError solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs);
+    // extension: solve_updated for nrhs right-hand sides, 16 per blocked pass pair, every column its own complex iteration
+    // (complex_solver_hipmf_solve_updated_many); steps, relres: resized to nrhs
+    StrError solve_updated_many(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol, int32_t max_steps,
+                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose);
     // complex_solver_mumps.rs:262-268: compute_condition_numbers -> 1 (all eight values), compute_error_estimates -> 2 (entries 0 - 4),
     // else 0, set by every factorize; solve then goes through complex_solver_hipmf_solve_with_error_analysis, and update_stats fills
     // mumps_stats (complex_solver_mumps.rs:429-436)
@@ -302,6 +309,7 @@ class ComplexSolverHIPMF {
 
   private:
     ComplexSolverHIPMF() {}
+    StrError updated_values(const ComplexCooMatrix &mat, double rel_tol, std::vector<double> &conv, const double **values) const;
     void *solver = nullptr; // struct InterfaceComplexHIPMF*
     bool initialized = false, value_map_set = false;
     Sym initialized_sym = Sym::No;

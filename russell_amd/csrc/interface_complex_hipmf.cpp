@@ -17,6 +17,7 @@
 #include <hipmf_device_rt.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <new>
 #include <string>
@@ -287,6 +288,25 @@ int32_t complex_solver_hipmf_solve(struct InterfaceComplexHIPMF *h, double *x, c
     return guarded(h, [&]() { return c_solve_body(h, x, rhs, verbose); });
 }
 
+// nrhs columns in blocks of 16 per pass pair (Solver::solve on the real-equivalent system: refinement and the Krylov rescue as the handle
+// is set up).  x, rhs: column-major ld x nrhs complex arrays, interleaved: columns 2 ld doubles apart.  Status codes and their order:
+// those of solver_hipmf_solve_many.
+static int32_t c_solve_many_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose, bool on_device) {
+    if (!h || !x || !rhs) return ERROR_NULL_POINTER;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (nrhs < 1 || ld < h->n) return ERROR_HIPMF_INVALID_VALUE;
+    if (!on_device) h->solver.opt.verbose = verbose == 1;
+    return h->solver.solve(x, rhs, nrhs, 2 * (int64_t)ld, on_device);
+}
+
+int32_t complex_solver_hipmf_solve_many(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_many_body(h, x, rhs, nrhs, ld, verbose, false); });
+}
+
+int32_t complex_solver_hipmf_solve_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld) {
+    return guarded(h, [&]() { return c_solve_many_body(h, d_x, d_rhs, nrhs, ld, 0, true); });
+}
+
 // Solve with new matrix values on the kept factor in complex arithmetic (Solver::solve_updated_complex).  The handle always carries a
 // signed value map -- identity after initialize / complex_solver_hipmf_factorize, the caller's triplets after set_value_map -- and this
 // call must not swap it (that would change what a later factorize_mapped reads): `mapped` has to name the map in force.
@@ -321,6 +341,45 @@ int32_t complex_solver_hipmf_solve_updated_device(struct InterfaceComplexHIPMF *
                                                   double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
     return guarded(h, [&]() {
         return c_solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "complex_solver_hipmf_solve_updated_device");
+    });
+}
+
+// The same for nrhs columns (Solver::solve_updated_many_complex): blocks of 16 columns, every column its own complex flexible GMRES, in
+// lockstep.  ld counts complex elements.  The order of the status codes is that of solver_hipmf_solve_updated_many; the map check of the
+// single complex form comes last.
+static int32_t c_solve_updated_many_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values,
+                                         int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device,
+                                         const char *who) {
+    if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (nrhs < 1 || ld < h->n || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if ((mapped != 0) != h->triplet_map) {
+        h->solver.last_error = mapped != 0 ? std::string(who) + ": mapped = 1 but no triplet map is installed (complex_solver_hipmf_set_value_map)"
+                                           : std::string(who) + ": mapped = 0 but the triplet map of complex_solver_hipmf_set_value_map is installed";
+        return ERROR_HIPMF_INVALID_VALUE;
+    }
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_updated_many_complex(x, rhs, nrhs, 2 * (int64_t)ld, values, rel_tol, max_steps, steps, relres, on_device);
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %d column(s) %s: %lld column step(s) in %lld blocked pass pair(s), %lld cycle(s), %lld block(s)\n", who, nrhs,
+               code == SUCCESSFUL_EXIT ? "converged" : "NOT all converged", (long long)h->solver.updated_column_steps, (long long)h->solver.updated_steps,
+               (long long)h->solver.updated_cycles, (long long)h->solver.updated_blocks);
+    return code;
+}
+
+int32_t complex_solver_hipmf_solve_updated_many(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values,
+                                                int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_updated_many_body(h, x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "complex_solver_hipmf_solve_updated_many");
+    });
+}
+
+int32_t complex_solver_hipmf_solve_updated_many_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                       const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
+    return guarded(h, [&]() {
+        return c_solve_updated_many_body(h, d_x, d_rhs, nrhs, ld, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true,
+                                         "complex_solver_hipmf_solve_updated_many_device");
     });
 }
 
@@ -424,6 +483,10 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_UPDATED_SPMV_US: return (int64_t)(1e3 * s.updated_ms[1]);
     case HIPMF_COUNTER_UPDATED_ARNOLDI_US: return (int64_t)(1e3 * s.updated_ms[2]);
     case HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC: return s.updated_complex ? 1 : 0;
+    case HIPMF_COUNTER_BLOCK_GROUPS: return s.block_groups_last;
+    case HIPMF_COUNTER_UPDATED_BLOCKS: return s.updated_blocks;
+    case HIPMF_COUNTER_UPDATED_COLUMN_STEPS: return s.updated_column_steps;
+    case HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES: return s.updated_block_basis_bytes();
     default: return -1;
     }
 }

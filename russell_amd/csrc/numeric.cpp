@@ -24,6 +24,7 @@
 #include "kernels_krylov.hpp"
 #include "kernels_krylov_blocked.hpp"
 #include "kernels_krylov_complex.hpp"
+#include "kernels_krylov_complex_blocked.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3403,8 +3404,9 @@ struct NestedSolveGuard {
     void unrefined_quiet() const { s.opt.refinement_nstep = 0, s.opt.verbose = false, s.in_rescue = true; } // (and no Krylov rescue inside)
 };
 
-// The arithmetic of the single-column core: the scalar of the host's least-squares problem, doubles per coefficient (and with them
-// the restart bound), the label of the verbose lines and the three launches that differ (kernels_krylov.hpp, kernels_krylov_complex.hpp).
+// The arithmetic of the single-column core and of the block driver: the scalar of the host's least-squares problem, doubles per
+// coefficient (and with them the restart bound), the labels of the verbose lines and the three launches that differ, single
+// (kernels_krylov.hpp, kernels_krylov_complex.hpp) and blocked (kernels_krylov_blocked.hpp, kernels_krylov_complex_blocked.hpp).
 struct UpdatedReal {
     typedef double scalar;
     static constexpr int32_t D = 1; // doubles per coefficient; the restart length is at most n / D
@@ -3412,6 +3414,16 @@ struct UpdatedReal {
     static void dots(dim3 g, hipStream_t st, int64_t n, const double *w, const double *V, int32_t nv, double *part) { hipLaunchKernelGGL(k_kry_dots, g, dim3(256), 0, st, n, w, V, nv, part); }
     static void update(dim3 g, hipStream_t st, int64_t n, double *w, const double *V, int32_t nv, const double *h, double *part) { hipLaunchKernelGGL(k_kry_update, g, dim3(256), 0, st, n, w, V, nv, h, part); }
     static void combine(dim3 g, hipStream_t st, int64_t n, double *x, const double *Z, int32_t nv, const double *y) { hipLaunchKernelGGL(k_kry_combine, g, dim3(256), 0, st, n, x, Z, nv, y); }
+    static constexpr const char *label_many = "solve_updated_many";
+    static void dots_blk(dim3 g, hipStream_t st, int64_t n, const double *W, const double *V, int64_t vstr, int32_t nv, uint32_t mask, double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_kryb_dots, g, dim3(256), 0, st, n, W, V, vstr, nv, mask, part, pcol);
+    }
+    static void update_blk(dim3 g, hipStream_t st, int64_t n, double *W, const double *V, int64_t vstr, int32_t nv, uint32_t mask, const double *h, int64_t hstr, double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_kryb_update, g, dim3(256), 0, st, n, W, V, vstr, nv, mask, h, hstr, part, pcol);
+    }
+    static void combine_blk(dim3 g, hipStream_t st, int64_t n, double *X, int64_t xstr, const double *Z, int64_t vstr, uint32_t mask, const int32_t *cnt, const double *y, int64_t ystr) {
+        hipLaunchKernelGGL(k_kryb_combine, g, dim3(256), 0, st, n, X, xstr, Z, vstr, mask, cnt, y, ystr);
+    }
 };
 struct UpdatedComplex {
     typedef std::complex<double> scalar;
@@ -3420,6 +3432,16 @@ struct UpdatedComplex {
     static void dots(dim3 g, hipStream_t st, int64_t n, const double *w, const double *V, int32_t nv, double *part) { hipLaunchKernelGGL(k_zkry_dots, g, dim3(256), 0, st, n, w, V, nv, part); }
     static void update(dim3 g, hipStream_t st, int64_t n, double *w, const double *V, int32_t nv, const double *h, double *part) { hipLaunchKernelGGL(k_zkry_update, g, dim3(256), 0, st, n, w, V, nv, h, part); }
     static void combine(dim3 g, hipStream_t st, int64_t n, double *x, const double *Z, int32_t nv, const double *y) { hipLaunchKernelGGL(k_zkry_combine, g, dim3(256), 0, st, n, x, Z, nv, y); }
+    static constexpr const char *label_many = "solve_updated_many (complex)";
+    static void dots_blk(dim3 g, hipStream_t st, int64_t n, const double *W, const double *V, int64_t vstr, int32_t nv, uint32_t mask, double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_zkryb_dots, g, dim3(256), 0, st, n, W, V, vstr, nv, mask, part, pcol);
+    }
+    static void update_blk(dim3 g, hipStream_t st, int64_t n, double *W, const double *V, int64_t vstr, int32_t nv, uint32_t mask, const double *h, int64_t hstr, double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_zkryb_update, g, dim3(256), 0, st, n, W, V, vstr, nv, mask, h, hstr, part, pcol);
+    }
+    static void combine_blk(dim3 g, hipStream_t st, int64_t n, double *X, int64_t xstr, const double *Z, int64_t vstr, uint32_t mask, const int32_t *cnt, const double *y, int64_t ystr) {
+        hipLaunchKernelGGL(k_zkryb_combine, g, dim3(256), 0, st, n, X, xstr, Z, vstr, mask, cnt, y, ystr);
+    }
 };
 
 // The transposed pass pair on one vector (kernels_solve_transpose.hpp) or on a block of TR_KB (kernels_solve_transpose_blocked.hpp): the
@@ -3768,7 +3790,7 @@ int32_t Solver::solve_updated_complex(double *x, const double *rhs, const double
 // Every column runs the flexible GMRES above on its own -- own basis, own Hessenberg matrix, rotations and g on the host -- and the
 // columns of a block of KRYB_COLS advance in lockstep: per block step ONE blocked pass pair Z_k = M^{-1} V_k (solve_core on the C
 // contiguous columns of step k), ONE pass over the matrix (k_kryb_spmv), CGS2 and the normalisation batched over the columns, ONE host
-// read of the block's record, C (2 k + 4) doubles.  A column that is done for the cycle (rotation estimate at the tolerance, hn not
+// read of the block's record, C (2 k + 4) doubles (complex coefficients: C (4 k + 6)).  A column that is done for the cycle (rotation estimate at the tolerance, hn not
 // positive, a non-finite record, its step limit) is "parked": its bit leaves the mask every kernel takes and its column of V_{k+1} is
 // zeros.  At the end of a cycle (k == m or every column parked) every column gets its own back substitution over its own count of
 // directions, one combine and one residual launch serve the block; a column is finished for the call when its TRUE residual meets the
@@ -3785,6 +3807,37 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
         updated_blocks = 0, updated_column_steps = updated_steps;
         return code;
     }
+    return solve_updated_many_core<UpdatedReal>(x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+}
+
+// The block form for the real-equivalent system of a COMPLEX matrix (complex_solver_hipmf_solve_updated_many): the same lockstep
+// iteration with complex coefficients per column (kernels_krylov_complex_blocked.hpp), on the conditions of solve_updated_complex.
+// ld counts doubles (twice the caller's complex leading dimension, so every column starts on a complex element).
+int32_t Solver::solve_updated_many_complex(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, double rel_tol, int32_t max_steps,
+                                           int32_t *steps_out, double *relres_out, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs || !values) return ERROR_NULL_POINTER;
+    if (nrhs < 1 || ld < S.n || (ld & 1) || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (nnz_in < 1 || (S.n & 1) || d_emap) return ERROR_HIPMF_INVALID_VALUE; // the complex handle: a value map, pairs, a general pattern
+    if (nrhs == 1) {
+        const int32_t code = solve_updated_complex(x, rhs, values, rel_tol, max_steps, steps_out, relres_out, on_device);
+        updated_blocks = 0, updated_column_steps = updated_steps;
+        return code;
+    }
+    updated_complex = true;
+    return solve_updated_many_core<UpdatedComplex>(x, rhs, nrhs, ld, values, true, rel_tol, max_steps, steps_out, relres_out, on_device);
+}
+
+// One driver serves both arithmetics, as solve_updated_core does: the policy P gives the three blocked launches that differ and the
+// doubles per coefficient D, which size the step's record (2 D nv + 2 doubles per column), the partial-sum slots (D (m + 1) nblk per
+// column), the restart bound (n / D), y (D m doubles per column) and the scalar of the per-column least-squares problems.  With D = 1
+// every launch, its order and its arguments are those of the real driver before the complex form existed.
+template <class P>
+int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol,
+                                        int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device) {
+    typedef typename P::scalar T;
+    constexpr int32_t D = P::D;
     DeviceScope dev_scope(device);
     const int32_t n = S.n;
     const UpdatedParams par(rel_tol, max_steps);
@@ -3799,31 +3852,31 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
     // buffers: bases for min(nrhs, 16) columns, wider when a later call is; the restart length is halved (down to 4) when they do not fit
     const int32_t CW = std::min<int32_t>(nrhs, KRYB_COLS);
     const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE);
-    int32_t m = std::max(4, std::min(par.restart, n));
-    if (ub_m < m || ub_cols < CW) {
+    int32_t m = std::max(4, std::min(par.restart, n / D));
+    if (ub_m < m || ub_cols < CW || ub_d < D) {
         const int32_t cols = std::max(ub_cols, CW);
-        ub_m = ub_cols = 0;
+        ub_m = ub_cols = ub_d = 0;
         const int32_t mm = grow_bases(d_ub_V, d_ub_Z, m, (size_t)cols * n);
         if (mm == 0) {
             last_error = "solve_updated_many: no device memory for the Krylov bases";
             return ERROR_HIP_MALLOC;
         }
-        const size_t pcol_new = std::max((size_t)(mm + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1));
-        const size_t rec_new = (size_t)cols * (3 * (size_t)mm + 4);
+        const size_t pcol_new = std::max((size_t)D * (mm + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1));
+        const size_t rec_new = (size_t)cols * (3 * (size_t)D * mm + 4);
         if (d_ub_vec.alloc(4 * (size_t)cols * n) != hipSuccess || d_ub_part.alloc(pcol_new * cols) != hipSuccess || d_ub_rec.alloc(rec_new) != hipSuccess ||
             h_ub.alloc(rec_new) != hipSuccess || d_ub_cnt.alloc((size_t)cols) != hipSuccess || h_ub_cnt.alloc((size_t)cols) != hipSuccess) {
             d_ub_V.reset(), d_ub_Z.reset();
             (void)hipGetLastError();
             return ERROR_HIP_MALLOC;
         }
-        ub_m = mm, ub_cols = cols;
+        ub_m = mm, ub_cols = cols, ub_d = D;
     }
     m = std::min(m, ub_m);
     if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(S.nnz_a, 1)), ERROR_HIP_MALLOC);
     HIPC(timer.create(), ERROR_HIP_SYNCHRONIZE);
-    const int64_t pcol = (int64_t)std::max((size_t)(ub_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1)); // partial-sum slots of a column
-    // device record and its pinned mirror: the step's record, C (2 nv + 2) | the residuals' sums, 2 C | y, column c at c m
-    const size_t off_res = (size_t)ub_cols * (2 * (size_t)ub_m + 2), off_y = off_res + 2 * (size_t)ub_cols;
+    const int64_t pcol = (int64_t)std::max((size_t)D * (ub_m + 1) * nblk, 2 * (size_t)std::max(spmv_blocks, 1)); // partial-sum slots of a column
+    // device record and its pinned mirror: the step's record, C (2 D nv + 2) | the residuals' sums, 2 C | y, column c at c D m
+    const size_t off_res = (size_t)ub_cols * (2 * (size_t)D * ub_m + 2), off_y = off_res + 2 * (size_t)ub_cols;
     double *const d_rec = d_ub_rec, *const d_res = d_ub_rec + off_res, *const d_y = d_ub_rec + off_y;
     double *const h_rec = h_ub, *const h_res = h_ub + off_res, *const h_y = h_ub + off_y;
     const size_t nb = sizeof(double) * (size_t)n;
@@ -3834,8 +3887,9 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
     if (code != SUCCESSFUL_EXIT) return code;
 
     bool all_converged = true;
-    std::vector<GivensLsq<double>> lsq((size_t)KRYB_COLS, GivensLsq<double>(m)); // per column of a block
-    std::vector<double> hcol((size_t)m);
+    std::vector<GivensLsq<T>> lsq((size_t)KRYB_COLS, GivensLsq<T>(m)); // per column of a block
+    std::vector<T> crec(2 * (size_t)m), hcol((size_t)m), y((size_t)m);
+    const int64_t ystr = (int64_t)D * m; // between the coefficients y of two columns
     {
         const NestedSolveGuard guard(*this);
         guard.unrefined_quiet();
@@ -3868,10 +3922,9 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
             // X_c += Z_c y_c over the first kc[c] directions for the columns of `mask` (h_y, h_ub_cnt filled by the caller; no synchronisation:
             // the residual that follows brings it)
             auto combine = [&](uint32_t mask) -> int32_t {
-                HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * (size_t)C * m, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+                HIPC(hipMemcpyAsync(d_y, h_y, sizeof(double) * (size_t)C * ystr, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
                 HIPC(hipMemcpyAsync(d_ub_cnt, h_ub_cnt, sizeof(int32_t) * (size_t)C, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
-                hipLaunchKernelGGL(k_kryb_combine, gk, b256, 0, STREAM, (int64_t)n, d_xx, xstr, (const double *)d_ub_Z, vstr, mask, (const int32_t *)d_ub_cnt, (const double *)d_y,
-                                   (int64_t)m);
+                P::combine_blk(gk, STREAM, (int64_t)n, d_xx, xstr, (const double *)d_ub_Z, vstr, mask, (const int32_t *)d_ub_cnt, (const double *)d_y, ystr);
                 return SUCCESSFUL_EXIT;
             };
 
@@ -3915,16 +3968,17 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
                                        act); // W = A_new Z_k
                     timer.mark(2);
                     const int32_t nv = k + 1;
-                    const int64_t rstr = 2 * (int64_t)nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
+                    const int64_t rstr = 2 * (int64_t)D * nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
+                    double *const d_nrm = d_rec + 2 * (size_t)D * nv;
                     for (int32_t round = 0; round < 2; round++) { // CGS2
-                        double *const hr = d_rec + (size_t)round * nv;
-                        hipLaunchKernelGGL(k_kryb_dots, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_ub_V, vstr, nv, act, (double *)d_ub_part, pcol);
-                        hipLaunchKernelGGL(k_kryb_reduce, dim3((unsigned)nv, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, hr, rstr);
-                        hipLaunchKernelGGL(k_kryb_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)d_ub_V, vstr, nv, act, (const double *)hr, rstr, (double *)d_ub_part, pcol);
-                        hipLaunchKernelGGL(k_kryb_reduce, dim3(1, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, d_rec + 2 * (size_t)nv + round, rstr);
+                        double *const hr = d_rec + (size_t)round * D * nv;
+                        P::dots_blk(gk, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_ub_V, vstr, nv, act, (double *)d_ub_part, pcol);
+                        hipLaunchKernelGGL(k_kryb_reduce, dim3((unsigned)(D * nv), (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, hr, rstr);
+                        P::update_blk(gk, STREAM, (int64_t)n, d_w, (const double *)d_ub_V, vstr, nv, act, (const double *)hr, rstr, (double *)d_ub_part, pcol);
+                        hipLaunchKernelGGL(k_kryb_reduce, dim3(1, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, nblk, act, d_nrm + round, rstr);
                     }
                     double *const vnext = d_ub_V + (size_t)(k + 1) * vstr;
-                    hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (int64_t)n, (const double *)(d_rec + 2 * (size_t)nv + 1), rstr, vnext, (int64_t)n,
+                    hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (int64_t)n, (const double *)(d_nrm + 1), rstr, vnext, (int64_t)n,
                                        act, parked);
                     timer.mark(3);
                     if (hipMemcpyAsync(h_rec, d_rec, sizeof(double) * (size_t)C * rstr, hipMemcpyDeviceToHost, STREAM) != hipSuccess) code = ERROR_HIP_MEMCPY;
@@ -3937,21 +3991,22 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
                         if (!((act >> c) & 1u)) continue;
                         const double *const rec = h_rec + (size_t)c * rstr;
                         bool finite = true;
-                        for (int32_t j = 0; j < 2 * nv + 2; j++) finite = finite && std::isfinite(rec[j]);
+                        for (int32_t j = 0; j < rstr; j++) finite = finite && std::isfinite(rec[j]);
                         if (!finite) { // (the column leaves the cycle with the directions before this one; the step is not counted for it)
                             newly |= 1u << c;
                             continue;
                         }
                         steps[c]++, updated_column_steps++, counted = true;
-                        for (int32_t j = 0; j < nv; j++) hcol[(size_t)j] = rec[j] + rec[nv + j];
-                        const double hn = sqrt(rec[2 * nv + 1]);
+                        memcpy(crec.data(), rec, sizeof(T) * 2 * nv); // the new Hessenberg column: the coefficients of the two rounds, added
+                        for (int32_t j = 0; j < nv; j++) hcol[(size_t)j] = crec[(size_t)j] + crec[(size_t)(nv + j)];
+                        const double hn = sqrt(rec[rstr - 1]);
                         lsq[(size_t)c].push(k, hcol.data(), hn);
-                        const double *const gc = lsq[(size_t)c].g.data();
+                        const double est = std::abs(lsq[(size_t)c].g[(size_t)k + 1]);
                         if (guard.verbose)
-                            fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", j0 + c, (long long)updated_cycles, k + 1,
-                                    fabs(gc[k + 1]), bnorm[c]);
+                            fprintf(stderr, "hipmf: %s: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label_many, j0 + c, (long long)updated_cycles, k + 1, est,
+                                    bnorm[c]);
                         kc[c] = k + 1;
-                        if (fabs(gc[k + 1]) <= par.tol * bnorm[c] || !(hn > 0.0) || steps[c] >= par.step_limit) newly |= 1u << c;
+                        if (est <= par.tol * bnorm[c] || !(hn > 0.0) || steps[c] >= par.step_limit) newly |= 1u << c;
                     }
                     if (counted) updated_steps++;
                     parked |= newly;
@@ -3969,7 +4024,8 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
                         done |= 1u << c;
                         continue;
                     }
-                    lsq[(size_t)c].solve(kc[c], h_y + (size_t)c * m);
+                    lsq[(size_t)c].solve(kc[c], y.data());
+                    memcpy(h_y + (size_t)c * ystr, y.data(), sizeof(T) * (size_t)kc[c]);
                     h_ub_cnt[c] = kc[c];
                     moved |= 1u << c;
                 }
@@ -3981,7 +4037,7 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
                 for (int32_t c = 0; c < C; c++) {
                     if (!((moved >> c) & 1u)) continue;
                     const double now = sqrt(h_res[2 * c]);
-                    if (guard.verbose) fprintf(stderr, "hipmf: solve_updated_many: column %d cycle %lld: |r| %.3e -> %.3e\n", j0 + c, (long long)updated_cycles, rnorm[c], now);
+                    if (guard.verbose) fprintf(stderr, "hipmf: %s: column %d cycle %lld: |r| %.3e -> %.3e\n", P::label_many, j0 + c, (long long)updated_cycles, rnorm[c], now);
                     if (!(now < rnorm[c])) { // no gain (or not a number): the column's cycle is taken back, x_c is the best iterate
                         back |= 1u << c, done |= 1u << c;
                         continue;
@@ -3992,7 +4048,7 @@ int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, i
                 if (back) {
                     for (int32_t c = 0; c < C; c++)
                         if ((back >> c) & 1u)
-                            for (int32_t j = 0; j < kc[c]; j++) h_y[(size_t)c * m + j] = -h_y[(size_t)c * m + j];
+                            for (int32_t j = 0; j < D * kc[c]; j++) h_y[(size_t)c * ystr + j] = -h_y[(size_t)c * ystr + j];
                     code = combine(back);
                     if (code == SUCCESSFUL_EXIT) code = residual(back);
                     if (code != SUCCESSFUL_EXIT) break;

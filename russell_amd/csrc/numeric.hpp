@@ -183,12 +183,14 @@ struct SolverUpdated {
     EventOwner up_ev[4];    // HIPMF_UPDATED_TIMING=1: around the pass pair, the SpMV and the Arnoldi kernels of a step
     // solver_hipmf_solve_updated_many (kernels_krylov_blocked.hpp): bases of a block of columns, V[(k C + c) n + i], of their own -- the
     // single form's stay as they are --, four n x C blocks (W, R, X, B; the device form uses the caller's x and b), partial sums per column,
-    // the step's record C (2 k + 4), the residuals' 2 C sums and the C m coefficients of the combine with its pinned mirror, the counts k_c
+    // the step's record C (2 D k + 2 D + 2), the residuals' 2 C sums and the C D m coefficients of the combine with its pinned mirror, the
+    // counts k_c; D = 1 (real coefficients) or 2 (complex_solver_hipmf_solve_updated_many, kernels_krylov_complex_blocked.hpp)
     DeviceArray<double> d_ub_V, d_ub_Z, d_ub_vec, d_ub_part, d_ub_rec;
     DeviceArray<int32_t> d_ub_cnt;
     PinnedArray<double> h_ub;
     PinnedArray<int32_t> h_ub_cnt;
     int32_t ub_m = 0, ub_cols = 0; // restart length and columns the block buffers are allocated for (0: not allocated)
+    int32_t ub_d = 0;              // ... and the doubles per coefficient (1 real, 2 complex) the partial sums and the record are sized for
 };
 
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
@@ -361,6 +363,10 @@ class Solver : public SolverDevice {
     int32_t solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
                                   bool on_device);
     bool updated_complex = false; // the last solve_updated_complex orthogonalised in complex arithmetic (false before the first)
+    // solve_updated_many for that system (the complex C-ABI): x, rhs column-major with ld DOUBLES (even, >= S.n) between columns; every
+    // column its own flexible GMRES in complex arithmetic (kernels_krylov_complex_blocked.hpp).  nrhs == 1 is solve_updated_complex.
+    int32_t solve_updated_many_complex(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, double rel_tol, int32_t max_steps, int32_t *steps,
+                                       double *relres, bool on_device);
     int64_t updated_blocks = 0, updated_column_steps = 0; // of the last solve_updated_many: 16-column blocks (0: single form), sum of the columns' steps
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
@@ -554,6 +560,10 @@ class Solver : public SolverDevice {
     // the flexible GMRES of solve_updated and solve_updated_complex; P: the arithmetic (UpdatedReal, UpdatedComplex in numeric.cpp)
     template <class P>
     int32_t solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, bool on_device);
+    // the block driver of solve_updated_many and solve_updated_many_complex; P as above
+    template <class P>
+    int32_t solve_updated_many_core(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                    double *relres, bool on_device);
     // the error analysis of both forms; P: what differs (EaReal, EaComplex in numeric.cpp)
     template <class P>
     int32_t error_analysis_core(const double *xbar, const double *rhs, double *out, int32_t option);

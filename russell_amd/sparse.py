@@ -186,6 +186,8 @@ def _L():
         "rh_clinsolver_solve": (cp, [vp, vp, i64, vp, i64, i32]),
         "rh_clinsolver_solve_transpose": (cp, [vp, vp, i64, vp, i64, i32, i32]),
         "rh_clinsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
+        "rh_clinsolver_solve_many": (cp, [vp, vp, vp, i64, i64]),
+        "rh_clinsolver_solve_updated_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
         "rh_clinsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(f64), pp(i32)]),
         "rh_clinsolver_mumps_stats": (None, [vp, vp]),
         "rh_error_string": (cp, [i32]),
@@ -718,6 +720,32 @@ class _ComplexActual:
                                                 C.byref(relres), int(verbose)))
         return out.view(np.complex128), int(steps.value), float(relres.value)
 
+    def solve_many(self, rhs_rows):
+        """A X = B for the complex right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim)), 16 per pass pair over the factor.
+        Returns x in the shape of rhs_rows."""
+        b = np.ascontiguousarray(np.asarray(rhs_rows, dtype=np.complex128))
+        if b.ndim != 2:
+            raise StrError("solve_many expects an array of shape (nrhs, ndim)")
+        nrhs, n = b.shape
+        x = np.zeros_like(b)
+        _check(_L().rh_clinsolver_solve_many(self._h, _ptr(x.view(np.float64)), _ptr(b.view(np.float64)), n, nrhs))
+        return x
+
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+        """solve_updated for the complex right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim), as solve_many takes them), 16 per
+        blocked pass pair, every column its own iteration in complex arithmetic.  Returns (x, steps, relres) with x in the shape of
+        rhs_rows and one entry of steps and relres per right-hand side; raises StrError("Error(2): ...") when any of them did not reach
+        the tolerance."""
+        b = np.ascontiguousarray(np.asarray(rhs_rows, dtype=np.complex128))
+        if b.ndim != 2:
+            raise StrError("solve_updated_many expects an array of shape (nrhs, ndim)")
+        nrhs, n = b.shape
+        x = np.zeros_like(b)
+        steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
+        _check(_L().rh_clinsolver_solve_updated_many(self._h, _ptr(x.view(np.float64)), mat._h, _ptr(b.view(np.float64)), n, nrhs, float(rel_tol), int(max_steps),
+                                                     _ptr(steps), _ptr(relres), int(verbose)))
+        return x, steps, relres
+
     def outputs(self):
         """determinant = determinant_coefficient x 10^determinant_exponent (complex_solver_umfpack.rs:411-414), rcond, perturbed pivots"""
         dr, di, de, rc, npv = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int32()
@@ -747,6 +775,14 @@ class ComplexLinSolver:
     def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
         """extension of the HIPMF backend, see `actual.solve_updated`"""
         return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
+
+    def solve_many(self, rhs_rows):
+        """extension of the HIPMF backend, see `actual.solve_many`"""
+        return self.actual.solve_many(rhs_rows)
+
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+        """extension of the HIPMF backend, see `actual.solve_updated_many`"""
+        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose)
 
 
 def handle_hipmf_error_code(code):

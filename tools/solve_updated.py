@@ -30,7 +30,17 @@ alpha = 2.6811, beta = 3.0504, factorised at h0 = 1; per step-size change h0 -> 
 complex_solver_hipmf_solve_updated_device, the median wall time of a call (device-resident x, rhs and values), the time per step and its
 split into pass pair / SpMV / Arnoldi kernels (HIP events, calls of their own), and the median wall time of
 complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve with the same new values on a second handle (host pointers: the complex
-C-ABI has no device entry points for them) -- the parent commit's only way.  All medians come from the same run."""
+C-ABI has no device entry points for them) -- the parent commit's only way.  All medians come from the same run.
+
+    python tools/solve_updated.py --complex --nrhs N [--out profiles/r13_solve_updated_complex_many.txt]
+
+The complex block form (profiles/r13_solve_updated_complex_many.txt): the same grid and factor, h0 -> h0/2, N random device-resident
+complex columns, three median wall times from the same run:
+    (a) ONE complex_solver_hipmf_solve_updated_many_device call,
+    (b) N complex_solver_hipmf_solve_updated_device calls on the same columns (that code is not touched by the block form),
+    (c) complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve_many(nrhs = N) on a second handle (host pointers),
+with the per-column step counts, UPDATED_STEPS (blocked pass pairs), UPDATED_COLUMN_STEPS and the split of (a) into pass pair / SpMV /
+Arnoldi kernels (HIP events, calls of their own).  The figures of merit are (a)/N, (b)/N and (c)/N."""
 import argparse
 import os
 import sys
@@ -165,15 +175,13 @@ def run_many(name, n, rp, ci, v, args, out):
     alt.close()
 
 
-def run_complex(args, out):
-    import ctypes as C
-
+def complex_grid(nx, ny):
+    """(library, n, values(h) interleaved, two handles factorised at h = 1, L) for K(h) = (alpha + i beta) / h I + L on the nx x ny grid"""
     import scipy.sparse as sp
 
     from russell_amd._capi import load
 
     lib = load()
-    nx = ny = 500
     alpha, beta = 2.6811, 3.0504
     T = lambda m: sp.diags([-np.ones(m - 1), 2.0 * np.ones(m), -np.ones(m - 1)], [-1, 0, 1])
     L = sp.csr_matrix(sp.kron(sp.identity(ny), T(nx)) + sp.kron(T(ny), sp.identity(nx)))
@@ -192,6 +200,15 @@ def run_complex(args, out):
         assert lib.complex_solver_hipmf_initialize(h, 0, 1, -1.0, -1, 0, 0, n, rp, ci, v0.ctypes.data) == 0
         assert lib.complex_solver_hipmf_factorize(h, None, None, None, None, None, None, None, 0, 0, v0) == 0
         handles.append(h)
+    return lib, n, values, handles, L
+
+
+def run_complex(args, out):
+    import ctypes as C
+
+    nx = ny = 500
+    lib, n, values, handles, L = complex_grid(nx, ny)
+    v0 = values(1.0)
     s, alt = handles
     counter = lambda which: int(lib.complex_solver_hipmf_get_counter(s, which))
     rng = np.random.default_rng(5)
@@ -238,6 +255,72 @@ def run_complex(args, out):
         lib.complex_solver_hipmf_drop(h)
 
 
+def run_complex_many(args, out):
+    import ctypes as C
+
+    nx = ny = 500
+    nrhs = args.nrhs
+    lib, n, values, handles, L = complex_grid(nx, ny)
+    v0, v1 = values(1.0), values(0.5)
+    s, alt = handles
+    counter = lambda which: int(lib.complex_solver_hipmf_get_counter(s, which))
+    rng = np.random.default_rng(5)
+    B = np.ascontiguousarray(rng.standard_normal((nrhs, 2 * n)))  # rows: the columns, n interleaved complex numbers each
+    col = 16 * n  # bytes of a column
+    d_x, d_b, d_v = (lib.hipmf_device_malloc(col * nrhs), lib.hipmf_device_malloc(col * nrhs), lib.hipmf_device_malloc(8 * v0.size))
+    assert d_x and d_b and d_v
+    assert lib.hipmf_memcpy_h2d(d_b, B.ctypes.data_as(C.c_void_p), B.nbytes) == 0
+    assert lib.hipmf_memcpy_h2d(d_v, v1.ctypes.data_as(C.c_void_p), v1.nbytes) == 0
+    istats, dstats = np.zeros(16, np.int64), np.zeros(16)
+    assert lib.complex_solver_hipmf_get_stats(s, istats, dstats) == 0
+    out("complex shifted grid %d x %d, h0 -> h0/2: n = %d complex, nnz = %d complex, real-equivalent factor %.0f MB, max_front %d; %d columns, tolerance %.0e, restart 30" %
+        (nx, ny, n, L.nnz, 8e-6 * (istats[4] + istats[5]), istats[6], nrhs, args.tol))
+    res = {}
+    steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
+
+    def blocked():
+        res["a"] = lib.complex_solver_hipmf_solve_updated_many_device(s, d_x, d_b, nrhs, n, d_v, 0, args.tol, 0, steps.ctypes.data, relres.ctypes.data)
+
+    def looped():
+        r = []
+        for c in range(nrhs):
+            st, rel = C.c_int32(0), C.c_double(0.0)
+            code = lib.complex_solver_hipmf_solve_updated_device(s, d_x + col * c, d_b + col * c, d_v, 0, args.tol, 0, C.byref(st), C.byref(rel))
+            r.append((st.value, rel.value, code))
+        res["b"] = r
+    os.environ.pop("HIPMF_UPDATED_TIMING", None)
+    a_med, a_lo, a_hi = timed(blocked, args.reps, args.warmup)
+    pairs, colsteps, blocks, basis = counter(28), counter(35), counter(34), counter(36)  # UPDATED_STEPS, _COLUMN_STEPS, _BLOCKS, _BLOCK_BASIS_BYTES
+    a_steps, a_rel = steps.copy(), relres.copy()
+    b_med, b_lo, b_hi = timed(looped, args.reps, args.warmup)
+    os.environ["HIPMF_UPDATED_TIMING"] = "1"
+    parts = []
+    for _ in range(3):
+        blocked()
+        parts.append([counter(k) / 1e3 for k in (31, 32, 33)])  # HIPMF_COUNTER_UPDATED_PRECOND_US / _SPMV_US / _ARNOLDI_US
+    os.environ.pop("HIPMF_UPDATED_TIMING", None)
+    parts = np.median(np.array(parts), axis=0)
+    X = np.zeros_like(B)
+
+    def alternative():
+        assert lib.complex_solver_hipmf_factorize_mapped(alt, None, None, None, None, 0, v1) == 0
+        assert lib.complex_solver_hipmf_solve_many(alt, X.reshape(-1), B.reshape(-1), nrhs, n, 0) == 0
+    c_med, c_lo, c_hi = timed(alternative, args.reps, args.warmup)
+    out("  %9s %9s | %9s %9s | %9s %9s | %7s | %6s %8s | %8s %8s %8s" % ("(a) ms", "(a)/N", "(b) ms", "(b)/N", "(c) ms", "(c)/N", "(a)/(b)", "pairs", "colsteps", "passpair",
+                                                                        "spmv", "arnoldi"))
+    out("  %9.3f %9.3f | %9.3f %9.3f | %9.3f %9.3f | %7.3f | %6d %8d | %8.3f %8.3f %8.3f" %
+        (a_med, a_med / nrhs, b_med, b_med / nrhs, c_med, c_med / nrhs, a_med / b_med, pairs, colsteps, parts[0], parts[1], parts[2]))
+    out("      status %d / %s, max relres %.1e / %.1e, complex arithmetic %d; %d block(s), block bases %.0f MB; (a) %.3f-%.3f, (b) %.3f-%.3f, (c) %.3f-%.3f ms" %
+        (res["a"], sorted(set(r[2] for r in res["b"])), float(np.max(a_rel)), max(r[1] for r in res["b"]), counter(37), blocks, 1e-6 * basis, a_lo, a_hi, b_lo, b_hi,
+         c_lo, c_hi))
+    out("      steps per column (a): %s" % " ".join(str(int(k)) for k in a_steps))
+    out("      steps per column (b): %s" % " ".join(str(r[0]) for r in res["b"]))
+    for p_ in (d_x, d_b, d_v):
+        lib.hipmf_device_free(p_)
+    for h in handles:
+        lib.complex_solver_hipmf_drop(h)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--complex", action="store_true", help="the complex form on the 500 x 500 complex shifted grid (see the module docstring)")
@@ -254,7 +337,11 @@ def main():
     def out(line):
         print(line, flush=True)
         lines.append(line)
-    if args.complex:
+    if args.complex and args.nrhs > 0:
+        out("(a) one complex_solver_hipmf_solve_updated_many_device call, (b) %d complex_solver_hipmf_solve_updated_device calls, (c) complex_solver_hipmf_factorize_mapped + "
+            "complex_solver_hipmf_solve_many(nrhs = %d), one MI355X; median of %d after %d warm-up" % (args.nrhs, args.nrhs, args.reps, args.warmup))
+        run_complex_many(args, out)
+    elif args.complex:
         out("complex_solver_hipmf_solve_updated_device against complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve, one MI355X; "
             "median of %d calls after %d warm-up calls" % (args.reps, args.warmup))
         run_complex(args, out)
