@@ -810,6 +810,20 @@ template <int TS> struct UpdateLdsT {
 };
 typedef UpdateLdsT<UPD_T> UpdateLds;
 
+// Tiles of a front in ONE trailing-update launch of step k0, the look-ahead piece not counted: the `ntiles` of update_body, whose task
+// number t_in == ntiles is the look-ahead piece (part_in: as update_body's; the host plans count the same way).
+template <bool SYM, int TS> __device__ __forceinline__ int update_ntiles(const FrontDesc &fd, const int32_t k0, const int part_in) {
+    const int part = part_in & 3;
+    const int f = fd.p + fd.m;
+    const int nb = (fd.p - k0) < NB ? (fd.p - k0) : NB;
+    const int base = k0 + nb;
+    const int ntF = (f - base + TS - 1) / TS, ntE = (base + TS - 1) / TS, nt = ntF + ntE;
+    const bool narrow = (k0 / NB) % fd.ugroup < fd.ugroup - 1 && fd.p - base > 0;
+    const int ntiles_all = SYM ? (narrow ? nt : ntF * (ntF + 1) / 2 + ntF * ntE) : (narrow ? 2 * nt : nt * nt);
+    if (SYM || part == 0 || narrow) return part == 2 ? 0 : ntiles_all; // (a narrow step belongs to part 1 as a whole)
+    return part == 1 ? 2 * nt - 1 : (nt - 1) * (nt - 1);
+}
+
 // One tile (t < ntiles) or the look-ahead piece (t == ntiles) of the trailing update of step k0 of the front in `slot`.
 // part (LU instances, full steps only): 0 = every tile; 1 = the tiles of the first block column and block row (what the next two panels
 // and the look-ahead touch: the "critical strips") + the look-ahead piece; 2 = all other tiles.  A full step split this way runs its
@@ -852,7 +866,7 @@ __device__ __forceinline__ void update_body(UpdateLdsT<TS> &sh, const int slot, 
     const bool split = !SYM && part != 0 && !narrow; // this front's step is a full one and the launch carries one part of it
     const int ntiles_all = SYM ? (narrow ? nt : ntri + ntF * ntE) : (narrow ? 2 * nt : nt * nt);
     // tiles of this front in THIS launch (the host counts the same way): a narrow step belongs to part 1 as a whole
-    const int ntiles = !split ? (part == 2 ? 0 : ntiles_all) : (part == 1 ? 2 * nt - 1 : (nt - 1) * (nt - 1));
+    const int ntiles = update_ntiles<SYM, TS>(fd, k0, part_in);
     // index of the tile in the full enumeration
     int t = t_in;
     if (split && t_in < ntiles) {
@@ -1146,18 +1160,41 @@ __device__ __forceinline__ void update_body(UpdateLdsT<TS> &sh, const int slot, 
 #else
 #define HIPMF_UPD32_BOUNDS __launch_bounds__(64, HIPMF_UPD32_WAVES)
 #endif
+// Which piece of a trailing-update launch workgroup g is.  The look-ahead pieces are the longest serial pieces of a step (one wavefront:
+// update of the next diagonal tile, then tile_lu32) and workgroups start in index order, so they LEAD the launch: workgroups
+// 0 .. nfollow - 1 are the look-ahead pieces of slots 0 .. nfollow - 1 (the fronts are sorted by pivots, non-increasing: the ones another
+// step follows are a prefix of the slots), the tiles of all fronts come after them in slot order and `pfx` counts tiles only.  As the last
+// workgroup of its front's range a look-ahead piece of a launch with more workgroups than are resident started in the last round and
+// its whole chain ran as a tail behind the tiles.  The order is free: the look-ahead piece reads the corner of the trailing matrix that
+// tile (0, 0) leaves alone and panel rows / columns that no tile writes, and it writes the other half of the dws double buffer.
+// nfollow == 0 (HIPMF_UPD_LA_FIRST=0, the split step's part 2): `pfx` counts the look-ahead piece as the last task of its front.
+// Returns update_body's task number (t == ntiles: the look-ahead piece); gshift: index of the front's first tile in the launch, mod 8.
+template <bool SYM, int TS>
+__device__ __forceinline__ int update_task(const int32_t *__restrict__ pfx, const int nactive, const FrontDesc *__restrict__ LFD, const int g, const int nfollow,
+                                           const int32_t k0, const int part, const Pfx4 q4, FrontDesc &fd, int &slot, int &gshift) {
+    if (g < nfollow) { // (no prefix word on this path: the slot is the index)
+        slot = g, gshift = 0;
+        fd = LFD[slot];
+        return update_ntiles<SYM, TS>(fd, k0, part);
+    }
+    int pfx_slot;
+    fd = load_front_pfx(pfx, nactive, LFD, g - nfollow, q4, slot, pfx_slot); // (LFD: the descriptors of the level's tiled fronts in slot order)
+    gshift = (pfx_slot + nfollow) & 7;
+    return g - nfollow - pfx_slot;
+}
+
 template <bool SYM, bool PAIRED = false>
 __global__ void HIPMF_UPD_BOUNDS k_update(const int32_t *__restrict__ pfx, int32_t nactive, const FrontDesc *__restrict__ LFD,
                                                 int32_t k0, double *__restrict__ pool,
                                                 double *__restrict__ dws, int32_t dws_stride, int32_t *__restrict__ lperm,
                                                 const unsigned long long *__restrict__ anorm_bits, double pivot_eps, FactorInfo *info,
-                                                double *__restrict__ diag, int32_t part, Pfx4 q4) {
+                                                double *__restrict__ diag, int32_t part, Pfx4 q4, int32_t nfollow) {
     __shared__ UpdateLds sh;
-    int pfx_slot, slot;
-    FrontDesc fd = load_front_pfx(pfx, nactive, LFD, blockIdx.x, q4, slot, pfx_slot); // (LFD: the descriptors of the level's tiled fronts in slot order)
-    const int t = blockIdx.x - pfx_slot;
+    int slot, gshift;
+    FrontDesc fd;
+    const int t = update_task<SYM, UPD_T>(pfx, nactive, LFD, blockIdx.x, nfollow, k0, SYM ? 0 : part, q4, fd, slot, gshift);
     fd_resident(fd);
-    update_body<SYM, false, UPD_T, PAIRED>(sh, slot, t, fd, k0, pool, dws, dws_stride, lperm, anorm_bits, pivot_eps, info, diag, SYM ? 0 : part, pfx_slot & 7);
+    update_body<SYM, false, UPD_T, PAIRED>(sh, slot, t, fd, k0, pool, dws, dws_stride, lperm, anorm_bits, pivot_eps, info, diag, SYM ? 0 : part, gshift);
 }
 
 // the same with 32 x 32 tiles, one wavefront per tile (levels whose largest tiled front has at most Solver::upd32_max_front rows)
@@ -1166,11 +1203,11 @@ __global__ void HIPMF_UPD32_BOUNDS k_update32(const int32_t *__restrict__ pfx, i
                                                  int32_t k0, double *__restrict__ pool,
                                                  double *__restrict__ dws, int32_t dws_stride, int32_t *__restrict__ lperm,
                                                  const unsigned long long *__restrict__ anorm_bits, double pivot_eps, FactorInfo *info,
-                                                 double *__restrict__ diag, Pfx4 q4) {
+                                                 double *__restrict__ diag, Pfx4 q4, int32_t nfollow) {
     __shared__ UpdateLdsT<UPD_T_SMALL> sh;
-    int pfx_slot, slot;
-    FrontDesc fd = load_front_pfx(pfx, nactive, LFD, blockIdx.x, q4, slot, pfx_slot);
-    const int t = blockIdx.x - pfx_slot;
+    int slot, gshift;
+    FrontDesc fd;
+    const int t = update_task<SYM, UPD_T_SMALL>(pfx, nactive, LFD, blockIdx.x, nfollow, k0, 0, q4, fd, slot, gshift);
     fd_resident(fd);
     update_body<SYM, false, UPD_T_SMALL, PAIRED>(sh, slot, t, fd, k0, pool, dws, dws_stride, lperm, anorm_bits, pivot_eps, info, diag);
 }

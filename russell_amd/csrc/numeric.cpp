@@ -346,6 +346,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
     if (const char *e = getenv("HIPMF_EA_LDS")) use_ea_lds = atoi(e) != 0;
     if (const char *e = getenv("HIPMF_EA_LU")) use_ea_lu = atoi(e) != 0;
     if (const char *e = getenv("HIPMF_UPD_XCD")) upd_xcd = atoi(e) != 0;
+    if (const char *e = getenv("HIPMF_UPD_LA_FIRST")) upd_la_first = atoi(e) != 0;
     if (const char *e = getenv("HIPMF_MID_LU_SPLIT")) mid_lu_split = atoi(e) != 0;
     if (const char *e = getenv("HIPMF_MID_FRONT")) use_mid = atoi(e) != 0;
     if (const char *e = getenv("HIPMF_MID_MMAX")) mid_mmax = std::max(0, std::min(MID_MMAX, atoi(e)));
@@ -1514,6 +1515,17 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             st.n_panel = (int32_t)acc;
             st.pfx_update = (int64_t)tasks.size();
             acc = 0;
+            // The look-ahead pieces lead the launch (update_task, kernels_factor.hpp): the prefix then counts tiles only.  The fronts are
+            // sorted by pivots, so the ones another step follows are a prefix of the slots.  (k_bstep / k_bstep32 of the opt-in
+            // block-inverse step read the same prefix and carry a look-ahead piece of the same kind: they keep the old order -- measured
+            // slower than the two-launch step and off by default, a reorder would want a measurement of its own.)
+            const bool la_first = upd_la_first && (S.sym_mode || !use_binv);
+            int32_t nfollow_all = 0;
+            while (nfollow_all < st.nactive && S.npiv(big[nfollow_all]) > k0 + NB) nfollow_all++;
+            for (int32_t a = nfollow_all; a < st.nactive; a++)
+                if (S.npiv(big[a]) > k0 + NB) return ERROR_HIPMF_SYMBOLIC; // (not a prefix: the level's fronts are not sorted)
+            st.nfollow = la_first ? nfollow_all : 0;
+            const int64_t la_own = la_first ? 0 : 1; // the look-ahead piece as the last task of its front's range
             for (int32_t a = 0; a < st.nactive; a++) {
                 tasks.push_back((int32_t)acc);
                 if (a >= 1 && a <= 3) st.upfx[a - 1] = (int32_t)acc;
@@ -1525,12 +1537,12 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
                 const int32_t G = update_group(S.fsize(big[a]));
                 const bool narrow = follow && ((k0 / NB) % G) != G - 1; // not the last step of a group: block column + block row only
                 // (symmetric fronts enumerate only the tiles with live entries: lower triangle of F, rows of F x columns of E)
-                if (S.sym_mode) acc += (narrow ? nt : ntF * (ntF + 1) / 2 + ntF * ntE) + (follow ? 1 : 0);
-                else acc += (narrow ? 2 * nt : nt * nt) + (follow ? 1 : 0);
+                if (S.sym_mode) acc += (narrow ? nt : ntF * (ntF + 1) / 2 + ntF * ntE) + (follow ? la_own : 0);
+                else acc += (narrow ? 2 * nt : nt * nt) + (follow ? la_own : 0);
             }
             tasks.push_back((int32_t)acc);
-            if (acc > 0x7fffffffLL) return ERROR_HIPMF_SYMBOLIC;
-            st.n_update = (int32_t)acc;
+            if (acc + st.nfollow > 0x7fffffffLL) return ERROR_HIPMF_SYMBOLIC;
+            st.n_update = (int32_t)acc + st.nfollow;
             // Split this step's update?  LU, 64 x 64 tiles, no active front in a narrow step (the group's last step: every front applies the
             // whole rank-64 update), some front goes on afterwards (there is a panel chain to run beside the bulk), enough workgroups
             // for the bulk to be worth a stream of its own.
@@ -1553,10 +1565,10 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
                             const int64_t fa = S.fsize(big[a]), nba = std::min<int64_t>(NB, S.npiv(big[a]) - k0), basea = k0 + nba;
                             const int64_t nt = (fa - basea + UT - 1) / UT + (basea + UT - 1) / UT;
                             const bool follow = S.npiv(big[a]) > k0 + NB;
-                            acc2 += part == 1 ? (2 * nt - 1) + (follow ? 1 : 0) : (nt - 1) * (nt - 1);
+                            acc2 += part == 1 ? (2 * nt - 1) + (follow ? la_own : 0) : (nt - 1) * (nt - 1);
                         }
                         tasks.push_back((int32_t)acc2);
-                        (part == 1 ? st.n_crit : st.n_rest) = (int32_t)acc2;
+                        (part == 1 ? st.n_crit : st.n_rest) = (int32_t)acc2 + (part == 1 ? st.nfollow : 0);
                     }
                 }
             }
@@ -2325,10 +2337,10 @@ int32_t Solver::run_factor() {
                                    d_pool, d_lperm, d_dws, dws_stride, d_scalar, opt.pivot_epsilon, d_info, d_diag, pre_lu, Pfx4{st.ppfx[0], st.ppfx[1], st.ppfx[2]});
                 if (st.n_update > 0 && L.upd_ts == UPD_T)
                     hipLaunchKernelGGL(k_update<true>, dim3(st.n_update), dim3(256), 0, STREAM, d_tasks + st.pfx_update, st.nactive, lfd, k0,
-                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 0, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]});
+                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 0, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]}, st.nfollow);
                 else if (st.n_update > 0)
                     hipLaunchKernelGGL(k_update32<true>, dim3(st.n_update), dim3(64), 0, STREAM, d_tasks + st.pfx_update, st.nactive, lfd, k0,
-                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]});
+                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]}, st.nfollow);
             } else if (use_binv) {
                 // one launch per step: every tile forms its own rows of W = A inv(D) (kernels_factor_binv.hpp)
                 if (k0 == 0) {
@@ -2351,9 +2363,9 @@ int32_t Solver::run_factor() {
                     HIPC(hipEventRecord((hipEvent_t)ev_pb, STREAM), ERROR_HIP_SYNCHRONIZE);
                     HIPC(hipStreamWaitEvent((hipStream_t)stream4, (hipEvent_t)ev_pb, 0), ERROR_HIP_SYNCHRONIZE);
                     hipLaunchKernelGGL((PZ ? k_update<false, true> : k_update<false, false>), dim3(st.n_crit), dim3(256), 0, STREAM, d_tasks + st.pfx_crit, st.nactive, lfd, k0, d_pool, d_dws,
-                                       dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 1, Pfx4{-1, -1, -1});
+                                       dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 1, Pfx4{-1, -1, -1}, st.nfollow);
                     hipLaunchKernelGGL((PZ ? k_update<false, true> : k_update<false, false>), dim3(st.n_rest), dim3(256), 0, (hipStream_t)stream4, d_tasks + st.pfx_rest, st.nactive, lfd, k0,
-                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 2, Pfx4{-1, -1, -1});
+                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, 2, Pfx4{-1, -1, -1}, 0);
                     HIPC(hipEventRecord((hipEvent_t)ev_rest, (hipStream_t)stream4), ERROR_HIP_SYNCHRONIZE);
                     rest_pending = true;
                     launches++;
@@ -2364,10 +2376,10 @@ int32_t Solver::run_factor() {
                         rest_pending = false;
                     }
                     hipLaunchKernelGGL((PZ ? k_update<false, true> : k_update<false, false>), dim3(st.n_update), dim3(256), 0, STREAM, d_tasks + st.pfx_update, st.nactive, lfd, k0,
-                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, upd_xcd ? 4 : 0, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]});
+                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, upd_xcd ? 4 : 0, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]}, st.nfollow);
                 } else
                     hipLaunchKernelGGL((PZ ? k_update32<false, true> : k_update32<false, false>), dim3(st.n_update), dim3(64), 0, STREAM, d_tasks + st.pfx_update, st.nactive, lfd, k0,
-                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]});
+                                       d_pool, d_dws, dws_stride, d_lperm, d_scalar, opt.pivot_epsilon, d_info, d_diag, Pfx4{st.upfx[0], st.upfx[1], st.upfx[2]}, st.nfollow);
             }
             launches += 2;
             k0 += NB;

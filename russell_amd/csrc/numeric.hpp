@@ -75,6 +75,7 @@ struct StepPlan {
     int32_t nactive = 0;
     int64_t pfx_panel = 0, pfx_update = 0; // offsets into d_tasks
     int32_t n_panel = 0, n_update = 0;
+    int32_t nfollow = 0; // look-ahead pieces at the head of the update launch (HIPMF_UPD_LA_FIRST=0: none, each is the last task of its front)
     int32_t ppfx[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, upfx[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}; // prefix words of slots 1 .. 3 (kernel arguments of launches with at most four fronts)
     // a full step whose trailing update runs in two launches: the critical strips (first block column / row + look-ahead) on the main
     // stream, the other tiles on a side stream beside the next group's panel steps
@@ -580,6 +581,7 @@ class Solver : public SolverDevice {
     int64_t work_blk_doubles = 0;  // stride between the columns of a blocked solve workspace: work_doubles without the tagged shadow xt
     std::vector<int32_t> sf_host, sfk_host; // (kind, front) per task (single-column lists / blocked list), kept only when tracing
     bool mid_lu_split = false;    // HIPMF_MID_LU_SPLIT=1: the k_front_lu fronts of a level in three launches by LDS class (two or four fronts per CU for the smaller ones); measured slower: 6.58 -> 6.95 ms
+    bool upd_la_first = true;     // HIPMF_UPD_LA_FIRST=0: the look-ahead piece of a front is the last workgroup of its range in a trailing-update launch (1: the look-ahead pieces lead the launch)
     bool upd_xcd = true;          // HIPMF_UPD_XCD=0: the tiles of a full trailing update in plain order (1: whole tile columns per XCD)
     bool use_ea_lds = true;       // HIPMF_EA_LDS=0: LU working blocks go back to k_zero + k_scatter + k_extend_add (read-modify-write per child) instead of k_extend_add_lds
     bool ea_lds_active() const { return use_ea_lds; }
