@@ -184,6 +184,30 @@ int32_t solver_hipmf_solve_sparse_device(struct InterfaceHIPMF *solver, double *
  * vectors, and the rows asked for in a block are its selection.  Accuracy, fallbacks and status codes as solver_hipmf_solve_sparse
  * (ERROR_HIPMF_INVALID_VALUE: nent < 1 or an index out of range); HIPMF_COUNTER_PRUNED_BLOCKS sums over the blocks. */
 int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *solver, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose);
+/* The same for the transposed system (adjoint right-hand sides, rows of the inverse):
+ *   x_sel(k, c) = (A^{-T} B)(sel_idx[k], c)
+ * Arguments, argument rules, status codes and their order exactly as solver_hipmf_solve_sparse / _device.  The blocks travel through the
+ * level-synchronous launches of the blocked transposed solve (solver_hipmf_solve_transpose_many) restricted to the marked fronts; the
+ * non-zeros enter through the column permutation and scaling, the wanted rows leave through the row ones.
+ * ACCURACY: one UNREFINED transposed pass pair per column, as above; the rows returned for a selection are bit for bit the rows of the
+ * sel_idx == NULL result of the same columns.
+ * FALLBACKS: the rules of solver_hipmf_solve_sparse (num_perturbed_pivots > 0, HIPMF_PRUNE_MAX_SHARE, HIPMF_PRUNE_MIN_BYTES); the block is
+ * then expanded and solved by solver_hipmf_solve_transpose_many_device -- refined and rescued as the handle is set up -- and the rows are
+ * selected.  The two thresholds were measured for the ordinary path only (profiles/r09_sparse_rhs.txt); they have NOT been measured for A^T.
+ * L D L^T / symmetric storage (A^T = A): solver_hipmf_solve_sparse itself, bit for bit.  HIPMF_COUNTER_PRUNED_* as there;
+ * HIPMF_COUNTER_PRUNED_TRANSPOSED_BLOCKS counts the blocks that ran the transposed pruned launches.  Speed against the blocked transposed
+ * solve on the expanded block (tools/sparse_rhs.py --transpose, profiles/r16_sparse_rhs_transpose.txt: one run per matrix on one MI355X,
+ * wall-clock medians): 1M-DOF 2D matrix, 1 column / 1 row 0.861 against 1.140 ms, 16 columns / 16 rows 0.968 against 3.405 ms; 100^3
+ * matrix, 1.943 against 4.884 ms and 2.378 against 10.888 ms. */
+int32_t solver_hipmf_solve_sparse_transpose(struct InterfaceHIPMF *solver, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr,
+                                            const int32_t *rhs_idx, const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose);
+int32_t solver_hipmf_solve_sparse_transpose_device(struct InterfaceHIPMF *solver, double *d_x_sel, int32_t ldx, int32_t nrhs, const int32_t *d_rhs_ptr,
+                                                   const int32_t *d_rhs_idx, const double *d_rhs_val, int32_t nsel, const int32_t *d_sel_idx, C_BOOL verbose);
+/* values[e] = (A^{-1})(rows[e], cols[e]) = (A^{-T})(cols[e], rows[e]) through the transposed system: the distinct ROWS are sorted by the
+ * position their unit vector enters the transposed elimination at, taken 16 at a time as unit right-hand sides of
+ * solver_hipmf_solve_sparse_transpose, and the columns asked for in a block are its selection -- one block per 16 rows of the inverse, where
+ * solver_hipmf_inverse_entries needs one per 16 columns.  Arguments, accuracy, fallbacks and status codes as solver_hipmf_inverse_entries. */
+int32_t solver_hipmf_inverse_entries_by_rows(struct InterfaceHIPMF *solver, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose);
 
 /* Solve with NEW matrix values on the KEPT factor (MKL PARDISO's "CGS/CG with the LU of a previous step", iparm[3]): solves
  *   A_new x = rhs,  A_new = the structure given to initialize with the `values` given here,
@@ -350,6 +374,7 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_UPDATED_COLUMN_STEPS 35       /* sum of steps[c] of that call; with UPDATED_STEPS (there: blocked pass pairs, summed over blocks) it says how full they were */
 #define HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES 36  /* device bytes held for the block bases of those calls (UPDATED_BASIS_BYTES stays the single form's) */
 #define HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC 37 /* complex handle: 1 when its last solve_updated / _device orthogonalised in complex arithmetic (0 before the first) */
+#define HIPMF_COUNTER_PRUNED_TRANSPOSED_BLOCKS 38   /* blocks of the last solver_hipmf_solve_sparse_transpose / _device / solver_hipmf_inverse_entries_by_rows (complex: trans = 1, 2) that ran the transposed pruned launches (0: A^T = A or everything fell back) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -454,6 +479,24 @@ int32_t complex_solver_hipmf_solve_many(struct InterfaceComplexHIPMF *solver, do
 int32_t complex_solver_hipmf_solve_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 /* conjugate: 1 -> A^H x = b, 0 -> A^T x = b (the real transposed solve of the real-equivalent system; umfpack_zi_solve's UMFPACK_Aat / UMFPACK_At) */
 int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose);
+/* Sparse right-hand sides and selected solution rows for the complex handle (host pointers):
+ *   x_sel(k, c) = (op(A)^{-1} B)(sel_idx[k], c),   trans = 0: op(A) = A,  1: A^T,  2: A^H
+ * B in compressed-column form as for solver_hipmf_solve_sparse with rhs_val interleaved (re, im) pairs, one per entry of rhs_idx; x_sel
+ * interleaved, column-major, ldx counted in COMPLEX elements (ldx >= nsel, or >= n with sel_idx == NULL).  A complex column is one real
+ * column of the real-equivalent system: a non-zero of row i is rows 2 i, 2 i + 1, a selected row k rows 2 k, 2 k + 1.  A^H is the
+ * transposed real-equivalent system; A^T is A^H with the imaginary parts negated on the way in and out (on the device); a complex-symmetric
+ * handle (lower triangle given) has A^T = A: trans = 1 is trans = 0 there.
+ * ACCURACY: one UNREFINED pass pair per column, selection rows bit for bit those of the sel_idx == NULL result, as for the real handle.
+ * FALLBACKS by the rules of solver_hipmf_solve_sparse (thresholds not measured for A^T / A^H): trans = 0 complex_solver_hipmf_solve_device on
+ * the expanded block, trans = 1, 2 the solve of complex_solver_hipmf_solve_transpose column by column, then the selection.
+ * Status codes and their order as solver_hipmf_solve_sparse; in addition ERROR_HIPMF_INVALID_VALUE for trans outside 0 .. 2.
+ * complex_solver_hipmf_get_counter answers HIPMF_COUNTER_PRUNED_* (fronts of the real-equivalent tree). */
+int32_t complex_solver_hipmf_solve_sparse(struct InterfaceComplexHIPMF *solver, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr,
+                                          const int32_t *rhs_idx, const double *rhs_val, int32_t nsel, const int32_t *sel_idx, int32_t trans, C_BOOL verbose);
+/* values[2 e], values[2 e + 1] = re, im of (A^{-1})(rows[e], cols[e]), e < nent; host arrays, any order, duplicates allowed.  Unit column
+ * cols[e] is real column 2 cols[e] alone, the rows asked for in a block of 16 columns are its selection.  Accuracy, fallbacks and status
+ * codes as solver_hipmf_inverse_entries. */
+int32_t complex_solver_hipmf_inverse_entries(struct InterfaceComplexHIPMF *solver, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose);
 /* Solves exactly as complex_solver_hipmf_solve (the same x, bit for bit), then the error analysis of solver_hipmf_solve_with_error_analysis
  * for the complex system (the argument shape of complex_solver_mumps_solve; RINFOG(4..11) of zmumps_c, interface_complex_mumps.c:243-280,
  * read by complex_solver_mumps.rs:262-268,429-436).  x, rhs: interleaved complex vectors of length 2 n.  |.| is the complex MODULUS

@@ -123,6 +123,11 @@ const char *rh_linsolver_solve_many(void *solver, double *x, const double *rhs, 
 const char *rh_linsolver_solve_sparse(void *solver, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val,
                                       int64_t nsel, const int32_t *sel, int32_t verbose);
 const char *rh_linsolver_inverse_entries(void *solver, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose);
+/* the same through A^T (solver_hipmf_solve_sparse_transpose / solver_hipmf_inverse_entries_by_rows): rows of A^{-T} B; the entries of
+ * A^{-1} with 16 distinct rows per block */
+const char *rh_linsolver_solve_sparse_transpose(void *solver, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val,
+                                                int64_t nsel, const int32_t *sel, int32_t verbose);
+const char *rh_linsolver_inverse_entries_by_rows(void *solver, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose);
 /* extension of the HIPMF backend (solver_hipmf_solve_updated of russell_hipmf.h): A_new x = rhs with the factor of the last factorize as
  * preconditioner; coo: the factorised matrix's structure with new values; "Error(2): ..." when the tolerance was not reached (x: best iterate) */
 const char *rh_linsolver_solve_updated(void *solver, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,

@@ -38,6 +38,10 @@ SYMBOLS = {
     "solver_hipmf_solve_sparse_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                       C.c_void_p, C.c_int32]),
     "solver_hipmf_inverse_entries": (C.c_int32, [C.c_void_p, C.c_int32, i32p, i32p, f64p, C.c_int32]),
+    "solver_hipmf_solve_sparse_transpose": (C.c_int32, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, i32p, f64p, C.c_int32, C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_sparse_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                                C.c_void_p, C.c_int32]),
+    "solver_hipmf_inverse_entries_by_rows": (C.c_int32, [C.c_void_p, C.c_int32, i32p, i32p, f64p, C.c_int32]),
     "solver_hipmf_solve_updated": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                C.c_int32]),
     "solver_hipmf_solve_updated_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
@@ -68,6 +72,8 @@ SYMBOLS = {
     "complex_solver_hipmf_get_determinant": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "complex_solver_hipmf_solve": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32]),
     "complex_solver_hipmf_solve_transpose": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_sparse": (C.c_int32, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, i32p, f64p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_inverse_entries": (C.c_int32, [C.c_void_p, C.c_int32, i32p, i32p, f64p, C.c_int32]),
     "complex_solver_hipmf_solve_with_error_analysis": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_int32]),
     "complex_solver_hipmf_set_value_map": (C.c_int32, [C.c_void_p, C.c_int32, i32p, i32p]),
     "complex_solver_hipmf_factorize_mapped": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -142,10 +142,12 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_transpose_many")
         return x
 
-    def solve_sparse(self, rhs_ptr, rhs_idx, rhs_val, select=None, ldx=None, verbose=False):
+    def solve_sparse(self, rhs_ptr, rhs_idx, rhs_val, select=None, ldx=None, verbose=False, transpose=False):
         """Rows `select` (None: all n) of A^{-1} B for B in compressed-column form (rhs_ptr of nrhs + 1 entries, 0-based row indices ascending
         within a column): an array of shape (nrhs, ldx) whose rows hold the columns' selected entries in their first nsel places (ldx
-        defaults to nsel).  One unrefined pass pair over the marked fronts per block of 16 columns."""
+        defaults to nsel).  One unrefined pass pair over the marked fronts per block of 16 columns.  transpose: A^{-T} B
+        (solver_hipmf_solve_sparse_transpose)."""
+        name = "solver_hipmf_solve_sparse_transpose" if transpose else "solver_hipmf_solve_sparse"
         ptr = np.ascontiguousarray(rhs_ptr, dtype=np.int32)
         idx = np.ascontiguousarray(rhs_idx, dtype=np.int32)
         val = np.ascontiguousarray(rhs_val, dtype=np.float64)
@@ -154,21 +156,23 @@ class Hipmf:
         nsel = self.n if sel is None else int(sel.size)
         ldx = nsel if ldx is None else int(ldx)
         x = np.zeros((max(nrhs, 0), max(ldx, 0)))
-        code = self.lib.solver_hipmf_solve_sparse(self.h, x, ldx, nrhs, ptr, idx, val, nsel, None if sel is None else sel.ctypes.data, int(verbose))
+        code = getattr(self.lib, name)(self.h, x, ldx, nrhs, ptr, idx, val, nsel, None if sel is None else sel.ctypes.data, int(verbose))
         if code != 0:
-            raise self._err(code, "solver_hipmf_solve_sparse")
+            raise self._err(code, name)
         return x
 
-    def inverse_entries(self, rows, cols, verbose=False):
-        """(A^{-1})[rows[e], cols[e]] for every e (any order, duplicates allowed), 16 distinct columns per pruned pass pair."""
+    def inverse_entries(self, rows, cols, verbose=False, by_rows=False):
+        """(A^{-1})[rows[e], cols[e]] for every e (any order, duplicates allowed), 16 distinct columns per pruned pass pair; by_rows: 16
+        distinct rows per transposed pruned pass pair (solver_hipmf_inverse_entries_by_rows)."""
+        name = "solver_hipmf_inverse_entries_by_rows" if by_rows else "solver_hipmf_inverse_entries"
         r = np.ascontiguousarray(rows, dtype=np.int32)
         c = np.ascontiguousarray(cols, dtype=np.int32)
         if r.shape != c.shape or r.ndim != 1:
             raise ValueError("inverse_entries expects two index vectors of equal length, got %r and %r" % (r.shape, c.shape))
         v = np.zeros(r.size)
-        code = self.lib.solver_hipmf_inverse_entries(self.h, int(r.size), r, c, v, int(verbose))
+        code = getattr(self.lib, name)(self.h, int(r.size), r, c, v, int(verbose))
         if code != 0:
-            raise self._err(code, "solver_hipmf_inverse_entries")
+            raise self._err(code, name)
         return v
 
     def solve_updated(self, rhs, values, mapped=False, rel_tol=0.0, max_steps=0, verbose=False):
@@ -224,7 +228,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -321,11 +325,12 @@ class Hipmf:
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_transpose_many_device")
 
-    def solve_sparse_device(self, d_x_sel, ldx, nrhs, d_rhs_ptr, d_rhs_idx, d_rhs_val, nsel, d_sel_idx=None):
+    def solve_sparse_device(self, d_x_sel, ldx, nrhs, d_rhs_ptr, d_rhs_idx, d_rhs_val, nsel, d_sel_idx=None, transpose=False):
         """solve_sparse with every array resident on the device (d_sel_idx None: all n rows)"""
-        code = self.lib.solver_hipmf_solve_sparse_device(self.h, d_x_sel, int(ldx), int(nrhs), d_rhs_ptr, d_rhs_idx, d_rhs_val, int(nsel), d_sel_idx, 0)
+        name = "solver_hipmf_solve_sparse_transpose_device" if transpose else "solver_hipmf_solve_sparse_device"
+        code = getattr(self.lib, name)(self.h, d_x_sel, int(ldx), int(nrhs), d_rhs_ptr, d_rhs_idx, d_rhs_val, int(nsel), d_sel_idx, 0)
         if code != 0:
-            raise self._err(code, "solver_hipmf_solve_sparse_device")
+            raise self._err(code, name)
 
     def solve_updated_device(self, d_x, d_rhs, d_values, mapped=False, rel_tol=0.0, max_steps=0):
         """solve_updated with x, rhs and values resident on the device; returns (steps, relres, status)"""

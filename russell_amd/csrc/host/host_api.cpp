@@ -746,6 +746,8 @@ struct Backend {
     decltype(&solver_hipmf_solve_many) solve_many = nullptr;
     decltype(&solver_hipmf_solve_sparse) solve_sparse = nullptr;
     decltype(&solver_hipmf_inverse_entries) inverse_entries = nullptr;
+    decltype(&solver_hipmf_solve_sparse_transpose) solve_sparse_t = nullptr;
+    decltype(&solver_hipmf_inverse_entries_by_rows) inverse_entries_by_rows = nullptr;
     decltype(&solver_hipmf_solve_updated) solve_updated = nullptr;
     decltype(&solver_hipmf_solve_updated_many) solve_updated_many = nullptr;
     decltype(&solver_hipmf_set_value_map) set_value_map = nullptr;
@@ -808,6 +810,8 @@ bool load_backend() {
     BIND(solve_many, "solver_hipmf_solve_many")
     BIND(solve_sparse, "solver_hipmf_solve_sparse")
     BIND(inverse_entries, "solver_hipmf_inverse_entries")
+    BIND(solve_sparse_t, "solver_hipmf_solve_sparse_transpose")
+    BIND(inverse_entries_by_rows, "solver_hipmf_inverse_entries_by_rows")
     BIND(solve_updated, "solver_hipmf_solve_updated")
     BIND(solve_updated_many, "solver_hipmf_solve_updated_many")
     BIND(set_value_map, "solver_hipmf_set_value_map")
@@ -1379,7 +1383,7 @@ StrError SolverHIPMF::solve_many(std::vector<double> &x, const std::vector<doubl
 }
 
 StrError SolverHIPMF::solve_sparse(std::vector<double> &x_sel, const std::vector<int32_t> &ptr, const std::vector<int32_t> &idx, const std::vector<double> &val,
-                                   const std::vector<int32_t> &select, bool verbose) {
+                                   const std::vector<int32_t> &select, bool verbose, bool transpose) {
     if (!factorized) return "the function factorize must be called before solve";
     if (ptr.size() < 2) return "the sparse right-hand side must have at least one column";
     const size_t ncol = ptr.size() - 1, ndim = initialized_ndim;
@@ -1397,21 +1401,23 @@ StrError SolverHIPMF::solve_sparse(std::vector<double> &x_sel, const std::vector
     const size_t nout = select.empty() ? ndim : select.size();
     if (x_sel.size() != nout * ncol) return "the dimension of the array of selected unknown values x is incorrect";
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.solve_sparse((InterfaceHIPMF *)solver, x_sel.data(), (int32_t)nout, (int32_t)ncol, ptr.data(), idx.data(), val.data(),
-                                            (int32_t)select.size(), select.empty() ? nullptr : select.data(), verbose ? 1 : 0);
+    int32_t status = (transpose ? g_backend.solve_sparse_t : g_backend.solve_sparse)((InterfaceHIPMF *)solver, x_sel.data(), (int32_t)nout, (int32_t)ncol, ptr.data(),
+                                                                                     idx.data(), val.data(), (int32_t)select.size(),
+                                                                                     select.empty() ? nullptr : select.data(), verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
 }
 
-StrError SolverHIPMF::inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose) {
+StrError SolverHIPMF::inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose, bool by_rows) {
     if (!factorized) return "the function factorize must be called before solve";
     if (rows.empty() || rows.size() != cols.size()) return "the arrays of row and column indices must have the same, positive length";
     if (values.size() != rows.size()) return "the dimension of the array of values is incorrect";
     for (size_t e = 0; e < rows.size(); e++)
         if (rows[e] < 0 || (size_t)rows[e] >= initialized_ndim || cols[e] < 0 || (size_t)cols[e] >= initialized_ndim) return "an index of an entry of the inverse is outside range";
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.inverse_entries((InterfaceHIPMF *)solver, (int32_t)rows.size(), rows.data(), cols.data(), values.data(), verbose ? 1 : 0);
+    int32_t status = (by_rows ? g_backend.inverse_entries_by_rows : g_backend.inverse_entries)((InterfaceHIPMF *)solver, (int32_t)rows.size(), rows.data(), cols.data(),
+                                                                                               values.data(), verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -2040,8 +2046,8 @@ const char *rh_linsolver_solve_many(void *h, double *x, const double *rhs, int64
     if (!e) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
-const char *rh_linsolver_solve_sparse(void *h, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val, int64_t nsel,
-                                      const int32_t *sel, int32_t verbose) {
+static const char *linsolver_solve_sparse(void *h, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val, int64_t nsel,
+                                          const int32_t *sel, int32_t verbose, bool transpose) {
     RhSolver *s = (RhSolver *)h;
     SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
     if (!a) return "solve_sparse is only available with Genie::Hipmf";
@@ -2051,19 +2057,33 @@ const char *rh_linsolver_solve_sparse(void *h, double *x_sel, int64_t nx, int64_
     const std::vector<int32_t> ii(idx, idx + nz), ss(sel, sel + (sel ? nsel : 0));
     const std::vector<double> vv(val, val + nz);
     std::vector<double> xx((size_t)nx);
-    StrError e = a->solve_sparse(xx, pp, ii, vv, ss, verbose != 0);
+    StrError e = a->solve_sparse(xx, pp, ii, vv, ss, verbose != 0, transpose);
     if (!e) std::copy(xx.begin(), xx.end(), x_sel);
     return e;
 }
-const char *rh_linsolver_inverse_entries(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose) {
+const char *rh_linsolver_solve_sparse(void *h, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val, int64_t nsel,
+                                      const int32_t *sel, int32_t verbose) {
+    return linsolver_solve_sparse(h, x_sel, nx, ncol, ptr, idx, val, nsel, sel, verbose, false);
+}
+const char *rh_linsolver_solve_sparse_transpose(void *h, double *x_sel, int64_t nx, int64_t ncol, const int32_t *ptr, const int32_t *idx, const double *val, int64_t nsel,
+                                                const int32_t *sel, int32_t verbose) {
+    return linsolver_solve_sparse(h, x_sel, nx, ncol, ptr, idx, val, nsel, sel, verbose, true);
+}
+static const char *linsolver_inverse_entries(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose, bool by_rows) {
     RhSolver *s = (RhSolver *)h;
     SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
     if (!a) return "inverse_entries is only available with Genie::Hipmf";
     const std::vector<int32_t> rr(rows, rows + (nent > 0 ? nent : 0)), cc(cols, cols + (nent > 0 ? nent : 0));
     std::vector<double> vv(rr.size());
-    StrError e = a->inverse_entries(vv, rr, cc, verbose != 0);
+    StrError e = a->inverse_entries(vv, rr, cc, verbose != 0, by_rows);
     if (!e) std::copy(vv.begin(), vv.end(), values);
     return e;
+}
+const char *rh_linsolver_inverse_entries(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose) {
+    return linsolver_inverse_entries(h, values, nent, rows, cols, verbose, false);
+}
+const char *rh_linsolver_inverse_entries_by_rows(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose) {
+    return linsolver_inverse_entries(h, values, nent, rows, cols, verbose, true);
 }
 const char *rh_linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
                                        double *relres, int32_t verbose) {

@@ -215,11 +215,11 @@ class SolverHIPMF : public LinSolTrait {
     StrError solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs);
     // extension: sparse right-hand sides in compressed-column form (ptr: ncol + 1 entries; row indices ascending within a column) and a
     // selection of rows (empty: all of them): x_sel column-major, (select.size() or ndim) x ncol; one unrefined pass pair over the fronts
-    // the non-zeros and the selected rows touch (solver_hipmf_solve_sparse)
+    // the non-zeros and the selected rows touch (solver_hipmf_solve_sparse); transpose: A^{-T} B (solver_hipmf_solve_sparse_transpose)
     StrError solve_sparse(std::vector<double> &x_sel, const std::vector<int32_t> &ptr, const std::vector<int32_t> &idx, const std::vector<double> &val,
-                          const std::vector<int32_t> &select, bool verbose);
-    // extension: values[e] = (A^{-1})(rows[e], cols[e]) (solver_hipmf_inverse_entries)
-    StrError inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose);
+                          const std::vector<int32_t> &select, bool verbose, bool transpose = false);
+    // extension: values[e] = (A^{-1})(rows[e], cols[e]) (solver_hipmf_inverse_entries; by_rows: solver_hipmf_inverse_entries_by_rows)
+    StrError inverse_entries(std::vector<double> &values, const std::vector<int32_t> &rows, const std::vector<int32_t> &cols, bool verbose, bool by_rows = false);
     // extension: A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES on the device
     // (solver_hipmf_solve_updated); mat: the factorised matrix's structure with new values.  Status 2 (not converged) is an error string of
     // its own; x then holds the best iterate.  rel_tol <= 0: 1e-12, max_steps <= 0: 4 x restart; steps / relres may be null.

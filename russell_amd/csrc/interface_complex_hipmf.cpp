@@ -397,6 +397,63 @@ int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *h, do
     });
 }
 
+// Sparse right-hand sides / selected rows for the complex handle (Solver::solve_sparse on the real-equivalent system): a complex column
+// is one real column -- the non-zero (re, im) of row i is rows 2 i, 2 i + 1 (the interleaved values ARE the real values, ascending order is
+// kept), a selected row k rows 2 k, 2 k + 1, and the real x_sel with leading dimension 2 ldx is the interleaved complex result.
+// trans = 2 (A^H) is the transposed real-equivalent system, trans = 1 (A^T) the same with the imaginary parts negated on the way in and
+// out (conj_pairs); a complex-symmetric handle has A^T = A.  The checks come in the order of solver_hipmf_solve_sparse.
+static int32_t c_solve_sparse_body(struct InterfaceComplexHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
+                                   const double *rhs_val, int32_t nsel, const int32_t *sel_idx, int32_t trans, C_BOOL verbose) {
+    if (!h) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x_sel || !rhs_ptr) return ERROR_NULL_POINTER;
+    const int32_t n = h->n;
+    if (trans < 0 || trans > 2 || nrhs < 1 || (sel_idx && nsel < 1)) return ERROR_HIPMF_INVALID_VALUE;
+    if (ldx < (sel_idx ? nsel : n)) return ERROR_HIPMF_INVALID_VALUE;
+    if (rhs_ptr[0] < 0) return ERROR_HIPMF_INVALID_VALUE;
+    for (int32_t c = 0; c < nrhs; c++)
+        if (rhs_ptr[c + 1] < rhs_ptr[c]) return ERROR_HIPMF_INVALID_VALUE;
+    const int64_t e0 = rhs_ptr[0], e1 = rhs_ptr[nrhs];
+    if (e1 > e0 && (!rhs_idx || !rhs_val)) return ERROR_NULL_POINTER;
+    if (2 * (e1 - e0) > 0x7fffffffLL) return ERROR_HIPMF_INVALID_VALUE;
+    std::vector<int32_t> ptr2((size_t)nrhs + 1), idx2((size_t)(2 * (e1 - e0))), sel2;
+    for (int32_t c = 0; c <= nrhs; c++) ptr2[(size_t)c] = (int32_t)(2 * (rhs_ptr[c] - e0));
+    for (int64_t e = e0; e < e1; e++) {
+        const int32_t i = rhs_idx[e];
+        if (i < 0 || i >= n) return ERROR_HIPMF_INVALID_VALUE;
+        idx2[(size_t)(2 * (e - e0))] = 2 * i, idx2[(size_t)(2 * (e - e0) + 1)] = 2 * i + 1;
+    }
+    if (sel_idx) {
+        sel2.resize(2 * (size_t)nsel);
+        for (int32_t k = 0; k < nsel; k++) {
+            if (sel_idx[k] < 0 || sel_idx[k] >= n) return ERROR_HIPMF_INVALID_VALUE;
+            sel2[2 * (size_t)k] = 2 * sel_idx[k], sel2[2 * (size_t)k + 1] = 2 * sel_idx[k] + 1;
+        }
+    }
+    if (trans == 1 && h->sym_lower) trans = 0;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_sparse(x_sel, 2 * (int64_t)ldx, nrhs, ptr2.data(), idx2.data(), rhs_val ? rhs_val + 2 * e0 : nullptr, 2 * nsel,
+                                                sel_idx ? sel2.data() : nullptr, false, false, trans != 0, trans == 1);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("complex_solver_hipmf_solve_sparse: Solution completed (%d column(s), trans = %d, %lld pruned block(s))\n", nrhs, trans, (long long)h->solver.pruned_blocks);
+    return code;
+}
+
+int32_t complex_solver_hipmf_solve_sparse(struct InterfaceComplexHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
+                                          const double *rhs_val, int32_t nsel, const int32_t *sel_idx, int32_t trans, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_sparse_body(h, x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, trans, verbose); });
+}
+
+// entries of the complex inverse: Solver::inverse_entries in its pairs form (unit column c = real column 2 c alone)
+int32_t complex_solver_hipmf_inverse_entries(struct InterfaceComplexHIPMF *h, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        if (!h) return (int32_t)ERROR_NULL_POINTER;
+        h->solver.opt.verbose = verbose == 1;
+        return h->solver.inverse_entries(nent, rows, cols, values, false, true);
+    });
+}
+
 // The complex error analysis (k_zea_rows) reads complex row i from row 2i of the real-equivalent CSR alone: stored entry (i, j) is the
 // adjacent pair (column 2j: +Re a_ij, column 2j+1: -Im a_ij).  build_real_equivalent always writes both, even where Im a_ij = 0, and the
 // solver keeps the pattern it was given; checked once per handle on the device's copy of the pattern and against the value map.
@@ -476,6 +533,11 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
     case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
     case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
+    case HIPMF_COUNTER_PRUNED_FWD_FRONTS: return s.pruned_fwd_fronts;
+    case HIPMF_COUNTER_PRUNED_BWD_FRONTS: return s.pruned_bwd_fronts;
+    case HIPMF_COUNTER_PRUNED_BLOCKS: return s.pruned_blocks;
+    case HIPMF_COUNTER_PRUNED_BYTES: return s.pruned_bytes;
+    case HIPMF_COUNTER_PRUNED_TRANSPOSED_BLOCKS: return s.pruned_transposed_blocks;
     case HIPMF_COUNTER_UPDATED_STEPS: return s.updated_steps;
     case HIPMF_COUNTER_UPDATED_CYCLES: return s.updated_cycles;
     case HIPMF_COUNTER_UPDATED_BASIS_BYTES: return s.updated_basis_bytes();

@@ -513,10 +513,12 @@ int32_t solver_hipmf_solve_transpose_many_device(struct InterfaceHIPMF *h, doubl
 // Sparse right-hand sides / selected rows / entries of the inverse (Solver::solve_sparse, Solver::inverse_entries; MUMPS's ICNTL(20) and
 // ICNTL(30)): one unrefined pass pair over the marked fronts per block of 16 columns.
 static int32_t solve_sparse_body(struct InterfaceHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
-                                 const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose, bool on_device, const char *who) {
+                                 const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose, bool on_device, const char *who,
+                                 bool transposed = false) {
     if (!h) return ERROR_NULL_POINTER;
     h->solver.opt.verbose = verbose == 1;
-    const int32_t code = h->solver.solve_sparse(x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, on_device);
+    // (a symmetric matrix that was expanded to a general one inside the handle, HIPMF_COUNTER_SYM_EXPANDED, still has A^T = A: the ordinary path)
+    const int32_t code = h->solver.solve_sparse(x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, on_device, false, transposed && !h->expanded);
     if (verbose == 1 && code == SUCCESSFUL_EXIT)
         printf("%s: Solution completed (%d column(s), %lld pruned block(s); last block: %lld / %lld fronts forward / backward, share %.3f)\n", who, nrhs,
                (long long)h->solver.pruned_blocks, (long long)h->solver.pruned_fwd_fronts, (long long)h->solver.pruned_bwd_fronts, h->solver.pruned_share_last);
@@ -535,15 +537,38 @@ int32_t solver_hipmf_solve_sparse_device(struct InterfaceHIPMF *h, double *d_x_s
     });
 }
 
+static int32_t inverse_entries_body(struct InterfaceHIPMF *h, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose, bool by_rows,
+                                    const char *who) {
+    if (!h) return ERROR_NULL_POINTER;
+    h->solver.opt.verbose = verbose == 1;
+    // (a symmetric matrix expanded to a general one inside the handle: A^{-1} is symmetric, the rows serve as columns of the ordinary path)
+    const int32_t code = (by_rows && h->expanded) ? h->solver.inverse_entries(nent, cols, rows, values) : h->solver.inverse_entries(nent, rows, cols, values, by_rows);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("%s: %d entr%s completed (%lld pruned block(s))\n", who, nent, nent == 1 ? "y" : "ies", (long long)h->solver.pruned_blocks);
+    return code;
+}
+
 int32_t solver_hipmf_inverse_entries(struct InterfaceHIPMF *h, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose) {
+    return guarded(h, [&]() { return inverse_entries_body(h, nent, rows, cols, values, verbose, false, "solver_hipmf_inverse_entries"); });
+}
+
+// The same through A^T (Solver::solve_sparse with transposed = true, kernels_solve_pruned_transpose.hpp)
+int32_t solver_hipmf_solve_sparse_transpose(struct InterfaceHIPMF *h, double *x_sel, int32_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx,
+                                            const double *rhs_val, int32_t nsel, const int32_t *sel_idx, C_BOOL verbose) {
     return guarded(h, [&]() {
-        if (!h) return (int32_t)ERROR_NULL_POINTER;
-        h->solver.opt.verbose = verbose == 1;
-        const int32_t code = h->solver.inverse_entries(nent, rows, cols, values);
-        if (verbose == 1 && code == SUCCESSFUL_EXIT)
-            printf("solver_hipmf_inverse_entries: %d entr%s completed (%lld pruned block(s))\n", nent, nent == 1 ? "y" : "ies", (long long)h->solver.pruned_blocks);
-        return code;
+        return solve_sparse_body(h, x_sel, ldx, nrhs, rhs_ptr, rhs_idx, rhs_val, nsel, sel_idx, verbose, false, "solver_hipmf_solve_sparse_transpose", true);
     });
+}
+
+int32_t solver_hipmf_solve_sparse_transpose_device(struct InterfaceHIPMF *h, double *d_x_sel, int32_t ldx, int32_t nrhs, const int32_t *d_rhs_ptr,
+                                                   const int32_t *d_rhs_idx, const double *d_rhs_val, int32_t nsel, const int32_t *d_sel_idx, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_sparse_body(h, d_x_sel, ldx, nrhs, d_rhs_ptr, d_rhs_idx, d_rhs_val, nsel, d_sel_idx, verbose, true, "solver_hipmf_solve_sparse_transpose_device", true);
+    });
+}
+
+int32_t solver_hipmf_inverse_entries_by_rows(struct InterfaceHIPMF *h, int32_t nent, const int32_t *rows, const int32_t *cols, double *values, C_BOOL verbose) {
+    return guarded(h, [&]() { return inverse_entries_body(h, nent, rows, cols, values, verbose, true, "solver_hipmf_inverse_entries_by_rows"); });
 }
 
 // Solve with new matrix values on the kept factor (Solver::solve_updated): flexible GMRES on the device, the factor of the last
@@ -705,6 +730,7 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_PRUNED_BWD_FRONTS: return s.pruned_bwd_fronts;
     case HIPMF_COUNTER_PRUNED_BLOCKS: return s.pruned_blocks;
     case HIPMF_COUNTER_PRUNED_BYTES: return s.pruned_bytes;
+    case HIPMF_COUNTER_PRUNED_TRANSPOSED_BLOCKS: return s.pruned_transposed_blocks;
     case HIPMF_COUNTER_UPDATED_STEPS: return s.updated_steps;
     case HIPMF_COUNTER_UPDATED_CYCLES: return s.updated_cycles;
     case HIPMF_COUNTER_UPDATED_BASIS_BYTES: return s.updated_basis_bytes();

@@ -21,6 +21,7 @@
 #include "kernels_solve_transpose.hpp"
 #include "kernels_solve_transpose_blocked.hpp"
 #include "kernels_solve_pruned.hpp"
+#include "kernels_solve_pruned_transpose.hpp"
 #include "kernels_krylov.hpp"
 #include "kernels_krylov_blocked.hpp"
 #include "kernels_krylov_complex.hpp"
@@ -4601,7 +4602,7 @@ int32_t Solver::sp_prepare() {
     return SUCCESSFUL_EXIT;
 }
 
-void Solver::sp_build_lists(const std::vector<int32_t> &fronts, bool forward, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const {
+void Solver::sp_build_lists(const std::vector<int32_t> &fronts, SpShape shape, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const {
     const size_t nl = (size_t)S.nlevels;
     lv.assign(nl, SpLevel());
     buf.clear();
@@ -4630,8 +4631,12 @@ void Solver::sp_build_lists(const std::vector<int32_t> &fronts, bool forward, st
         for (int32_t *q = b; q < e; q++)
             if (S.fsize(*q) > SMALL_F) {
                 const int32_t p = S.npiv(*q), f = S.fsize(*q);
+                if (shape == SP_FORWARD_T) { // (tiles of TR_COLS stored columns of E' over [0, f), every start a multiple of 16)
+                    for (int32_t r0 = 0; r0 < f; r0 += TR_COLS) task(*q, r0, std::min(f, r0 + TR_COLS)), L.pr_cnt++;
+                    continue;
+                }
                 for (int32_t r0 = 0; r0 < p; r0 += SP_ROWS) task(*q, r0, std::min(p, r0 + SP_ROWS)), L.pr_cnt++;
-                if (forward) // (the tiles of the update rows start at p: no tile straddles the pivot block, whose known zeros are skipped)
+                if (shape == SP_FORWARD) // (the tiles of the update rows start at p: no tile straddles the pivot block, whose known zeros are skipped)
                     for (int32_t r0 = p; r0 < f; r0 += SP_ROWS) task(*q, r0, std::min(f, r0 + SP_ROWS)), L.pr_cnt++;
             }
     }
@@ -4679,6 +4684,42 @@ int32_t Solver::run_pruned(double *XP, const std::vector<SpLevel> &fl, const std
     return SUCCESSFUL_EXIT;
 }
 
+// The same for A^T: the forward (U^T) pass over the lists of shape SP_FORWARD_T, the backward (L^T) pass over backward lists -- the
+// blocked transposed kernels on the pruned path's workspace, the two forward kernels that add children's updates with the mark test
+// (kernels_solve_pruned_transpose.hpp).  Nothing of the blocked transposed solve's own buffers (d_work_tb, d_tblk) is touched.
+int32_t Solver::run_pruned_transposed(double *XP, const std::vector<SpLevel> &fl, const std::vector<SpLevel> &bl) {
+    const int64_t xs = S.n;
+    const int32_t *FB = d_sp_fwd.a, *BB = d_sp_bwd.a;
+    const int32_t ep = sp_epoch;
+    auto tasks = [](const int32_t *base, int32_t off) { return reinterpret_cast<const SolveTask *>(base + off); };
+    for (size_t l = 0; l < fl.size(); l++) {
+        const SpLevel &L = fl[l];
+        if (L.small_cnt > 0) {
+            const int32_t ldu = L.pmax | 1;
+            hipLaunchKernelGGL(k_spt_fwd_small, dim3(L.small_cnt), dim3(64), sizeof(double) * (size_t)ldu * (size_t)L.fmax, STREAM, FB + L.small_off, d_fd, d_pool,
+                               d_child, d_rel, d_sp_mark, ep, d_sp_work, XP, xs, ldu);
+        }
+        if (L.va_cnt > 0)
+            hipLaunchKernelGGL(k_spt_assemble, dim3(L.va_cnt), dim3(256), 0, STREAM, tasks(FB, L.va_off), d_fd, d_child, d_rel, d_sp_mark, ep, d_sp_work,
+                               (const double *)XP, xs);
+        if (L.pr_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemm_blk<true>, dim3(L.pr_cnt), dim3(256), 0, STREAM, tasks(FB, L.pr_off), d_fd, d_pool, d_sp_work, XP, xs);
+    }
+    for (size_t l = bl.size(); l-- > 0;) {
+        const SpLevel &L = bl[l];
+        if (L.va_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gather_blk, dim3(L.va_cnt), dim3(256), 0, STREAM, tasks(BB, L.va_off), d_fd, d_rows, d_sp_work, (const double *)XP, xs);
+        if (L.pr_cnt > 0)
+            hipLaunchKernelGGL(k_tr_gemm_blk<false>, dim3(L.pr_cnt), dim3(256), 0, STREAM, tasks(BB, L.pr_off), d_fd, d_pool, d_sp_work, XP, xs);
+        if (L.small_cnt > 0) {
+            const int32_t ldl = L.fmax | 1;
+            hipLaunchKernelGGL(k_tr_bwd_small_blk, dim3(L.small_cnt), dim3(64), sizeof(double) * (size_t)ldl * (size_t)L.pmax, STREAM, BB + L.small_off, d_fd, d_pool,
+                               d_rows, d_lperm, XP, xs, ldl);
+        }
+    }
+    return SUCCESSFUL_EXIT;
+}
+
 // x_sel(k, c) = (A^{-1} B)(sel_idx[k], c), column-major with ldx >= the number of rows returned (nsel, or n when sel_idx == nullptr).
 // Per block of up to SP_KB columns:
 //   mark     forward set = union of the root paths of the fronts of the non-zeros' permuted positions, backward set (once per call) = the
@@ -4692,9 +4733,14 @@ int32_t Solver::run_pruned(double *XP, const std::vector<SpLevel> &fl, const std
 //            permutation and column scaling).  One unrefined pass pair: a residual needs all of x and all of A, which is what pruning avoids
 //            (MUMPS's ICNTL(20) / ICNTL(30) solves are unrefined too).
 // accumulate: pruned_blocks continues to count (inverse_entries calls this once per block of columns).
+// transposed (A^T X = B; a handle with A^T = A runs everything above unchanged): the maps swap roles.  b enters as k_tr_perm_in_cols has
+// it, xp[j] = cs[perm[j]] b[perm[j]] -- a non-zero of row i at sp_ipos_c[i], scaled by cs, and the forward set is marked from there --;
+// x leaves as k_perm_out_cols has it with d_rperm / d_rs -- row k from sp_ipos_r[k], scaled by rs, the backward set marked from there.
+// The passes are run_pruned_transposed, the fallback (same rules; the thresholds have not been measured for A^T) is solve_transpose_many
+// on the expanded block, or solve_transpose column by column for conj_pairs.  conj_pairs: k_spt_conj_in / k_spt_conj_out around a pruned block.
 int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx, const double *rhs_val, int32_t nsel,
-                             const int32_t *sel_idx, bool on_device, bool accumulate) {
-    if (!accumulate) pruned_blocks = 0;
+                             const int32_t *sel_idx, bool on_device, bool accumulate, bool transposed, bool conj_pairs) {
+    if (!accumulate) pruned_blocks = 0, pruned_transposed_blocks = 0;
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x_sel || !rhs_ptr) return ERROR_NULL_POINTER;
@@ -4702,6 +4748,8 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
     if (nrhs < 1 || (sel_idx && nsel < 1)) return ERROR_HIPMF_INVALID_VALUE;
     const int32_t nout = sel_idx ? nsel : n;
     if (ldx < nout) return ERROR_HIPMF_INVALID_VALUE;
+    const bool tr = transposed && !(S.sym_mode || d_tptr);
+    if (conj_pairs && (!tr || on_device)) return ERROR_HIPMF_INVALID_VALUE; // (the sign kernels work on the staged copies of a transposed block)
     DeviceScope dev_scope(device);
     // host copies of the index arrays (the marking runs on the host), validated before anything reads through them
     std::vector<int32_t> ptr_keep, idx_keep, sel_keep;
@@ -4762,6 +4810,11 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
     if (const char *e = getenv("HIPMF_PRUNE_MAX_SHARE")) theta = atof(e);
     if (const char *e = getenv("HIPMF_PRUNE_MIN_BYTES")) min_bytes_1col = atof(e);
     const bool never_pruned = n_perturbed > 0;
+    const std::vector<int32_t> &pos_in = tr ? sp_ipos_c : sp_ipos_r, &pos_out = tr ? sp_ipos_r : sp_ipos_c; // where b enters, where x leaves
+    const int32_t *const d_ipr = d_sp_ipos_r, *const d_ipc = d_sp_ipos_c;
+    const double *const d_rsc = d_rs, *const d_csc = d_cs;
+    const int32_t *d_pos_in = tr ? d_ipc : d_ipr, *d_pos_out = tr ? d_ipr : d_ipc;
+    const double *d_sc_in = tr ? d_csc : d_rsc, *d_sc_out = tr ? d_rsc : d_csc;
     // the backward set and its lists: once per call
     std::vector<int32_t> bset, fset, bbuf, fbuf;
     std::vector<SpLevel> blv, flv;
@@ -4776,10 +4829,10 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
             b_pf = sp_total_pf;
         } else {
             for (int32_t k = 0; k < nsel; k++)
-                for (int32_t s = S.sn_of[(size_t)sp_ipos_c[(size_t)hs[k]]]; s >= 0 && sp_stamp_b[(size_t)s] != be; s = S.sn_parent[(size_t)s])
+                for (int32_t s = S.sn_of[(size_t)pos_out[(size_t)hs[k]]]; s >= 0 && sp_stamp_b[(size_t)s] != be; s = S.sn_parent[(size_t)s])
                     sp_stamp_b[(size_t)s] = be, bset.push_back(s), b_pf += (double)S.npiv(s) * (double)S.fsize(s);
         }
-        sp_build_lists(bset, false, bbuf, blv);
+        sp_build_lists(bset, SP_BACKWARD, bbuf, blv);
         HIPC(d_sp_bwd.need(std::max<size_t>(bbuf.size(), 1)), ERROR_HIP_MALLOC);
         if (!bbuf.empty()) HIPC(hipMemcpyAsync(d_sp_bwd.a, bbuf.data(), sizeof(int32_t) * bbuf.size(), hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
         bwd_ready = true;
@@ -4801,7 +4854,7 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
             fe = ++sp_epoch;
             fset.clear();
             for (int32_t e = hp[j0]; e < hp[j0 + nk]; e++)
-                for (int32_t s = S.sn_of[(size_t)sp_ipos_r[(size_t)hi[e]]]; s >= 0 && sp_stamp_f[(size_t)s] != fe; s = S.sn_parent[(size_t)s])
+                for (int32_t s = S.sn_of[(size_t)pos_in[(size_t)hi[e]]]; s >= 0 && sp_stamp_f[(size_t)s] != fe; s = S.sn_parent[(size_t)s])
                     sp_stamp_f[(size_t)s] = fe, fset.push_back(s), f_pf += (double)S.npiv(s) * (double)S.fsize(s);
             pruned_share_last = sp_total_pf > 0.0 ? (f_pf + b_pf) / (2.0 * sp_total_pf) : 0.0;
             if (pruned_share_last > theta) pruned = false;
@@ -4810,7 +4863,7 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
             if (theta < 1.0 && nk == 1 && 16.0 * sp_total_pf < min_bytes_1col) pruned = false;
         }
         if (pruned) {
-            sp_build_lists(fset, true, fbuf, flv);
+            sp_build_lists(fset, tr ? SP_FORWARD_T : SP_FORWARD, fbuf, flv);
             // k_sp_begin's list behind the forward lists: the forward set (marked), then the fronts of the backward set alone (~s)
             const size_t begin_off = fbuf.size();
             for (int32_t s : fset) fbuf.push_back(s);
@@ -4822,13 +4875,15 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
             HIPC(hipMemcpyAsync(d_sp_fwd.a, fbuf.data(), sizeof(int32_t) * fbuf.size(), hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
             double *XP = d_sp_xp;
             hipLaunchKernelGGL(k_sp_begin, dim3((unsigned)begin_cnt), b256, 0, STREAM, d_sp_fwd.a + begin_off, d_fd, d_sp_mark, fe, XP, (int64_t)n);
+            if (nz > 0 && conj_pairs) // (d_val is the staged copy: conj_pairs comes with host arrays)
+                hipLaunchKernelGGL(k_spt_conj_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols.ptr[0], cols.ptr[nk], d_idx, d_sp_val.a);
             if (nz > 0)
-                hipLaunchKernelGGL(k_sp_scatter_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols, nk, d_idx, d_val, (const int32_t *)d_sp_ipos_r, (const double *)d_rs, XP,
-                                   (int64_t)n);
-            code = run_pruned(XP, flv, blv);
+                hipLaunchKernelGGL(k_sp_scatter_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols, nk, d_idx, d_val, d_pos_in, d_sc_in, XP, (int64_t)n);
+            code = tr ? run_pruned_transposed(XP, flv, blv) : run_pruned(XP, flv, blv);
             if (code != SUCCESSFUL_EXIT) return code;
-            hipLaunchKernelGGL(k_sp_gather_out, gsel, b256, 0, STREAM, nout, d_sel, (const int32_t *)d_sp_ipos_c, (const double *)d_cs, (const double *)XP, (int64_t)n,
-                               out_blk, ostr, nk);
+            hipLaunchKernelGGL(k_sp_gather_out, gsel, b256, 0, STREAM, nout, d_sel, d_pos_out, d_sc_out, (const double *)XP, (int64_t)n, out_blk, ostr, nk);
+            if (conj_pairs) hipLaunchKernelGGL(k_spt_conj_out, gsel, b256, 0, STREAM, nout, d_sel, out_blk, ostr, nk);
+            if (tr) pruned_transposed_blocks++;
             pruned_fwd_fronts = (int64_t)fset.size(), pruned_bwd_fronts = (int64_t)bset.size();
             pruned_bytes = (int64_t)(8.0 * (f_pf + b_pf));
             pruned_blocks++;
@@ -4840,7 +4895,7 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
             if (nz > 0)
                 hipLaunchKernelGGL(k_sp_scatter_in, dim3((nz + 255) / 256), b256, 0, STREAM, cols, nk, d_idx, d_val, (const int32_t *)nullptr, (const double *)nullptr, B,
                                    (int64_t)n);
-            code = solve(X, B, nk, n, true);
+            code = !tr ? solve(X, B, nk, n, true) : (conj_pairs ? solve_transpose(X, B, nk, n, true, true) : solve_transpose_many(X, B, nk, n, true));
             if (code != SUCCESSFUL_EXIT) return code;
             hipLaunchKernelGGL(k_sp_gather_out, gsel, b256, 0, STREAM, nout, d_sel, (const int32_t *)nullptr, (const double *)nullptr, (const double *)X, (int64_t)n, out_blk,
                                ostr, nk);
@@ -4864,13 +4919,16 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
 // values[e] = (A^{-1})(rows[e], cols[e]): the distinct columns sorted by the position their unit vector enters the elimination at
 // (neighbours share most of their root paths), blocks of at most SP_KB of them, right-hand sides = unit vectors, selected rows = the union
 // of the rows asked for in the block; one solve_sparse per block.
-int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values) {
-    pruned_blocks = 0;
+// by_rows: the mirror image through A^T -- (A^{-1})(r, c) = (A^{-T})(c, r): the distinct ROWS sorted by the position their unit vector
+// enters the transposed elimination at (sp_ipos_c), sixteen of them per transposed pruned solve, the columns asked for its selection.
+// pairs: indices of the complex matrix behind a real-equivalent handle (unit vector 2 u alone, rows 2 w and 2 w + 1, interleaved values).
+int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values, bool by_rows, bool pairs) {
+    pruned_blocks = 0, pruned_transposed_blocks = 0;
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!rows || !cols || !values) return ERROR_NULL_POINTER;
     if (nent < 1) return ERROR_HIPMF_INVALID_VALUE;
-    const int32_t n = S.n;
+    const int32_t n = pairs ? S.n / 2 : S.n, w = pairs ? 2 : 1;
     for (int32_t e = 0; e < nent; e++)
         if (rows[e] < 0 || rows[e] >= n || cols[e] < 0 || cols[e] >= n) return ERROR_HIPMF_INVALID_VALUE;
     {
@@ -4880,9 +4938,11 @@ int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t
     }
     std::vector<int32_t> ent((size_t)nent);
     for (int32_t e = 0; e < nent; e++) ent[(size_t)e] = e;
+    const int32_t *unit = by_rows ? rows : cols, *want = by_rows ? cols : rows; // the unit right-hand sides, the rows of the solution asked for
+    const std::vector<int32_t> &pos = (by_rows && !(S.sym_mode || d_tptr)) ? sp_ipos_c : sp_ipos_r;
     std::sort(ent.begin(), ent.end(), [&](int32_t a, int32_t b) {
-        const int32_t pa = sp_ipos_r[(size_t)cols[a]], pb = sp_ipos_r[(size_t)cols[b]];
-        return pa != pb ? pa < pb : (rows[a] != rows[b] ? rows[a] < rows[b] : a < b);
+        const int32_t pa = pos[(size_t)w * (size_t)unit[a]], pb = pos[(size_t)w * (size_t)unit[b]];
+        return pa != pb ? pa < pb : (want[a] != want[b] ? want[a] < want[b] : a < b);
     });
     std::vector<int32_t> ptr, idx, sel;
     std::vector<double> val, out;
@@ -4892,12 +4952,12 @@ int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t
         ptr.assign(1, 0), idx.clear(), sel.clear();
         size_t e1 = e0;
         while (e1 < ent.size()) {
-            const int32_t c = cols[ent[e1]];
+            const int32_t c = w * unit[ent[e1]];
             if (idx.empty() || idx.back() != c) {
                 if ((int32_t)idx.size() == SP_KB) break;
                 idx.push_back(c), ptr.push_back((int32_t)idx.size());
             }
-            sel.push_back(rows[ent[e1]]);
+            for (int32_t h = 0; h < w; h++) sel.push_back(w * want[ent[e1]] + h);
             e1++;
         }
         std::sort(sel.begin(), sel.end());
@@ -4905,14 +4965,14 @@ int32_t Solver::inverse_entries(int32_t nent, const int32_t *rows, const int32_t
         const int32_t nk = (int32_t)idx.size(), ns = (int32_t)sel.size();
         val.assign((size_t)nk, 1.0);
         out.assign((size_t)nk * (size_t)ns, 0.0);
-        const int32_t code = solve_sparse(out.data(), ns, nk, ptr.data(), idx.data(), val.data(), ns, sel.data(), false, true);
+        const int32_t code = solve_sparse(out.data(), ns, nk, ptr.data(), idx.data(), val.data(), ns, sel.data(), false, true, by_rows);
         if (code != SUCCESSFUL_EXIT) return code;
         int32_t c = -1, last = -1;
         for (size_t e = e0; e < e1; e++) {
             const int32_t en = ent[e];
-            if (cols[en] != last) last = cols[en], c++;
-            const int32_t k = (int32_t)(std::lower_bound(sel.begin(), sel.end(), rows[en]) - sel.begin());
-            values[en] = out[(size_t)c * (size_t)ns + (size_t)k];
+            if (unit[en] != last) last = unit[en], c++;
+            const int32_t k = (int32_t)(std::lower_bound(sel.begin(), sel.end(), w * want[en]) - sel.begin());
+            for (int32_t h = 0; h < w; h++) values[(size_t)w * (size_t)en + (size_t)h] = out[(size_t)c * (size_t)ns + (size_t)k + (size_t)h];
         }
         e0 = e1;
     }

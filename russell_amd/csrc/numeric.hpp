@@ -150,6 +150,10 @@ struct SolverPruned {
         int32_t va_off = 0, va_cnt = 0;                           // SolveTasks: the big fronts' vectors (assembly forward, gather backward)
         int32_t pr_off = 0, pr_cnt = 0;                           // SolveTasks: their products, SP_ROWS rows each
     };
+    // what the product tasks of a list cover: rows [0, p) of E' (backward; also the 16-column tiles of E over [0, p) of the transposed
+    // backward pass), rows [0, p) and [p, f) of E (forward: the tiles restart at p), or 16-column tiles of E' over [0, f) from 0
+    // (transposed forward: k_tr_gemm_blk wants tile starts that are multiples of 16)
+    enum SpShape { SP_BACKWARD = 0, SP_FORWARD = 1, SP_FORWARD_T = 2 };
     template <class T> struct Growing {
         DeviceArray<T> a;
         size_t cap = 0;
@@ -333,10 +337,18 @@ class Solver : public SolverDevice {
     // marked fronts.  sel_idx == nullptr: all n rows.  Blocks whose marked fronts read more than HIPMF_PRUNE_MAX_SHARE of what a full pass
     // pair reads, and every block of a factor with replaced pivots, go through solve() on the expanded columns.  on_device: every array
     // but the handle's own lives on the device.  See numeric.cpp.
+    // transposed: A^T in place of A through the pruned transposed launches of kernels_solve_pruned_transpose.hpp (L D L^T / symmetric
+    // storage: A^T = A, the ordinary path and its bits); its fallback is solve_transpose_many on the expanded columns.  The two thresholds
+    // were measured for the ordinary path only.  conj_pairs (with transposed, host arrays): interleaved complex pairs whose imaginary
+    // parts -- the odd rows -- are negated on the way in and out (the complex twin's A^T through the real-equivalent A^H).
     int32_t solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int32_t *rhs_ptr, const int32_t *rhs_idx, const double *rhs_val, int32_t nsel,
-                         const int32_t *sel_idx, bool on_device, bool accumulate = false);
-    // values[e] = (A^{-1})(rows[e], cols[e]) (host arrays): blocks of at most 16 distinct columns, neighbours in the elimination order together
-    int32_t inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values);
+                         const int32_t *sel_idx, bool on_device, bool accumulate = false, bool transposed = false, bool conj_pairs = false);
+    // values[e] = (A^{-1})(rows[e], cols[e]) (host arrays): blocks of at most 16 distinct columns, neighbours in the elimination order together.
+    // by_rows: blocks of at most 16 distinct ROWS as unit right-hand sides of the transposed pruned solve ((A^{-1})(r, c) = (A^{-T})(c, r)),
+    // the columns asked for in a block its selection.  pairs: this handle holds the real-equivalent system of a complex matrix of order
+    // n / 2; rows / cols index the complex matrix, values are interleaved (re, im) -- unit column c is real column 2 c, row r rows 2 r, 2 r + 1.
+    int32_t inverse_entries(int32_t nent, const int32_t *rows, const int32_t *cols, double *values, bool by_rows = false, bool pairs = false);
+    int64_t pruned_transposed_blocks = 0;                 // blocks of the last such call that ran the transposed pruned kernels
     int64_t pruned_fwd_fronts = 0, pruned_bwd_fronts = 0; // fronts the forward / backward pass of the last pruned block visited
     int64_t pruned_blocks = 0;                            // blocks of the last solve_sparse / inverse_entries that ran pruned
     int64_t pruned_bytes = 0;                             // 8 x the factor entries (p f per front and pass) those fronts hold
@@ -600,10 +612,11 @@ class Solver : public SolverDevice {
     int32_t tr_rescue(double *tx, const double *tb, bool first_column); // FGMRES on one transposed column (the preconditioner: tr_pass)
     int32_t tr_prepare_blocked();
     int32_t sp_prepare();
-    // per-level lists of the fronts in `fronts` (any order) into `buf`, levels ascending: forward shapes (assembly + products over f rows)
-    // or backward shapes (gather + products over p rows)
-    void sp_build_lists(const std::vector<int32_t> &fronts, bool forward, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const;
+    // per-level lists of the fronts in `fronts` (any order) into `buf`, levels ascending: forward shapes (assembly + products over f rows),
+    // backward shapes (gather + products over p rows) or transposed forward shapes (assembly + 16-column tiles over f columns)
+    void sp_build_lists(const std::vector<int32_t> &fronts, SpShape shape, std::vector<int32_t> &buf, std::vector<SpLevel> &lv) const;
     int32_t run_pruned(double *XP, const std::vector<SpLevel> &fl, const std::vector<SpLevel> &bl);
+    int32_t run_pruned_transposed(double *XP, const std::vector<SpLevel> &fl, const std::vector<SpLevel> &bl); // the same for A^T
 };
 
 } // namespace hipmf

@@ -168,6 +168,8 @@ def _L():
         "rh_linsolver_solve_many": (cp, [vp, vp, vp, i64, i64]),
         "rh_linsolver_solve_sparse": (cp, [vp, vp, i64, i64, vp, vp, vp, i64, vp, i32]),
         "rh_linsolver_inverse_entries": (cp, [vp, vp, i64, vp, vp, i32]),
+        "rh_linsolver_solve_sparse_transpose": (cp, [vp, vp, i64, i64, vp, vp, vp, i64, vp, i32]),
+        "rh_linsolver_inverse_entries_by_rows": (cp, [vp, vp, i64, vp, vp, i32]),
         "rh_linsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
         "rh_linsolver_solve_updated_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
         "rh_linsolver_times": (None, [vp, pp(C.c_uint64)]),
@@ -493,10 +495,11 @@ class _Actual:
         _check(_L().rh_linsolver_solve_many(self._h, _ptr(x), _ptr(b), n, nrhs))
         return x
 
-    def solve_sparse(self, rhs_cols, select=None, verbose=False):
+    def solve_sparse(self, rhs_cols, select=None, verbose=False, transpose=False):
         """Rows `select` (None: all) of A^{-1} B for a sparse B: `rhs_cols` is a list of (indices, values) pairs, one per column, or a
         compressed-column triple (ptr, idx, val); row indices ascending within a column.  Returns an array of shape (ncol, nsel): row c
-        holds the selected entries of column c.  One unrefined pass pair over the fronts the non-zeros and the selected rows touch."""
+        holds the selected entries of column c.  One unrefined pass pair over the fronts the non-zeros and the selected rows touch.
+        transpose: rows of A^{-T} B."""
         if isinstance(rhs_cols, tuple) and len(rhs_cols) == 3 and np.ndim(rhs_cols[0]) == 1 and not isinstance(rhs_cols[0], tuple):
             ptr, idx, val = (np.asarray(a) for a in rhs_cols)
         else:
@@ -519,17 +522,18 @@ class _Actual:
             raise StrError("the function factorize must be called before solve")
         ncol, nout = ptr.size - 1, (self._ndim if sel is None else sel.size)
         x = np.zeros((ncol, nout))
-        _check(_L().rh_linsolver_solve_sparse(self._h, _ptr(x), x.size, ncol, _ptr(ptr), _ptr(idx), _ptr(val), 0 if sel is None else sel.size,
-                                              None if sel is None else _ptr(sel), int(verbose)))
+        fn = _L().rh_linsolver_solve_sparse_transpose if transpose else _L().rh_linsolver_solve_sparse
+        _check(fn(self._h, _ptr(x), x.size, ncol, _ptr(ptr), _ptr(idx), _ptr(val), 0 if sel is None else sel.size, None if sel is None else _ptr(sel), int(verbose)))
         return x
 
-    def inverse_entries(self, rows, cols, verbose=False):
-        """(A^{-1})[rows[e], cols[e]] for every e: any order, duplicates allowed."""
+    def inverse_entries(self, rows, cols, verbose=False, by_rows=False):
+        """(A^{-1})[rows[e], cols[e]] for every e: any order, duplicates allowed.  by_rows: through A^T, 16 distinct rows per block."""
         r, c = np.ascontiguousarray(rows, dtype=np.int32).ravel(), np.ascontiguousarray(cols, dtype=np.int32).ravel()
         if r.size != c.size or r.size == 0:
             raise StrError("the arrays of row and column indices must have the same, positive length")
         v = np.zeros(r.size)
-        _check(_L().rh_linsolver_inverse_entries(self._h, _ptr(v), r.size, _ptr(r), _ptr(c), int(verbose)))
+        fn = _L().rh_linsolver_inverse_entries_by_rows if by_rows else _L().rh_linsolver_inverse_entries
+        _check(fn(self._h, _ptr(v), r.size, _ptr(r), _ptr(c), int(verbose)))
         return v
 
     def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
@@ -598,13 +602,13 @@ class LinSolver:
         _check(err.value)
         self.actual = _Actual(h)
 
-    def solve_sparse(self, rhs_cols, select=None, verbose=False):
+    def solve_sparse(self, rhs_cols, select=None, verbose=False, transpose=False):
         """extension of the HIPMF backend, see `actual.solve_sparse`"""
-        return self.actual.solve_sparse(rhs_cols, select, verbose)
+        return self.actual.solve_sparse(rhs_cols, select, verbose, transpose)
 
-    def inverse_entries(self, rows, cols, verbose=False):
+    def inverse_entries(self, rows, cols, verbose=False, by_rows=False):
         """extension of the HIPMF backend, see `actual.inverse_entries`"""
-        return self.actual.inverse_entries(rows, cols, verbose)
+        return self.actual.inverse_entries(rows, cols, verbose, by_rows)
 
     def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
         """extension of the HIPMF backend, see `actual.solve_updated`"""

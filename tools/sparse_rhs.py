@@ -13,7 +13,14 @@ matrix, the 100^3 7-point one) and case
 the line gives the fronts the forward / backward pass visited, the share of a full pass pair's factor entries they hold and the bytes
 that is, the median HIP-event time of the pruned call (dstats[8]: uploads, launches and copies of the call; HIPMF_PRUNE_MAX_SHARE=1 so
 that the pruned path runs whatever its share) and of solver_hipmf_solve_device on the expanded block on the same handle, each over
---reps calls after --warmup.  Case d has no expanded twin of the same shape: its reference is 256 / 16 times the 16-column solve."""
+--reps calls after --warmup.  Case d has no expanded twin of the same shape: its reference is 256 / 16 times the 16-column solve.
+
+    python tools/sparse_rhs.py --transpose [...]
+
+the table of profiles/r16_sparse_rhs_transpose.txt: cases a, b and d through A^T (solver_hipmf_solve_sparse_transpose_device,
+solver_hipmf_inverse_entries_by_rows) against solver_hipmf_solve_transpose_many_device on the expanded block.  The matrices are handed
+over in general form, so the transposed launches run.  The transposed dense solve keeps no HIP-event time of its own: BOTH sides of this
+table are host wall-clock medians around the call (the calls return synchronised); the pruned call's own event time is printed beside it."""
 import argparse
 import os
 import sys
@@ -38,6 +45,17 @@ def median_ms(fn, s, reps, warmup):
     return float(np.median(t)), float(np.min(t)), float(np.max(t))
 
 
+def median_wall_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
 def dev(s, arr, keep):
     a = np.ascontiguousarray(arr)
     p = s.dev_alloc(max(a.nbytes, 8))
@@ -45,6 +63,51 @@ def dev(s, arr, keep):
     if a.nbytes:
         s.h2d(p, a)
     return p
+
+
+def run_matrix_transposed(name, n, rp, ci, v, coords, reps, warmup, out):
+    """cases a, b, d through A^T; wall-clock medians on both sides"""
+    s = Hipmf()
+    keep = []
+    try:
+        t0 = time.perf_counter()
+        assert s.initialize(n, rp, ci, refinement_nstep=0) == 0
+        assert s.factorize(v) == 0
+        st = s.stats()
+        assert s.counter("symmetric_ldlt") == 0
+        out("%s, A^T: n = %d, nsuper = %d, levels = %d, max front = %d, factor (L + U entries) %.1f MB, set-up %.1f s"
+            % (name, n, st["nsuper"], st["nlevels"], st["max_front"], 8.0 * (st["nnz_l"] + st["nnz_u"]) / 1e6, time.perf_counter() - t0))
+        out("  case  cols  rows        fwd fronts  bwd fronts  MB visited  transposed blocks  pruned wall ms (min .. max)  [event ms]   solve_transpose_many_device wall ms (min .. max)   ratio")
+        d_x, d_b = s.dev_alloc(8 * n * 16), s.dev_alloc(8 * n * 16)
+        keep += [d_x, d_b]
+        dense_ms = {}
+        for tag, cols, sel in [("a", coords(1, "leaf"), coords(1, "leaf")), ("b", coords(16, "leaf"), coords(16, "leaf") + 1)]:
+            k, nsel = cols.size, sel.size
+            d_ptr, d_idx, d_val = dev(s, np.arange(k + 1, dtype=np.int32), keep), dev(s, cols.astype(np.int32), keep), dev(s, np.ones(k), keep)
+            d_sel, d_out = dev(s, sel.astype(np.int32), keep), dev(s, np.zeros(nsel * k), keep)
+            B = np.zeros((k, n))
+            B[np.arange(k), cols] = 1.0
+            s.h2d(d_b, B)
+            pm = median_wall_ms(lambda: s.solve_sparse_device(d_out, nsel, k, d_ptr, d_idx, d_val, nsel, d_sel, transpose=True), reps, warmup)
+            ev = s.stats()["solve_total_ms"]
+            ff, bf, tb = s.counter("pruned_fwd_fronts"), s.counter("pruned_bwd_fronts"), s.counter("pruned_transposed_blocks")
+            dm = median_wall_ms(lambda: s.solve_transpose_many_device(d_x, d_b, k), reps, warmup)
+            dense_ms[k] = dm[0]
+            X, Xs = np.zeros((k, n)), np.zeros((k, nsel))
+            s.d2h(X, d_x)
+            s.d2h(Xs, d_out)
+            agree = np.abs(Xs - X[:, sel]).max() / np.abs(X).max()
+            out("  %-4s  %4d  %-10s  %10d  %10d  %10.1f  %17d  %8.3f (%.3f .. %.3f)  [%.3f]   %8.3f (%.3f .. %.3f)   %6.2f   max |pruned - dense| / |x| = %.1e"
+                % (tag, k, str(nsel), ff, bf, s.counter("pruned_bytes") / 1e6, tb, pm[0], pm[1], pm[2], ev, dm[0], dm[1], dm[2], pm[0] / dm[0], agree))
+        diag = coords(min(256, n // 2), "spread").astype(np.int32)
+        pm = median_wall_ms(lambda: s.inverse_entries(diag, diag, by_rows=True), max(3, reps // 3), 1)
+        out("  %-4s  %4d  %-10s  %10d  %10d  %10.1f  %17d  %8.3f (%.3f .. %.3f)  [%.3f]   %8.3f (16 x the 16-column solve)   %6.2f   (fronts and MB: the last block)"
+            % ("d", diag.size, "diagonal", s.counter("pruned_fwd_fronts"), s.counter("pruned_bwd_fronts"), s.counter("pruned_bytes") / 1e6, s.counter("pruned_transposed_blocks"),
+               pm[0], pm[1], pm[2], s.stats()["solve_total_ms"], 16 * dense_ms[16], pm[0] / (16 * dense_ms[16])))
+    finally:
+        for p in keep:
+            s.dev_free(p)
+        s.close()
 
 
 def run_matrix(name, n, rp, ci, v, coords, reps, warmup, out):
@@ -106,7 +169,9 @@ def main():
     ap.add_argument("--nx2d", type=int, default=1000, help="grid edge of the 2D matrix (smaller: a rehearsal)")
     ap.add_argument("--nx3d", type=int, default=100, help="grid edge of the 3D matrix")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--transpose", action="store_true", help="cases a, b, d through A^T against solver_hipmf_solve_transpose_many_device")
     a = ap.parse_args()
+    run = run_matrix_transposed if a.transpose else run_matrix
     os.environ["HIPMF_PRUNE_MAX_SHARE"] = "1"
 
     def out(line):
@@ -124,7 +189,7 @@ def main():
                 return np.array([nx * (3 + i // 4) + 5 + (i % 4) for i in range(k)])
             return np.linspace(0, n - 1, k + 2)[1:-1].astype(np.int64)
 
-        run_matrix("2D 5-point Poisson %d x %d" % (nx, nx), n, rp, ci, v, c2, a.reps, a.warmup, out)
+        run("2D 5-point Poisson %d x %d" % (nx, nx), n, rp, ci, v, c2, a.reps, a.warmup, out)
     if a.matrix in ("3d", "both"):
         nx = a.nx3d
         n, rp, ci, v = P.poisson3d(nx)
@@ -134,7 +199,7 @@ def main():
                 return np.array([nx * nx * (3 + i // 8) + nx * (4 + (i // 4) % 2) + 5 + (i % 4) for i in range(k)])
             return np.linspace(0, n - 1, k + 2)[1:-1].astype(np.int64)
 
-        run_matrix("3D 7-point Poisson %d^3" % nx, n, rp, ci, v, c3, a.reps, a.warmup, out)
+        run("3D 7-point Poisson %d^3" % nx, n, rp, ci, v, c3, a.reps, a.warmup, out)
 
 
 if __name__ == "__main__":
