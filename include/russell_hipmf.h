@@ -264,6 +264,38 @@ int32_t solver_hipmf_solve_updated_many(struct InterfaceHIPMF *solver, double *x
 int32_t solver_hipmf_solve_updated_many_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
                                                const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
 
+/* The TRANSPOSED forms: A_new^T x = rhs on the kept factor, for the adjoint systems of the callers above (discrete adjoints and
+ * sensitivities of a step with a lagged Jacobian, adjoint right-hand sides after a coefficient update, condition estimates of the updated
+ * matrix) without a new factorisation.  Arguments, values / mapped, rel_tol, max_steps, steps, relres, the per-column arrays, the return
+ * codes, the argument checks and their order are exactly those of solver_hipmf_solve_updated / _device / _many / _many_device.
+ * Method: the same right-preconditioned flexible GMRES from x = 0 (one core serves both; HIPMF_UPDATED_RESTART and HIPMF_UPDATED_TIMING
+ * apply) with A_new^T as operator -- products and 2-norm residuals over the rows of A^T, long rows (dense columns of A) summed by a whole
+ * workgroup, every sum in a fixed order: bit-reproducible from call to call -- and the UNREFINED transposed pass pair of the kept factor as
+ * preconditioner (single: the kernels of solver_hipmf_solve_transpose; blocks of 16: those of solver_hipmf_solve_transpose_many, whose
+ * buffers the first call allocates; without memory for them the columns go through the single form one at a time).  A cycle that does not
+ * lower the true residual is taken back, non-finite records end a cycle, as above.  After a factorisation that replaced pivots the
+ * preconditioner is merely weaker; there is no rescue inside.  L D L^T fronts, symmetric storage or a symmetric matrix expanded inside the
+ * handle (A^T = A): the non-transposed form, its bits.
+ * NO SIDE EFFECTS: a later solver_hipmf_solve / _solve_transpose and every counter of the ordinary and of the transposed solves
+ * (HIPMF_COUNTER_TRANSPOSED_SOLVES, _TRANSPOSED_BLOCKS, _TRANSPOSED_KRYLOV_ITERATIONS, the refinement statistics, the timers) are what they
+ * would have been without the call; HIPMF_COUNTER_UPDATED_* report the call as for the non-transposed forms.
+ * WHEN IT PAYS (tools/solve_updated.py --transpose, one MI355X, profiles/r17_solve_updated_transpose.txt; DESIGN.md section 13 "The
+ * transposed form"): at 1M unknowns a transposed step costs 1.25 ms (the transposed pass pair 1.12) against 0.56 ms for a plain step and
+ * 8.4 ms for factorize_device + solve_transpose_device: the single form wins below seven steps and loses to refactorising beyond (15.0
+ * against 8.45 ms at 12 steps).  The block form costs 0.213 ms per column and step, 4 - 6 times less than the loop of single calls, but
+ * 16 or 64 columns share one refactorisation: it lost to factorize_device + solve_transpose_many_device in every case measured (1.60
+ * against 0.83 ms per column at six steps and 16 columns). */
+int32_t solver_hipmf_solve_updated_transpose(struct InterfaceHIPMF *solver, double *x, const double *rhs, const double *values, int32_t mapped,
+                                             double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose);
+int32_t solver_hipmf_solve_updated_transpose_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped,
+                                                    double rel_tol, int32_t max_steps, int32_t *steps, double *relres);
+int32_t solver_hipmf_solve_updated_transpose_many(struct InterfaceHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld,
+                                                  const double *values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
+                                                  C_BOOL verbose);
+int32_t solver_hipmf_solve_updated_transpose_many_device(struct InterfaceHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                         const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                                         double *relres);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -479,6 +511,19 @@ int32_t complex_solver_hipmf_solve_many(struct InterfaceComplexHIPMF *solver, do
 int32_t complex_solver_hipmf_solve_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld);
 /* conjugate: 1 -> A^H x = b, 0 -> A^T x = b (the real transposed solve of the real-equivalent system; umfpack_zi_solve's UMFPACK_Aat / UMFPACK_At) */
 int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t conjugate, C_BOOL verbose);
+/* The same for nrhs columns, 16 per transposed pass pair: solver_hipmf_solve_transpose_many for the complex handle.  x, rhs: column-major
+ * ld x nrhs COMPLEX arrays, interleaved; ld counts complex elements, ld >= n; entries n .. ld - 1 of every column of x are not written.
+ * conjugate = 1: A^H X = B, the blocked transposed solve of the real-equivalent system; conjugate = 0: A^T X = B, the same solve with the
+ * imaginary parts of every block's staged columns negated on entry and exit (one launch per block each way); refinement and the
+ * transposed rescue per column run in between, on the A^H system.  nrhs == 1 is complex_solver_hipmf_solve_transpose, bit for bit;
+ * HIPMF_TRANSPOSE_BLOCKED=0 or no memory for the block buffers: that call column by column.  HIPMF_COUNTER_TRANSPOSED_BLOCKS counts the
+ * blocks.  _device: device pointers; d_x may alias d_rhs.  ERROR_NULL_POINTER, ERROR_NEED_FACTORIZATION in this order, then
+ * ERROR_HIPMF_INVALID_VALUE (conjugate not 0 or 1, nrhs < 1, ld < n).  Measured (tools/transpose_many.py --complex, 500 x 500 complex grid,
+ * default refinement, profiles/r17_complex_transpose_many.txt): 0.36 ms per column (A^T 0.37) against 2.55 for the column loop. */
+int32_t complex_solver_hipmf_solve_transpose_many(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld,
+                                                  int32_t conjugate, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_transpose_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                         int32_t conjugate);
 /* Sparse right-hand sides and selected solution rows for the complex handle (host pointers):
  *   x_sel(k, c) = (op(A)^{-1} B)(sel_idx[k], c),   trans = 0: op(A) = A,  1: A^T,  2: A^H
  * B in compressed-column form as for solver_hipmf_solve_sparse with rhs_val interleaved (re, im) pairs, one per entry of rhs_idx; x_sel
@@ -576,6 +621,28 @@ int32_t complex_solver_hipmf_solve_updated_many(struct InterfaceComplexHIPMF *so
 int32_t complex_solver_hipmf_solve_updated_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
                                                        const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
                                                        double *relres);
+/* The TRANSPOSED forms for the complex handle: A_new^H z = c (conjugate = 1) or A_new^T z = c (conjugate = 0) on the kept factor, as
+ * solver_hipmf_solve_updated_transpose and its three siblings for the real handle, in the complex arithmetic of the forms above.
+ * conjugate = 1 is the transposed real-equivalent system: operator A_new^H, preconditioner the unrefined transposed pass pair.
+ * conjugate = 0 is the same iteration on conjugated data (A_new^T z = c <=> A_new^H conj(z) = conj(c)): the imaginary parts of c are
+ * negated on entry (in a staging copy: c is not changed) and those of z on exit; steps and relres are those of the A^H iteration on
+ * conj(c), and z equals conj of the conjugate = 1 result for conj(c) bit for bit.  A complex-symmetric handle (lower triangle given) has
+ * A^T = A: conjugate = 0 is the non-transposed form there, its bits.  ld counts complex elements.  Checks and their order: those of the
+ * non-transposed complex forms, with ERROR_HIPMF_INVALID_VALUE for a conjugate other than 0 or 1 right after ERROR_NEED_FACTORIZATION;
+ * the map check comes last.  No side effects on the handle, as for the real forms.  Measured (tools/solve_updated.py --complex
+ * --transpose, 500 x 500 complex shifted grid, conjugate = 1, profiles/r17_solve_updated_transpose.txt): 1.22 ms per step against 9.6 ms
+ * for factorize_mapped + solve_transpose, break-even at eight steps (h -> h/2 takes 11: 13.4 ms, a loss); block form 2.27 ms per column
+ * against 13.35 for the loop of single calls and 0.97 (16 columns) for factorize_mapped + solve_transpose_many. */
+int32_t complex_solver_hipmf_solve_updated_transpose(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, const double *values, int32_t mapped,
+                                                     double rel_tol, int32_t max_steps, int32_t *steps, double *relres, int32_t conjugate, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_updated_transpose_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, const double *d_values,
+                                                            int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, int32_t conjugate);
+int32_t complex_solver_hipmf_solve_updated_transpose_many(struct InterfaceComplexHIPMF *solver, double *x, const double *rhs, int32_t nrhs, int32_t ld,
+                                                          const double *values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                                          double *relres, int32_t conjugate, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_updated_transpose_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs,
+                                                                 int32_t ld, const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps,
+                                                                 int32_t *steps, double *relres, int32_t conjugate);
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *solver);
 
 /* plain device-memory helpers so that callers need no HIP binding of their own */

@@ -107,6 +107,13 @@ const char *rh_clinsolver_solve_updated(void *solver, double *x, int64_t nx, voi
 const char *rh_clinsolver_solve_many(void *solver, double *x, const double *rhs, int64_t n, int64_t nrhs);
 const char *rh_clinsolver_solve_updated_many(void *solver, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
                                              int32_t *steps, double *relres, int32_t verbose);
+/* the transposed forms (complex_solver_hipmf_solve_updated_transpose / _many, complex_solver_hipmf_solve_transpose_many of russell_hipmf.h):
+ * conjugate = 1 -> A^H, 0 -> A^T; everything else as the functions above */
+const char *rh_clinsolver_solve_updated_transpose(void *solver, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
+                                                  int32_t *steps, double *relres, int32_t conjugate, int32_t verbose);
+const char *rh_clinsolver_solve_updated_transpose_many(void *solver, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol,
+                                                       int32_t max_steps, int32_t *steps, double *relres, int32_t conjugate, int32_t verbose);
+const char *rh_clinsolver_solve_transpose_many(void *solver, double *x, const double *rhs, int64_t n, int64_t nrhs, int32_t conjugate);
 /* determinant = (det_re + i det_im) x 10^det_exp (LinSolParams.compute_determinant; complex_solver_umfpack.rs:411-414) */
 void rh_clinsolver_outputs(void *solver, double *det_re, double *det_im, double *det_exp, double *rcond, int32_t *npert);
 /* the eight values of mumps_stats (RINFOG(4..11)) of the last solve when LinSolParams.compute_error_estimates (entries 0 - 4) or
@@ -136,6 +143,11 @@ const char *rh_linsolver_solve_updated(void *solver, double *x, int64_t nx, void
  * "Error(2): ..." when any column did not reach the tolerance (x, steps and relres are written then too) */
 const char *rh_linsolver_solve_updated_many(void *solver, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
                                             int32_t *steps, double *relres, int32_t verbose);
+/* the transposed forms, A_new^T x = rhs (solver_hipmf_solve_updated_transpose / _many): the arguments of the two functions above */
+const char *rh_linsolver_solve_updated_transpose(void *solver, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
+                                                 int32_t *steps, double *relres, int32_t verbose);
+const char *rh_linsolver_solve_updated_transpose_many(void *solver, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol,
+                                                      int32_t max_steps, int32_t *steps, double *relres, int32_t verbose);
 void rh_linsolver_times(void *solver, uint64_t *ns3);
 void rh_linsolver_outputs(void *solver, double *det_coef, double *det_exp, double *rcond, int32_t *eff_ordering, int32_t *eff_scaling, int32_t *npert);
 const char *rh_linsolver_stats_json(void *solver, void *coo, const char *name, const double *x, const double *rhs);

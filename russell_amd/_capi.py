@@ -50,6 +50,14 @@ SYMBOLS = {
                                                     C.c_int32]),
     "solver_hipmf_solve_updated_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_int32,
                                                            C.c_void_p, C.c_void_p]),
+    "solver_hipmf_solve_updated_transpose": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
+                                                         C.POINTER(C.c_double), C.c_int32]),
+    "solver_hipmf_solve_updated_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32,
+                                                                C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "solver_hipmf_solve_updated_transpose_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, f64p, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                                              C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_updated_transpose_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                                                     C.c_int32, C.c_void_p, C.c_void_p]),
     "solver_hipmf_solve_with_error_analysis": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_int32]),
     "solver_hipmf_mat_vec_mul": (C.c_int32, [C.c_void_p, f64p, C.c_double, f64p]),
     "solver_hipmf_get_permutation": (C.c_int32, [C.c_void_p, i32p]),
@@ -88,6 +96,16 @@ SYMBOLS = {
                                                             C.c_void_p, C.c_int32]),
     "complex_solver_hipmf_solve_updated_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    "complex_solver_hipmf_solve_updated_transpose": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
+                                                                 C.POINTER(C.c_double), C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_updated_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32,
+                                                                        C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32]),
+    "complex_solver_hipmf_solve_updated_transpose_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, f64p, C.c_int32, C.c_double, C.c_int32,
+                                                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_updated_transpose_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                                             C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_solve_transpose_many": (C.c_int32, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "complex_solver_hipmf_solve_transpose_many_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "complex_solver_hipmf_get_stats": (C.c_int32, [C.c_void_p, i64p, f64p]),
     "complex_solver_hipmf_get_counter": (C.c_int64, [C.c_void_p, C.c_int32]),
     "complex_solver_hipmf_last_error": (C.c_char_p, [C.c_void_p]),

@@ -175,22 +175,26 @@ class Hipmf:
             raise self._err(code, name)
         return v
 
-    def solve_updated(self, rhs, values, mapped=False, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated(self, rhs, values, mapped=False, rel_tol=0.0, max_steps=0, verbose=False, transpose=False):
         """A_new x = rhs for the matrix with the structure of initialize and the `values` given here (mapped: the inputs of the installed
-        value map), by flexible GMRES on the device with the kept factor as right preconditioner.  Returns (x, steps, relres, status):
+        value map), by flexible GMRES on the device with the kept factor as right preconditioner; transpose: A_new^T x = rhs
+        (solver_hipmf_solve_updated_transpose).  Returns (x, steps, relres, status):
         status 0 = converged, 2 = HIPMF_WARNING_NOT_CONVERGED (x is the best iterate); any other status raises."""
+        name = "solver_hipmf_solve_updated_transpose" if transpose else "solver_hipmf_solve_updated"
         x = np.zeros(self.n)
         steps, relres = C.c_int32(0), C.c_double(0.0)
-        code = self.lib.solver_hipmf_solve_updated(self.h, x, np.ascontiguousarray(rhs, dtype=np.float64), np.ascontiguousarray(values, dtype=np.float64),
-                                                   int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres), int(verbose))
+        code = getattr(self.lib, name)(self.h, x, np.ascontiguousarray(rhs, dtype=np.float64), np.ascontiguousarray(values, dtype=np.float64),
+                                       int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres), int(verbose))
         if code not in (0, self.WARNING_NOT_CONVERGED):
-            raise self._err(code, "solver_hipmf_solve_updated")
+            raise self._err(code, name)
         return x, int(steps.value), float(relres.value), code
 
-    def solve_updated_many(self, rhs_colmajor, values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, verbose=False):
+    def solve_updated_many(self, rhs_colmajor, values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, verbose=False, transpose=False):
         """solve_updated for the right-hand sides of an array of shape (nrhs, ld) as solve_many takes it, 16 columns per blocked pass pair,
-        every column its own iteration.  Returns (x, steps, relres, status): x in the layout of solve_many, steps and relres NumPy arrays
+        every column its own iteration; transpose: A_new^T X = B (solver_hipmf_solve_updated_transpose_many).  Returns (x, steps, relres,
+        status): x in the layout of solve_many, steps and relres NumPy arrays
         of nrhs entries, status 0 = every column converged, 2 = at least one did not (relres tells which); any other status raises."""
+        name = "solver_hipmf_solve_updated_transpose_many" if transpose else "solver_hipmf_solve_updated_many"
         b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
         ld = self.n if ld is None else int(ld)
         if b.ndim != 2 or b.shape[1] != ld:
@@ -199,10 +203,10 @@ class Hipmf:
         x = np.zeros_like(b)
         x[:, self.n:] = b[:, self.n:]
         steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
-        code = self.lib.solver_hipmf_solve_updated_many(self.h, x, b, nrhs, ld, np.ascontiguousarray(values, dtype=np.float64), int(bool(mapped)), float(rel_tol),
-                                                        int(max_steps), steps.ctypes.data, relres.ctypes.data, int(verbose))
+        code = getattr(self.lib, name)(self.h, x, b, nrhs, ld, np.ascontiguousarray(values, dtype=np.float64), int(bool(mapped)), float(rel_tol),
+                                       int(max_steps), steps.ctypes.data, relres.ctypes.data, int(verbose))
         if code not in (0, self.WARNING_NOT_CONVERGED):
-            raise self._err(code, "solver_hipmf_solve_updated_many")
+            raise self._err(code, name)
         return x, steps, relres, code
 
     def mat_vec_mul(self, u, alpha=1.0):
@@ -332,21 +336,22 @@ class Hipmf:
         if code != 0:
             raise self._err(code, name)
 
-    def solve_updated_device(self, d_x, d_rhs, d_values, mapped=False, rel_tol=0.0, max_steps=0):
+    def solve_updated_device(self, d_x, d_rhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, transpose=False):
         """solve_updated with x, rhs and values resident on the device; returns (steps, relres, status)"""
+        name = "solver_hipmf_solve_updated_transpose_device" if transpose else "solver_hipmf_solve_updated_device"
         steps, relres = C.c_int32(0), C.c_double(0.0)
-        code = self.lib.solver_hipmf_solve_updated_device(self.h, d_x, d_rhs, d_values, int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps),
-                                                          C.byref(relres))
+        code = getattr(self.lib, name)(self.h, d_x, d_rhs, d_values, int(bool(mapped)), float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres))
         if code not in (0, self.WARNING_NOT_CONVERGED):
-            raise self._err(code, "solver_hipmf_solve_updated_device")
+            raise self._err(code, name)
         return int(steps.value), float(relres.value), code
 
-    def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None):
+    def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, transpose=False):
         """solve_updated_many with x, rhs (column-major ld x nrhs) and values resident on the device; returns (steps, relres, status)"""
+        name = "solver_hipmf_solve_updated_transpose_many_device" if transpose else "solver_hipmf_solve_updated_many_device"
         nrhs = int(nrhs)
         steps, relres = np.zeros(max(nrhs, 1), np.int32), np.zeros(max(nrhs, 1))
-        code = self.lib.solver_hipmf_solve_updated_many_device(self.h, d_x, d_rhs, nrhs, int(ld or self.n), d_values, int(bool(mapped)), float(rel_tol),
-                                                               int(max_steps), steps.ctypes.data, relres.ctypes.data)
+        code = getattr(self.lib, name)(self.h, d_x, d_rhs, nrhs, int(ld or self.n), d_values, int(bool(mapped)), float(rel_tol),
+                                       int(max_steps), steps.ctypes.data, relres.ctypes.data)
         if code not in (0, self.WARNING_NOT_CONVERGED):
-            raise self._err(code, "solver_hipmf_solve_updated_many_device")
+            raise self._err(code, name)
         return steps[:nrhs], relres[:nrhs], code

@@ -769,6 +769,11 @@ struct Backend {
     decltype(&complex_solver_hipmf_solve_updated) zsolve_updated = nullptr;
     decltype(&complex_solver_hipmf_solve_many) zsolve_many = nullptr;
     decltype(&complex_solver_hipmf_solve_updated_many) zsolve_updated_many = nullptr;
+    decltype(&solver_hipmf_solve_updated_transpose) solve_updated_t = nullptr;
+    decltype(&solver_hipmf_solve_updated_transpose_many) solve_updated_t_many = nullptr;
+    decltype(&complex_solver_hipmf_solve_updated_transpose) zsolve_updated_t = nullptr;
+    decltype(&complex_solver_hipmf_solve_updated_transpose_many) zsolve_updated_t_many = nullptr;
+    decltype(&complex_solver_hipmf_solve_transpose_many) zsolve_t_many = nullptr;
     bool tried = false;
 };
 Backend g_backend;
@@ -833,6 +838,11 @@ bool load_backend() {
     BIND(zsolve_updated, "complex_solver_hipmf_solve_updated")
     BIND(zsolve_many, "complex_solver_hipmf_solve_many")
     BIND(zsolve_updated_many, "complex_solver_hipmf_solve_updated_many")
+    BIND(solve_updated_t, "solver_hipmf_solve_updated_transpose")
+    BIND(solve_updated_t_many, "solver_hipmf_solve_updated_transpose_many")
+    BIND(zsolve_updated_t, "complex_solver_hipmf_solve_updated_transpose")
+    BIND(zsolve_updated_t_many, "complex_solver_hipmf_solve_updated_transpose_many")
+    BIND(zsolve_t_many, "complex_solver_hipmf_solve_transpose_many")
 #undef BIND
     g_backend.dl = dl;
     return true;
@@ -1266,8 +1276,9 @@ StrError ComplexSolverHIPMF::solve_transpose(std::vector<double> &x, const std::
 // CSR entries on the host and a changed pattern is refused.  The backend does not swap the handle's map for this call, so with the
 // triplet map installed the summed value of a CSR entry travels in the place of the entry's first triplet, zeros in the others.
 StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps,
-                                           int32_t *steps, double *relres, bool verbose) {
+                                           int32_t *steps, double *relres, bool verbose, int32_t trans) {
     if (!factorized) return "the function factorize must be called before solve";
+    if (trans < 0 || trans > 2) return "trans must be 0 (A), 1 (A^T) or 2 (A^H)";
     if (x.size() != 2 * initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
     if (rhs.size() != 2 * initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
     std::vector<double> conv;
@@ -1275,8 +1286,10 @@ StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const Complex
     StrError e = updated_values(mat, rel_tol, conv, &values);
     if (e) return e;
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.zsolve_updated((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), values, value_map_set ? 1 : 0, rel_tol, max_steps, steps, relres,
-                                              verbose ? 1 : 0);
+    int32_t status = trans == 0 ? g_backend.zsolve_updated((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), values, value_map_set ? 1 : 0, rel_tol, max_steps, steps,
+                                                           relres, verbose ? 1 : 0)
+                                : g_backend.zsolve_updated_t((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), values, value_map_set ? 1 : 0, rel_tol, max_steps, steps,
+                                                             relres, trans == 2 ? 1 : 0, verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1286,8 +1299,9 @@ StrError ComplexSolverHIPMF::solve_updated(std::vector<double> &x, const Complex
 // steps and relres one entry per column.  The error string of status 2 when any column did not converge; x, steps and relres are
 // written then too.
 StrError ComplexSolverHIPMF::solve_updated_many(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol,
-                                                int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose) {
+                                                int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose, int32_t trans) {
     if (!factorized) return "the function factorize must be called before solve";
+    if (trans < 0 || trans > 2) return "trans must be 0 (A), 1 (A^T) or 2 (A^H)";
     if (nrhs < 1) return "the number of right-hand sides must be at least one";
     if (rhs.size() != 2 * initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
     if (x.size() != 2 * initialized_ndim * nrhs) return "the dimension of the vector of unknown values x is incorrect";
@@ -1297,8 +1311,10 @@ StrError ComplexSolverHIPMF::solve_updated_many(std::vector<double> &x, const Co
     if (e) return e;
     steps.assign(nrhs, 0), relres.assign(nrhs, 0.0);
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.zsolve_updated_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, values,
-                                                   value_map_set ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(), verbose ? 1 : 0);
+    int32_t status = trans == 0 ? g_backend.zsolve_updated_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, values,
+                                                                value_map_set ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(), verbose ? 1 : 0)
+                                : g_backend.zsolve_updated_t_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, values,
+                                                                  value_map_set ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(), trans == 2 ? 1 : 0, verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1311,6 +1327,18 @@ StrError ComplexSolverHIPMF::solve_many(std::vector<double> &x, const std::vecto
     if (rhs.size() != 2 * initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
     uint64_t t0 = now_ns();
     int32_t status = g_backend.zsolve_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, 0);
+    if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
+    time_solve_ns = now_ns() - t0;
+    return nullptr;
+}
+
+// nrhs transposed solves, 16 columns per transposed pass pair (complex_solver_hipmf_solve_transpose_many): the layout of solve_many
+StrError ComplexSolverHIPMF::solve_transpose_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs, bool conjugate) {
+    if (!factorized) return "the function factorize must be called before solve";
+    if (nrhs < 1 || x.size() != 2 * initialized_ndim * nrhs) return "the dimension of the vector of unknown values x is incorrect";
+    if (rhs.size() != 2 * initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
+    uint64_t t0 = now_ns();
+    int32_t status = g_backend.zsolve_t_many((InterfaceComplexHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, conjugate ? 1 : 0, 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1427,7 +1455,7 @@ StrError SolverHIPMF::inverse_entries(std::vector<double> &values, const std::ve
 // new values.  Triplets in the order the value map was built from travel as they are (mapped); otherwise they are converted on the host
 // and a changed pattern is refused, as in factorize.  x is written also when the iteration did not converge (the best iterate).
 StrError SolverHIPMF::solve_updated(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps,
-                                    int32_t *steps, double *relres, bool verbose) {
+                                    int32_t *steps, double *relres, bool verbose, bool transpose) {
     if (!factorized) return "the function factorize must be called before solve";
     if (x.size() != initialized_ndim) return "the dimension of the vector of unknown values x is incorrect";
     if (rhs.size() != initialized_ndim) return "the dimension of the right-hand side vector is incorrect";
@@ -1447,8 +1475,9 @@ StrError SolverHIPMF::solve_updated(std::vector<double> &x, const CooMatrix &mat
             return "the updated matrix must be the factorized matrix with new values (sparsity pattern differs)";
     }
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.solve_updated((InterfaceHIPMF *)solver, x.data(), rhs.data(), mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol,
-                                             max_steps, steps, relres, verbose ? 1 : 0);
+    int32_t status = (transpose ? g_backend.solve_updated_t : g_backend.solve_updated)((InterfaceHIPMF *)solver, x.data(), rhs.data(),
+                                                                                       mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol, max_steps,
+                                                                                       steps, relres, verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1457,7 +1486,7 @@ StrError SolverHIPMF::solve_updated(std::vector<double> &x, const CooMatrix &mat
 // The same for nrhs right-hand sides (solver_hipmf_solve_updated_many): x and rhs column-major ndim x nrhs, steps and relres one entry per
 // column.  The error string of status 2 when any column did not converge; x, steps and relres are written then too.
 StrError SolverHIPMF::solve_updated_many(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol,
-                                         int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose) {
+                                         int32_t max_steps, std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose, bool transpose) {
     if (!factorized) return "the function factorize must be called before solve";
     if (nrhs < 1) return "the number of right-hand sides must be at least one";
     if (rhs.size() != initialized_ndim * nrhs) return "the dimension of the right-hand side vector is incorrect";
@@ -1479,9 +1508,9 @@ StrError SolverHIPMF::solve_updated_many(std::vector<double> &x, const CooMatrix
     }
     steps.assign(nrhs, 0), relres.assign(nrhs, 0.0);
     uint64_t t0 = now_ns();
-    int32_t status = g_backend.solve_updated_many((InterfaceHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim,
-                                                  mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol, max_steps, steps.data(), relres.data(),
-                                                  verbose ? 1 : 0);
+    int32_t status = (transpose ? g_backend.solve_updated_t_many : g_backend.solve_updated_many)(
+        (InterfaceHIPMF *)solver, x.data(), rhs.data(), (int32_t)nrhs, (int32_t)initialized_ndim, mapped ? mat.values.data() : conv.values.data(), mapped ? 1 : 0, rel_tol,
+        max_steps, steps.data(), relres.data(), verbose ? 1 : 0);
     if (status != SUCCESSFUL_EXIT) return handle_hipmf_error_code(status);
     time_solve_ns = now_ns() - t0;
     return nullptr;
@@ -1957,14 +1986,32 @@ const char *rh_clinsolver_solve_transpose(void *h, double *x, int64_t nx, const 
     if (!e) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
-const char *rh_clinsolver_solve_updated(void *h, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
-                                        double *relres, int32_t verbose) {
+static const char *clinsolver_solve_updated(void *h, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                            double *relres, int32_t verbose, int32_t trans) {
     RhComplexSolver *s = (RhComplexSolver *)h;
     if (!ccoo || !x || !rhs) return "solve_updated needs a matrix, x and a right-hand side";
     const std::vector<double> rr(rhs, rhs + (nr > 0 ? nr : 0));
     std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
-    StrError e = s->s->solve_updated(xx, *(const ComplexCooMatrix *)ccoo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
+    StrError e = s->s->solve_updated(xx, *(const ComplexCooMatrix *)ccoo, rr, rel_tol, max_steps, steps, relres, verbose != 0, trans);
     if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
+    return e;
+}
+const char *rh_clinsolver_solve_updated(void *h, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                        double *relres, int32_t verbose) {
+    return clinsolver_solve_updated(h, x, nx, ccoo, rhs, nr, rel_tol, max_steps, steps, relres, verbose, 0);
+}
+const char *rh_clinsolver_solve_updated_transpose(void *h, double *x, int64_t nx, void *ccoo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
+                                                  int32_t *steps, double *relres, int32_t conjugate, int32_t verbose) {
+    return clinsolver_solve_updated(h, x, nx, ccoo, rhs, nr, rel_tol, max_steps, steps, relres, verbose, conjugate == 1 ? 2 : (conjugate == 0 ? 1 : -1));
+}
+const char *rh_clinsolver_solve_transpose_many(void *h, double *x, const double *rhs, int64_t n, int64_t nrhs, int32_t conjugate) {
+    RhComplexSolver *s = (RhComplexSolver *)h;
+    if (!x || !rhs) return "solve_transpose_many needs x and right-hand sides";
+    if (conjugate != 0 && conjugate != 1) return "conjugate must be 0 (A^T) or 1 (A^H)";
+    const size_t len = n > 0 && nrhs > 0 ? 2 * (size_t)n * (size_t)nrhs : 0;
+    std::vector<double> xx(len), rr(rhs, rhs + len);
+    StrError e = s->s->solve_transpose_many(xx, rr, (size_t)(nrhs > 0 ? nrhs : 0), conjugate == 1);
+    if (!e) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
 // x, rhs: column-major n x nrhs complex arrays, interleaved (2 n nrhs doubles)
@@ -1977,21 +2024,29 @@ const char *rh_clinsolver_solve_many(void *h, double *x, const double *rhs, int6
     if (!e) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
-const char *rh_clinsolver_solve_updated_many(void *h, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
-                                             int32_t *steps, double *relres, int32_t verbose) {
+static const char *clinsolver_solve_updated_many(void *h, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                                 int32_t *steps, double *relres, int32_t verbose, int32_t trans) {
     RhComplexSolver *s = (RhComplexSolver *)h;
     if (!ccoo || !x || !rhs || !steps || !relres) return "solve_updated_many needs a matrix, x, right-hand sides, steps and relres";
     const size_t len = n > 0 && nrhs > 0 ? 2 * (size_t)n * (size_t)nrhs : 0;
     const std::vector<double> rr(rhs, rhs + len);
     std::vector<double> xx(len), rel;
     std::vector<int32_t> st;
-    StrError e = s->s->solve_updated_many(xx, *(const ComplexCooMatrix *)ccoo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0);
+    StrError e = s->s->solve_updated_many(xx, *(const ComplexCooMatrix *)ccoo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0, trans);
     if (st.size() == (size_t)nrhs) { // (the backend ran: the best iterates and the per-column figures go out with the error string of status 2 too)
         std::copy(xx.begin(), xx.end(), x);
         std::copy(st.begin(), st.end(), steps);
         std::copy(rel.begin(), rel.end(), relres);
     }
     return e;
+}
+const char *rh_clinsolver_solve_updated_many(void *h, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                             int32_t *steps, double *relres, int32_t verbose) {
+    return clinsolver_solve_updated_many(h, x, ccoo, rhs, n, nrhs, rel_tol, max_steps, steps, relres, verbose, 0);
+}
+const char *rh_clinsolver_solve_updated_transpose_many(void *h, double *x, void *ccoo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                                       int32_t *steps, double *relres, int32_t conjugate, int32_t verbose) {
+    return clinsolver_solve_updated_many(h, x, ccoo, rhs, n, nrhs, rel_tol, max_steps, steps, relres, verbose, conjugate == 1 ? 2 : (conjugate == 0 ? 1 : -1));
 }
 const char *rh_clinsolver_solve(void *h, double *x, int64_t nx, const double *rhs, int64_t nr, int32_t verbose) {
     RhComplexSolver *s = (RhComplexSolver *)h;
@@ -2085,20 +2140,28 @@ const char *rh_linsolver_inverse_entries(void *h, double *values, int64_t nent, 
 const char *rh_linsolver_inverse_entries_by_rows(void *h, double *values, int64_t nent, const int32_t *rows, const int32_t *cols, int32_t verbose) {
     return linsolver_inverse_entries(h, values, nent, rows, cols, verbose, true);
 }
-const char *rh_linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
-                                       double *relres, int32_t verbose) {
+static const char *linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                           double *relres, int32_t verbose, bool transpose) {
     RhSolver *s = (RhSolver *)h;
     SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
     if (!a) return "solve_updated is only available with Genie::Hipmf";
     if (!coo || !x || !rhs) return "solve_updated needs a matrix, x and a right-hand side";
     const std::vector<double> rr(rhs, rhs + (nr > 0 ? nr : 0));
     std::vector<double> xx((size_t)(nx > 0 ? nx : 0));
-    StrError e = a->solve_updated(xx, *(const CooMatrix *)coo, rr, rel_tol, max_steps, steps, relres, verbose != 0);
+    StrError e = a->solve_updated(xx, *(const CooMatrix *)coo, rr, rel_tol, max_steps, steps, relres, verbose != 0, transpose);
     if (xx.size() == (size_t)nx) std::copy(xx.begin(), xx.end(), x);
     return e;
 }
-const char *rh_linsolver_solve_updated_many(void *h, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
-                                            int32_t *steps, double *relres, int32_t verbose) {
+const char *rh_linsolver_solve_updated(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps, int32_t *steps,
+                                       double *relres, int32_t verbose) {
+    return linsolver_solve_updated(h, x, nx, coo, rhs, nr, rel_tol, max_steps, steps, relres, verbose, false);
+}
+const char *rh_linsolver_solve_updated_transpose(void *h, double *x, int64_t nx, void *coo, const double *rhs, int64_t nr, double rel_tol, int32_t max_steps,
+                                                 int32_t *steps, double *relres, int32_t verbose) {
+    return linsolver_solve_updated(h, x, nx, coo, rhs, nr, rel_tol, max_steps, steps, relres, verbose, true);
+}
+static const char *linsolver_solve_updated_many(void *h, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                                int32_t *steps, double *relres, int32_t verbose, bool transpose) {
     RhSolver *s = (RhSolver *)h;
     SolverHIPMF *a = dynamic_cast<SolverHIPMF *>(s->ls.actual.get());
     if (!a) return "solve_updated_many is only available with Genie::Hipmf";
@@ -2107,13 +2170,21 @@ const char *rh_linsolver_solve_updated_many(void *h, double *x, void *coo, const
     const std::vector<double> rr(rhs, rhs + len);
     std::vector<double> xx(len), rel;
     std::vector<int32_t> st;
-    StrError e = a->solve_updated_many(xx, *(const CooMatrix *)coo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0);
+    StrError e = a->solve_updated_many(xx, *(const CooMatrix *)coo, rr, (size_t)(nrhs > 0 ? nrhs : 0), rel_tol, max_steps, st, rel, verbose != 0, transpose);
     if (st.size() == (size_t)nrhs) { // (the backend ran: the best iterates and the per-column figures go out with the error string of status 2 too)
         std::copy(xx.begin(), xx.end(), x);
         std::copy(st.begin(), st.end(), steps);
         std::copy(rel.begin(), rel.end(), relres);
     }
     return e;
+}
+const char *rh_linsolver_solve_updated_many(void *h, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                            int32_t *steps, double *relres, int32_t verbose) {
+    return linsolver_solve_updated_many(h, x, coo, rhs, n, nrhs, rel_tol, max_steps, steps, relres, verbose, false);
+}
+const char *rh_linsolver_solve_updated_transpose_many(void *h, double *x, void *coo, const double *rhs, int64_t n, int64_t nrhs, double rel_tol, int32_t max_steps,
+                                                      int32_t *steps, double *relres, int32_t verbose) {
+    return linsolver_solve_updated_many(h, x, coo, rhs, n, nrhs, rel_tol, max_steps, steps, relres, verbose, true);
 }
 void rh_linsolver_times(void *h, uint64_t *ns3) {
     RhSolver *s = (RhSolver *)h;

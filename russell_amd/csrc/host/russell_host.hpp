@@ -223,12 +223,13 @@ class SolverHIPMF : public LinSolTrait {
     // extension: A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES on the device
     // (solver_hipmf_solve_updated); mat: the factorised matrix's structure with new values.  Status 2 (not converged) is an error string of
     // its own; x then holds the best iterate.  rel_tol <= 0: 1e-12, max_steps <= 0: 4 x restart; steps / relres may be null.
+    // transpose: A_new^T x = rhs (solver_hipmf_solve_updated_transpose), here and in solve_updated_many.
     StrError solve_updated(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
-                           double *relres, bool verbose);
+                           double *relres, bool verbose, bool transpose = false);
     // extension: the same for nrhs right-hand sides, 16 per blocked pass pair, every column its own iteration (solver_hipmf_solve_updated_many);
     // x, rhs: column-major ndim x nrhs; steps / relres: resized to nrhs.  The error string of status 2 when any column did not converge.
     StrError solve_updated_many(std::vector<double> &x, const CooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol, int32_t max_steps,
-                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose);
+                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose, bool transpose = false);
     // extension: the backend's diagnostic counters (HIPMF_COUNTER_* of include/russell_hipmf.h; -1 before the first factorize)
     int64_t get_counter(int32_t which) const;
 
@@ -282,15 +283,19 @@ class ComplexSolverHIPMF {
     // extension: A_new x = rhs with the factor of the last factorize as right preconditioner of a flexible GMRES in complex arithmetic
     // (complex_solver_hipmf_solve_updated); mat: the factorised matrix's structure with new values.  Status 2 (not converged) is an error
     // string of handle_hipmf_error_code; x then holds the best iterate.
+    // trans (here and in solve_updated_many): 0 the system with A_new, 1 A_new^T, 2 A_new^H (complex_solver_hipmf_solve_updated_transpose
+    // with conjugate = 0, 1)
     StrError solve_updated(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, double rel_tol, int32_t max_steps, int32_t *steps,
-                           double *relres, bool verbose);
+                           double *relres, bool verbose, int32_t trans = 0);
     // extension: nrhs right-hand sides, 16 columns per pass pair over the factor (complex_solver_hipmf_solve_many); x, rhs: column-major
     // n x nrhs complex arrays, interleaved (2 n nrhs doubles)
     StrError solve_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs);
+    // extension: nrhs columns of A^T X = B (conjugate = false) or A^H X = B, 16 per transposed pass pair (complex_solver_hipmf_solve_transpose_many)
+    StrError solve_transpose_many(std::vector<double> &x, const std::vector<double> &rhs, size_t nrhs, bool conjugate);
     // extension: solve_updated for nrhs right-hand sides, 16 per blocked pass pair, every column its own complex iteration
     // (complex_solver_hipmf_solve_updated_many); steps, relres: resized to nrhs
     StrError solve_updated_many(std::vector<double> &x, const ComplexCooMatrix &mat, const std::vector<double> &rhs, size_t nrhs, double rel_tol, int32_t max_steps,
-                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose);
+                                std::vector<int32_t> &steps, std::vector<double> &relres, bool verbose, int32_t trans = 0);
     // complex_solver_mumps.rs:262-268: compute_condition_numbers -> 1 (all eight values), compute_error_estimates -> 2 (entries 0 - 4),
     // else 0, set by every factorize; solve then goes through complex_solver_hipmf_solve_with_error_analysis, and update_stats fills
     // mumps_stats (complex_solver_mumps.rs:429-436)

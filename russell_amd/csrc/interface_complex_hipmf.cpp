@@ -310,11 +310,18 @@ int32_t complex_solver_hipmf_solve_device(struct InterfaceComplexHIPMF *h, doubl
 // Solve with new matrix values on the kept factor in complex arithmetic (Solver::solve_updated_complex).  The handle always carries a
 // signed value map -- identity after initialize / complex_solver_hipmf_factorize, the caller's triplets after set_value_map -- and this
 // call must not swap it (that would change what a later factorize_mapped reads): `mapped` has to name the map in force.
+// trans: 0 the system with A_new, 1 A_new^T (conjugated data around the A^H iteration; a complex-symmetric handle: A^T = A, the plain form),
+// 2 A_new^H (the transposed real-equivalent system)
 static int32_t c_solve_updated_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
-                                    int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+                                    int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who, int32_t trans = 0) {
     if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
     if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (trans < 0 || trans > 2) return ERROR_HIPMF_INVALID_VALUE;
+    // the transposed entry points check rel_tol here, so that their map check comes last whatever the handle (a complex-symmetric one
+    // included, which takes the plain core below); the plain entry points keep their order: the map, then rel_tol in the core
+    if (trans != 0 && !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
+    if (trans == 1 && h->sym_lower) trans = 0;
     if ((mapped != 0) != h->triplet_map) {
         h->solver.last_error = mapped != 0 ? std::string(who) + ": mapped = 1 but no triplet map is installed (complex_solver_hipmf_set_value_map)"
                                            : std::string(who) + ": mapped = 0 but the triplet map of complex_solver_hipmf_set_value_map is installed";
@@ -323,7 +330,7 @@ static int32_t c_solve_updated_body(struct InterfaceComplexHIPMF *h, double *x, 
     h->solver.opt.verbose = verbose == 1;
     int32_t st = 0;
     double rel = 0.0;
-    const int32_t code = h->solver.solve_updated_complex(x, rhs, values, rel_tol, max_steps, &st, &rel, on_device);
+    const int32_t code = h->solver.solve_updated_complex(x, rhs, values, rel_tol, max_steps, &st, &rel, on_device, trans != 0, trans == 1);
     if (steps) *steps = st;
     if (relres) *relres = rel;
     if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
@@ -349,10 +356,12 @@ int32_t complex_solver_hipmf_solve_updated_device(struct InterfaceComplexHIPMF *
 // single complex form comes last.
 static int32_t c_solve_updated_many_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values,
                                          int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device,
-                                         const char *who) {
+                                         const char *who, int32_t trans = 0) {
     if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
     if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (trans < 0 || trans > 2) return ERROR_HIPMF_INVALID_VALUE;
+    if (trans == 1 && h->sym_lower) trans = 0;
     if (nrhs < 1 || ld < h->n || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if ((mapped != 0) != h->triplet_map) {
         h->solver.last_error = mapped != 0 ? std::string(who) + ": mapped = 1 but no triplet map is installed (complex_solver_hipmf_set_value_map)"
@@ -360,7 +369,7 @@ static int32_t c_solve_updated_many_body(struct InterfaceComplexHIPMF *h, double
         return ERROR_HIPMF_INVALID_VALUE;
     }
     h->solver.opt.verbose = verbose == 1;
-    const int32_t code = h->solver.solve_updated_many_complex(x, rhs, nrhs, 2 * (int64_t)ld, values, rel_tol, max_steps, steps, relres, on_device);
+    const int32_t code = h->solver.solve_updated_many_complex(x, rhs, nrhs, 2 * (int64_t)ld, values, rel_tol, max_steps, steps, relres, on_device, trans != 0, trans == 1);
     if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
         printf("%s: %d column(s) %s: %lld column step(s) in %lld blocked pass pair(s), %lld cycle(s), %lld block(s)\n", who, nrhs,
                code == SUCCESSFUL_EXIT ? "converged" : "NOT all converged", (long long)h->solver.updated_column_steps, (long long)h->solver.updated_steps,
@@ -395,6 +404,64 @@ int32_t complex_solver_hipmf_solve_transpose(struct InterfaceComplexHIPMF *h, do
         h->solver.opt.verbose = verbose == 1;
         return h->solver.solve_transpose(x, rhs, 1, h->solver.S.n, false, conjugate == 0);
     });
+}
+
+// trans of the bodies above from the conjugate argument of the transposed forms: 1 -> A^H (2), 0 -> A^T (1), anything else is refused
+static int32_t trans_of(int32_t conjugate) { return conjugate == 1 ? 2 : (conjugate == 0 ? 1 : -1); }
+
+int32_t complex_solver_hipmf_solve_updated_transpose(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped,
+                                                     double rel_tol, int32_t max_steps, int32_t *steps, double *relres, int32_t conjugate, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_updated_body(h, x, rhs, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "complex_solver_hipmf_solve_updated_transpose",
+                                    trans_of(conjugate));
+    });
+}
+
+int32_t complex_solver_hipmf_solve_updated_transpose_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, const double *d_values,
+                                                            int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, int32_t conjugate) {
+    return guarded(h, [&]() {
+        return c_solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "complex_solver_hipmf_solve_updated_transpose_device",
+                                    trans_of(conjugate));
+    });
+}
+
+int32_t complex_solver_hipmf_solve_updated_transpose_many(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld,
+                                                          const double *values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                                          double *relres, int32_t conjugate, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_updated_many_body(h, x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps, relres, verbose, false,
+                                         "complex_solver_hipmf_solve_updated_transpose_many", trans_of(conjugate));
+    });
+}
+
+int32_t complex_solver_hipmf_solve_updated_transpose_many_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs,
+                                                                 int32_t ld, const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps,
+                                                                 int32_t *steps, double *relres, int32_t conjugate) {
+    return guarded(h, [&]() {
+        return c_solve_updated_many_body(h, d_x, d_rhs, nrhs, ld, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true,
+                                         "complex_solver_hipmf_solve_updated_transpose_many_device", trans_of(conjugate));
+    });
+}
+
+// Many columns of A^T Z = C / A^H Z = C, 16 per transposed pass pair (Solver::solve_transpose_many on the real-equivalent system; conjugate
+// = 0: every block's staged columns conjugated on entry and exit); the statistics are those of column 0.
+static int32_t c_solve_transpose_many_body(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, int32_t conjugate, C_BOOL verbose,
+                                           bool on_device) {
+    if (!h || !x || !rhs) return ERROR_NULL_POINTER;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if ((conjugate != 0 && conjugate != 1) || nrhs < 1 || ld < h->n) return ERROR_HIPMF_INVALID_VALUE;
+    if (!on_device) h->solver.opt.verbose = verbose == 1;
+    return h->solver.solve_transpose_many(x, rhs, nrhs, 2 * (int64_t)ld, on_device, conjugate == 0);
+}
+
+int32_t complex_solver_hipmf_solve_transpose_many(struct InterfaceComplexHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, int32_t conjugate,
+                                                  C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_transpose_many_body(h, x, rhs, nrhs, ld, conjugate, verbose, false); });
+}
+
+int32_t complex_solver_hipmf_solve_transpose_many_device(struct InterfaceComplexHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                         int32_t conjugate) {
+    return guarded(h, [&]() { return c_solve_transpose_many_body(h, d_x, d_rhs, nrhs, ld, conjugate, 0, true); });
 }
 
 // Sparse right-hand sides / selected rows for the complex handle (Solver::solve_sparse on the real-equivalent system): a complex column
@@ -533,6 +600,7 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_TRANSPOSED_SOLVES: return s.transposed_solves;
     case HIPMF_COUNTER_ANALYSIS_SOLVES: return s.analysis_solves;
     case HIPMF_COUNTER_TRANSPOSED_KRYLOV_ITERATIONS: return s.krylov_iterations_t;
+    case HIPMF_COUNTER_TRANSPOSED_BLOCKS: return s.transposed_blocks;
     case HIPMF_COUNTER_PRUNED_FWD_FRONTS: return s.pruned_fwd_fronts;
     case HIPMF_COUNTER_PRUNED_BWD_FRONTS: return s.pruned_bwd_fronts;
     case HIPMF_COUNTER_PRUNED_BLOCKS: return s.pruned_blocks;

@@ -574,14 +574,15 @@ int32_t solver_hipmf_inverse_entries_by_rows(struct InterfaceHIPMF *h, int32_t n
 // Solve with new matrix values on the kept factor (Solver::solve_updated): flexible GMRES on the device, the factor of the last
 // factorize as right preconditioner.  Status codes in the order of solver_hipmf_solve_sparse: NULL pointers, initialize, factorize.
 static int32_t solve_updated_body(struct InterfaceHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
-                                  int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+                                  int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who, bool transposed = false) {
     if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
     if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
     h->solver.opt.verbose = verbose == 1;
     int32_t st = 0;
     double rel = 0.0;
-    const int32_t code = h->solver.solve_updated(x, rhs, values, mapped != 0, rel_tol, max_steps, &st, &rel, on_device);
+    // (a symmetric matrix that was expanded to a general one inside the handle still has A^T = A: the non-transposed form)
+    const int32_t code = h->solver.solve_updated(x, rhs, values, mapped != 0, rel_tol, max_steps, &st, &rel, on_device, transposed && !h->expanded);
     if (steps) *steps = st;
     if (relres) *relres = rel;
     if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
@@ -602,12 +603,13 @@ int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *h, double *d_x,
 
 // The same for nrhs columns (Solver::solve_updated_many): blocks of 16 columns, every column its own flexible GMRES, in lockstep.
 static int32_t solve_updated_many_body(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values, int32_t mapped,
-                                       double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who) {
+                                       double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who,
+                                       bool transposed = false) {
     if (!h || !x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
     if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
     h->solver.opt.verbose = verbose == 1;
-    const int32_t code = h->solver.solve_updated_many(x, rhs, nrhs, ld, values, mapped != 0, rel_tol, max_steps, steps, relres, on_device);
+    const int32_t code = h->solver.solve_updated_many(x, rhs, nrhs, ld, values, mapped != 0, rel_tol, max_steps, steps, relres, on_device, transposed && !h->expanded);
     if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
         printf("%s: %d column(s) %s: %lld column step(s) in %lld blocked pass pair(s), %lld cycle(s), %lld block(s)\n", who, nrhs,
                code == SUCCESSFUL_EXIT ? "converged" : "NOT all converged", (long long)h->solver.updated_column_steps, (long long)h->solver.updated_steps,
@@ -626,6 +628,38 @@ int32_t solver_hipmf_solve_updated_many_device(struct InterfaceHIPMF *h, double 
                                                int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
     return guarded(h, [&]() {
         return solve_updated_many_body(h, d_x, d_rhs, nrhs, ld, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_many_device");
+    });
+}
+
+// The transposed forms, A_new^T x = rhs (Solver::solve_updated / solve_updated_many with the transposed operator): the same bodies.
+int32_t solver_hipmf_solve_updated_transpose(struct InterfaceHIPMF *h, double *x, const double *rhs, const double *values, int32_t mapped, double rel_tol,
+                                             int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_updated_body(h, x, rhs, values, mapped, rel_tol, max_steps, steps, relres, verbose, false, "solver_hipmf_solve_updated_transpose", true);
+    });
+}
+
+int32_t solver_hipmf_solve_updated_transpose_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, const double *d_values, int32_t mapped,
+                                                    double rel_tol, int32_t max_steps, int32_t *steps, double *relres) {
+    return guarded(h, [&]() {
+        return solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_transpose_device", true);
+    });
+}
+
+int32_t solver_hipmf_solve_updated_transpose_many(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values,
+                                                  int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_updated_many_body(h, x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps, relres, verbose, false,
+                                       "solver_hipmf_solve_updated_transpose_many", true);
+    });
+}
+
+int32_t solver_hipmf_solve_updated_transpose_many_device(struct InterfaceHIPMF *h, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                         const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
+                                                         double *relres) {
+    return guarded(h, [&]() {
+        return solve_updated_many_body(h, d_x, d_rhs, nrhs, ld, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true,
+                                       "solver_hipmf_solve_updated_transpose_many_device", true);
     });
 }
 

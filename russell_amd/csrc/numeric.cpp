@@ -26,6 +26,7 @@
 #include "kernels_krylov_blocked.hpp"
 #include "kernels_krylov_complex.hpp"
 #include "kernels_krylov_complex_blocked.hpp"
+#include "kernels_krylov_transpose.hpp"
 #include "kernels_error_analysis_complex.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -3457,6 +3458,22 @@ struct UpdatedComplex {
     }
 };
 
+// The columns of a block form one at a time through its single form (no memory for the block buffers of the transposed pass pair):
+// `one(c)` solves column c; the counters of the call are the sums over the columns, updated_blocks = 0.
+template <class F>
+int32_t updated_one_by_one(Solver &s, int32_t nrhs, F one) {
+    bool all_converged = true;
+    int64_t steps = 0, cycles = 0;
+    for (int32_t c = 0; c < nrhs; c++) {
+        const int32_t code = one(c);
+        if (code != SUCCESSFUL_EXIT && code != WARNING_NOT_CONVERGED) return code;
+        all_converged = all_converged && code == SUCCESSFUL_EXIT;
+        steps += s.updated_steps, cycles += s.updated_cycles;
+    }
+    s.updated_steps = s.updated_column_steps = steps, s.updated_cycles = cycles, s.updated_blocks = 0;
+    return all_converged ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
+}
+
 // The transposed pass pair on one vector (kernels_solve_transpose.hpp) or on a block of TR_KB (kernels_solve_transpose_blocked.hpp): the
 // six kernels, the workspace, and the column stride xs of the block, which the blocked kernels take right after the vector -- their last
 // pointer (launch; the small-front kernels end with the leading dimension of their LDS panel: launch_ld).
@@ -3606,6 +3623,55 @@ struct EaComplex {
 
 } // namespace
 
+// The operator of the single-column core and of the block driver, next to the arithmetic: A_new (the stream SpMV on the row blocks of
+// initialize, preconditioner solve_core) or A_new^T (kernels_krylov_transpose.hpp on the row blocks of A^T that tr_prepare() cuts,
+// preconditioner the unrefined transposed pass pair: level-synchronous launches that wait for nothing and take no device gate).  An
+// operator gives the preconditioner call on C contiguous columns, the product and the residual, single and blocked, and where the
+// residual's partial sums go: `blocks` slots per sum, in the Krylov kernels' buffer (plain) or in d_tt_part.  Both read d_up_vals.
+struct Solver::OpPlain {
+    static constexpr const char *tag = "";
+    static int32_t blocks(const Solver &s) { return s.spmv_blocks; }
+    static double *part(Solver &, double *krylov_part) { return krylov_part; }
+    static int64_t pcol(const Solver &, int64_t krylov_pcol) { return krylov_pcol; }
+    static int32_t precond(Solver &s, double *z, const double *v, int32_t C) { return s.solve_core(z, v, C, s.S.n, true); }
+    static void product(Solver &s, hipStream_t st, const double *z, double *w) {
+        hipLaunchKernelGGL(k_spmv_stream<false>, dim3(s.spmv_blocks), dim3(256), 0, st, s.d_row_blk, s.d_rp, s.d_ci, s.d_up_vals, s.d_tptr, s.d_tidx, s.d_arow, 1.0, z,
+                           (const double *)nullptr, w, (unsigned long long *)nullptr);
+    }
+    static void residual(Solver &s, hipStream_t st, const double *x, const double *b, double *r, double *part) {
+        hipLaunchKernelGGL(k_kry_residual, dim3(s.spmv_blocks), dim3(256), 0, st, s.d_row_blk, s.d_rp, s.d_ci, s.d_up_vals, s.d_tptr, s.d_tidx, s.d_arow, x, b, r, part);
+    }
+    static void product_blk(Solver &s, hipStream_t st, int64_t n, const double *Z, double *W, int32_t C, uint32_t mask) {
+        hipLaunchKernelGGL(k_kryb_spmv, dim3(s.spmv_blocks), dim3(256), 0, st, s.d_row_blk, s.d_rp, s.d_ci, s.d_up_vals, s.d_tptr, s.d_tidx, s.d_arow, n, Z, W, C, mask);
+    }
+    static void residual_blk(Solver &s, hipStream_t st, int64_t n, const double *X, int64_t xstr, const double *B, int64_t bstr, double *R, int32_t C, uint32_t mask,
+                             double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_kryb_residual, dim3(s.spmv_blocks), dim3(256), 0, st, s.d_row_blk, s.d_rp, s.d_ci, s.d_up_vals, s.d_tptr, s.d_tidx, s.d_arow, n, X, xstr, B, bstr,
+                           R, C, mask, part, pcol);
+    }
+};
+struct Solver::OpTransposed { // (after tr_prepare(); the blocked launches after tr_prepare_blocked())
+    static constexpr const char *tag = " (transposed)";
+    static int32_t blocks(const Solver &s) { return s.tt_blocks; }
+    static double *part(Solver &s, double *) { return s.d_tt_part; }
+    static int64_t pcol(const Solver &s, int64_t) { return 2 * (int64_t)s.tt_blocks; }
+    static int32_t precond(Solver &s, double *z, const double *v, int32_t C) { return C == 1 ? s.tr_pass(z, v) : s.tr_pass_blk(z, v, C); }
+    static void product(Solver &s, hipStream_t st, const double *z, double *w) {
+        hipLaunchKernelGGL(k_kry_spmv_t, dim3(s.tt_blocks), dim3(256), 0, st, s.d_ttblk, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_up_vals, z, w);
+    }
+    static void residual(Solver &s, hipStream_t st, const double *x, const double *b, double *r, double *part) {
+        hipLaunchKernelGGL(k_kry_residual_t, dim3(s.tt_blocks), dim3(256), 0, st, s.d_ttblk, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_up_vals, x, b, r, part);
+    }
+    static void product_blk(Solver &s, hipStream_t st, int64_t n, const double *Z, double *W, int32_t C, uint32_t mask) {
+        hipLaunchKernelGGL(k_kryb_spmv_t, dim3(s.tt_blocks), dim3(256), 0, st, s.d_ttblk, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_up_vals, n, Z, W, C, mask);
+    }
+    static void residual_blk(Solver &s, hipStream_t st, int64_t n, const double *X, int64_t xstr, const double *B, int64_t bstr, double *R, int32_t C, uint32_t mask,
+                             double *part, int64_t pcol) {
+        hipLaunchKernelGGL(k_kryb_residual_t, dim3(s.tt_blocks), dim3(256), 0, st, s.d_ttblk, s.d_ttptr, s.d_ttrow, s.d_ttmap, s.d_up_vals, n, X, xstr, B, bstr, R, C, mask,
+                           part, pcol);
+    }
+};
+
 // ---- solve with new matrix values on the kept factor (solver_hipmf_solve_updated, complex_solver_hipmf_solve_updated) ----
 // The callers of this backend change the VALUES of the matrix often and by little (a new step size scales the shift of gamma M - J, a
 // Jacobian moves in a few rows): instead of a factorisation the old factor M serves as RIGHT preconditioner of a flexible GMRES on
@@ -3624,9 +3690,13 @@ struct EaComplex {
 // and residual are the real form's launches; the coefficients are complex, D = 2 doubles each: h_j = sum conj(v_j,i) w_i (k_zkry_dots:
 // two sums per basis vector, k_kry_reduce over 2 nv columns leaves them interleaved), k_zkry_update, k_zkry_combine.  The preconditioner
 // only has to give SOME vector: a factor that is not exactly complex-linear (HIPMF_COMPLEX_PAIRS=0, replaced pivots) is merely weaker.
-template <class P>
+// The operator is a second axis, O: OpPlain is the text above; OpTransposed solves A_new^T x = b with z_k = M^{-T} v_k (tr_pass) and
+// w = A_new^T z_k, r = b - A_new^T x from kernels_krylov_transpose.hpp -- Arnoldi, CGS2, the records, the least-squares problem and
+// the cycle logic are shared.  conj_pairs (complex A^T through the A^H iteration): b is conjugated into the staging vector on entry, x
+// on exit.
+template <class P, class O>
 int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
-                                   double *relres_out, bool on_device) {
+                                   double *relres_out, bool on_device, bool conj_pairs) {
     typedef typename P::scalar T;
     constexpr int32_t D = P::D;
     DeviceScope dev_scope(device);
@@ -3668,17 +3738,19 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
     // the operator's values: the staging factorize gives its own, into d_up_vals
     int32_t code = stage_values(d_up_vals, values, mapped, on_device);
     if (code != SUCCESSFUL_EXIT) return code;
-    if (!on_device) {
-        HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    const dim3 gk((unsigned)nblk), b256(256), gn((unsigned)((n + 255) / 256));
+    if (!on_device || conj_pairs) { // (the caller's device vector is read where it is unless it has to be conjugated)
+        HIPC(hipMemcpyAsync(d_up_vec + 3 * (size_t)n, rhs, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        if (conj_pairs) hipLaunchKernelGGL(k_tr_conj, gn, b256, 0, STREAM, n, d_up_vec + 3 * (size_t)n);
         d_bb = d_up_vec + 3 * (size_t)n;
     }
     HIPC(hipMemsetAsync(d_xx, 0, nb, STREAM), ERROR_HIP_MEMCPY);
 
-    const dim3 gk((unsigned)nblk), b256(256);
+    double *const d_rpart = O::part(*this, d_up_part); // the partial sums of the residual
     // r = b - A_new x with its two sums on the host (one synchronisation)
     auto residual = [&](double &rr, double &bb) -> int32_t {
-        hipLaunchKernelGGL(k_kry_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, d_xx, d_bb, d_r, d_up_part);
-        hipLaunchKernelGGL(k_kry_reduce, dim3(2), b256, 0, STREAM, d_up_part, spmv_blocks, d_res);
+        O::residual(*this, STREAM, d_xx, d_bb, d_r, d_rpart);
+        hipLaunchKernelGGL(k_kry_reduce, dim3(2), b256, 0, STREAM, (const double *)d_rpart, O::blocks(*this), d_res);
         HIPC(hipMemcpyAsync(h_res, d_res, 2 * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
         HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
         rr = h_res[0], bb = h_res[1];
@@ -3694,6 +3766,10 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
     auto finish = [&](int32_t code, double relres) -> int32_t {
         if (steps_out) *steps_out = (int32_t)updated_steps;
         if (relres_out) *relres_out = relres;
+        if (conj_pairs && updated_steps > 0) { // (no step: x is the zeros of the entry, kept +0.0 as the other forms return them)
+            hipLaunchKernelGGL(k_tr_conj, gn, b256, 0, STREAM, n, d_xx);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        }
         if (!on_device) HIPC(hipMemcpy(x, d_xx, nb, hipMemcpyDeviceToHost), ERROR_HIP_MEMCPY);
         HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
         return code;
@@ -3720,11 +3796,10 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
                 double *const zk = d_up_Z + (size_t)k * n;
                 const double *const vk = d_up_V + (size_t)k * n;
                 timer.mark(0);
-                code = solve_core(zk, vk, 1, n, true); // z_k = M^{-1} v_k
+                code = O::precond(*this, zk, vk, 1); // z_k = M^{-1} v_k
                 if (code != SUCCESSFUL_EXIT) break;
                 timer.mark(1);
-                hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, (const double *)zk,
-                                   (const double *)nullptr, d_w, (unsigned long long *)nullptr); // w = A_new z_k
+                O::product(*this, STREAM, zk, d_w); // w = A_new z_k
                 timer.mark(2);
                 const int32_t nv = k + 1;
                 double *const d_nrm = d_h + 2 * D * (size_t)nv; // the squared norms after the two rounds
@@ -3751,7 +3826,7 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
                 const double hn = sqrt(h_rec[nrec - 1]);
                 lsq.push(k, hcol.data(), hn);
                 if (guard.verbose)
-                    fprintf(stderr, "hipmf: %s: cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label, (long long)updated_cycles, k + 1, std::abs(lsq.g[(size_t)k + 1]), bnorm);
+                    fprintf(stderr, "hipmf: %s%s: cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label, O::tag, (long long)updated_cycles, k + 1, std::abs(lsq.g[(size_t)k + 1]), bnorm);
                 k++;
                 if (std::abs(lsq.g[(size_t)k]) <= par.tol * bnorm || !(hn > 0.0)) break;
             }
@@ -3763,7 +3838,7 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
             const double before = rnorm;
             code = residual(rr, bb);
             if (code != SUCCESSFUL_EXIT) break;
-            if (guard.verbose) fprintf(stderr, "hipmf: %s: cycle %lld: |r| %.3e -> %.3e\n", P::label, (long long)updated_cycles, before, sqrt(rr));
+            if (guard.verbose) fprintf(stderr, "hipmf: %s%s: cycle %lld: |r| %.3e -> %.3e\n", P::label, O::tag, (long long)updated_cycles, before, sqrt(rr));
             if (!(sqrt(rr) < before)) { // no gain (or not a number): the cycle is taken back, x is the best iterate
                 code = combine(k, -1.0);
                 if (code == SUCCESSFUL_EXIT) code = residual(rr, bb);
@@ -3778,25 +3853,35 @@ int32_t Solver::solve_updated_core(double *x, const double *rhs, const double *v
 }
 
 int32_t Solver::solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps_out,
-                              double *relres_out, bool on_device) {
+                              double *relres_out, bool on_device, bool transposed) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
-    return solve_updated_core<UpdatedReal>(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+    if (!transposed || S.sym_mode || d_tptr) // (A^T = A: L D L^T fronts, symmetric storage)
+        return solve_updated_core<UpdatedReal, OpPlain>(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device, false);
+    DeviceScope dev_scope(device);
+    const int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    return solve_updated_core<UpdatedReal, OpTransposed>(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device, false);
 }
 
 // values: always the inputs of the installed (signed) value map, gathered as factorize_mapped gathers them
 int32_t Solver::solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps_out,
-                                      double *relres_out, bool on_device) {
+                                      double *relres_out, bool on_device, bool transposed, bool conj_pairs) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs || !values) return ERROR_NULL_POINTER;
     if (!std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if (nnz_in < 1 || (S.n & 1) || d_emap) return ERROR_HIPMF_INVALID_VALUE; // the complex handle: a value map, pairs, a general pattern
     updated_complex = true;
-    return solve_updated_core<UpdatedComplex>(x, rhs, values, true, rel_tol, max_steps, steps_out, relres_out, on_device);
+    if (!transposed || S.sym_mode || d_tptr) // (a symmetric real-equivalent form: A^H = A)
+        return solve_updated_core<UpdatedComplex, OpPlain>(x, rhs, values, true, rel_tol, max_steps, steps_out, relres_out, on_device, conj_pairs);
+    DeviceScope dev_scope(device);
+    const int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    return solve_updated_core<UpdatedComplex, OpTransposed>(x, rhs, values, true, rel_tol, max_steps, steps_out, relres_out, on_device, conj_pairs);
 }
 
 // ---- the same for a block of right-hand sides (solver_hipmf_solve_updated_many; kernels_krylov_blocked.hpp) ----
@@ -3808,47 +3893,71 @@ int32_t Solver::solve_updated_complex(double *x, const double *rhs, const double
 // zeros.  At the end of a cycle (k == m or every column parked) every column gets its own back substitution over its own count of
 // directions, one combine and one residual launch serve the block; a column is finished for the call when its TRUE residual meets the
 // tolerance, when the cycle brought no gain (taken back) or when its steps are used up.  The block goes on with the others.
+// transposed: the block form also needs the buffers of the blocked transposed pass pair; without memory for them the columns go through
+// the single transposed form one at a time, as solve_transpose_many does.
 int32_t Solver::solve_updated_many(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol,
-                                   int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device) {
+                                   int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device, bool transposed) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs || !values) return ERROR_NULL_POINTER;
     if (nrhs < 1 || ld < S.n || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if (mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
     if (nrhs == 1) {
-        const int32_t code = solve_updated(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+        const int32_t code = solve_updated(x, rhs, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device, transposed);
         updated_blocks = 0, updated_column_steps = updated_steps;
         return code;
     }
-    return solve_updated_many_core<UpdatedReal>(x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device);
+    if (!transposed || S.sym_mode || d_tptr)
+        return solve_updated_many_core<UpdatedReal, OpPlain>(x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device, false);
+    DeviceScope dev_scope(device);
+    const int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    if (tr_prepare_blocked() != SUCCESSFUL_EXIT)
+        return updated_one_by_one(*this, nrhs, [&](int32_t c) {
+            return solve_updated(x + (int64_t)c * ld, rhs + (int64_t)c * ld, values, mapped, rel_tol, max_steps, steps_out ? steps_out + c : nullptr,
+                                 relres_out ? relres_out + c : nullptr, on_device, true);
+        });
+    return solve_updated_many_core<UpdatedReal, OpTransposed>(x, rhs, nrhs, ld, values, mapped, rel_tol, max_steps, steps_out, relres_out, on_device, false);
 }
 
 // The block form for the real-equivalent system of a COMPLEX matrix (complex_solver_hipmf_solve_updated_many): the same lockstep
 // iteration with complex coefficients per column (kernels_krylov_complex_blocked.hpp), on the conditions of solve_updated_complex.
 // ld counts doubles (twice the caller's complex leading dimension, so every column starts on a complex element).
 int32_t Solver::solve_updated_many_complex(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, double rel_tol, int32_t max_steps,
-                                           int32_t *steps_out, double *relres_out, bool on_device) {
+                                           int32_t *steps_out, double *relres_out, bool on_device, bool transposed, bool conj_pairs) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs || !values) return ERROR_NULL_POINTER;
     if (nrhs < 1 || ld < S.n || (ld & 1) || !std::isfinite(rel_tol)) return ERROR_HIPMF_INVALID_VALUE;
     if (nnz_in < 1 || (S.n & 1) || d_emap) return ERROR_HIPMF_INVALID_VALUE; // the complex handle: a value map, pairs, a general pattern
     if (nrhs == 1) {
-        const int32_t code = solve_updated_complex(x, rhs, values, rel_tol, max_steps, steps_out, relres_out, on_device);
+        const int32_t code = solve_updated_complex(x, rhs, values, rel_tol, max_steps, steps_out, relres_out, on_device, transposed, conj_pairs);
         updated_blocks = 0, updated_column_steps = updated_steps;
         return code;
     }
     updated_complex = true;
-    return solve_updated_many_core<UpdatedComplex>(x, rhs, nrhs, ld, values, true, rel_tol, max_steps, steps_out, relres_out, on_device);
+    if (!transposed || S.sym_mode || d_tptr)
+        return solve_updated_many_core<UpdatedComplex, OpPlain>(x, rhs, nrhs, ld, values, true, rel_tol, max_steps, steps_out, relres_out, on_device, conj_pairs);
+    DeviceScope dev_scope(device);
+    const int32_t code = tr_prepare();
+    if (code != SUCCESSFUL_EXIT) return code;
+    if (tr_prepare_blocked() != SUCCESSFUL_EXIT)
+        return updated_one_by_one(*this, nrhs, [&](int32_t c) {
+            return solve_updated_complex(x + (int64_t)c * ld, rhs + (int64_t)c * ld, values, rel_tol, max_steps, steps_out ? steps_out + c : nullptr,
+                                         relres_out ? relres_out + c : nullptr, on_device, true, conj_pairs);
+        });
+    return solve_updated_many_core<UpdatedComplex, OpTransposed>(x, rhs, nrhs, ld, values, true, rel_tol, max_steps, steps_out, relres_out, on_device, conj_pairs);
 }
 
 // One driver serves both arithmetics, as solve_updated_core does: the policy P gives the three blocked launches that differ and the
 // doubles per coefficient D, which size the step's record (2 D nv + 2 doubles per column), the partial-sum slots (D (m + 1) nblk per
 // column), the restart bound (n / D), y (D m doubles per column) and the scalar of the per-column least-squares problems.  With D = 1
 // every launch, its order and its arguments are those of the real driver before the complex form existed.
-template <class P>
+// O is the operator axis of solve_updated_core: the blocked preconditioner call, product and residual.  conj_pairs: the block's
+// right-hand sides are conjugated into the staging block on entry, its solutions on exit (k_tr_conj_cols).
+template <class P, class O>
 int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol,
-                                        int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device) {
+                                        int32_t max_steps, int32_t *steps_out, double *relres_out, bool on_device, bool conj_pairs) {
     typedef typename P::scalar T;
     constexpr int32_t D = P::D;
     DeviceScope dev_scope(device);
@@ -3903,6 +4012,9 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
     std::vector<GivensLsq<T>> lsq((size_t)KRYB_COLS, GivensLsq<T>(m)); // per column of a block
     std::vector<T> crec(2 * (size_t)m), hcol((size_t)m), y((size_t)m);
     const int64_t ystr = (int64_t)D * m; // between the coefficients y of two columns
+    double *const d_rpart = O::part(*this, d_ub_part); // the partial sums of the residuals and their slots per column
+    const int64_t rpcol = O::pcol(*this, pcol);
+    const bool stage_b = !on_device || conj_pairs; // (the caller's device block is read where it is unless it has to be conjugated)
     {
         const NestedSolveGuard guard(*this);
         guard.unrefined_quiet();
@@ -3913,21 +4025,22 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
             updated_blocks++;
             double *const d_w = d_ub_vec, *const d_r = d_ub_vec + (size_t)C * n;
             double *const d_xx = on_device ? x + (int64_t)j0 * ld : d_ub_vec + 2 * (size_t)ub_cols * n;
-            const double *const d_bb = on_device ? rhs + (int64_t)j0 * ld : d_ub_vec + 3 * (size_t)ub_cols * n;
-            const int64_t xstr = on_device ? ld : (int64_t)n;
-            if (!on_device)
+            const double *const d_bb = stage_b ? d_ub_vec + 3 * (size_t)ub_cols * n : rhs + (int64_t)j0 * ld;
+            const int64_t xstr = on_device ? ld : (int64_t)n, bstr = stage_b ? (int64_t)n : ld;
+            if (stage_b)
                 for (int32_t c = 0; c < C && code == SUCCESSFUL_EXIT; c++)
-                    if (hipMemcpyAsync(d_ub_vec + 3 * (size_t)ub_cols * n + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, hipMemcpyHostToDevice, STREAM) != hipSuccess)
+                    if (hipMemcpyAsync(d_ub_vec + 3 * (size_t)ub_cols * n + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                       STREAM) != hipSuccess)
                         code = ERROR_HIP_MEMCPY;
             if (code != SUCCESSFUL_EXIT) break;
-            const dim3 gk((unsigned)nblk, (unsigned)C);
+            const dim3 gk((unsigned)nblk, (unsigned)C), gconj((unsigned)((n / 2 + 255) / 256), (unsigned)C);
+            if (conj_pairs) hipLaunchKernelGGL(k_tr_conj_cols, gconj, b256, 0, STREAM, n, d_ub_vec + 3 * (size_t)ub_cols * n, (int64_t)n, all, C);
             hipLaunchKernelGGL(k_kryb_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)nullptr, (int64_t)0, (const double *)nullptr, (int64_t)0, d_xx, xstr, 0u, all); // x = 0
 
             // R_c = B_c - A_new X_c and its two sums for the columns of `mask`, on the host after one synchronisation
             auto residual = [&](uint32_t mask) -> int32_t {
-                hipLaunchKernelGGL(k_kryb_residual, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)d_xx,
-                                   xstr, d_bb, xstr, d_r, C, mask, (double *)d_ub_part, pcol);
-                hipLaunchKernelGGL(k_kryb_reduce, dim3(2, (unsigned)C), b256, 0, STREAM, (const double *)d_ub_part, pcol, spmv_blocks, mask, d_res, (int64_t)2);
+                O::residual_blk(*this, STREAM, (int64_t)n, (const double *)d_xx, xstr, d_bb, bstr, d_r, C, mask, d_rpart, rpcol);
+                hipLaunchKernelGGL(k_kryb_reduce, dim3(2, (unsigned)C), b256, 0, STREAM, (const double *)d_rpart, rpcol, O::blocks(*this), mask, d_res, (int64_t)2);
                 HIPC(hipMemcpyAsync(h_res, d_res, 2 * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
                 HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
                 return SUCCESSFUL_EXIT;
@@ -3974,11 +4087,10 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
                     double *const zk = d_ub_Z + (size_t)k * vstr;
                     const double *const vk = d_ub_V + (size_t)k * vstr;
                     timer.mark(0);
-                    code = solve_core(zk, vk, C, n, true); // Z_k = M^{-1} V_k: one blocked pass pair
+                    code = O::precond(*this, zk, vk, C); // Z_k = M^{-1} V_k: one blocked pass pair
                     if (code != SUCCESSFUL_EXIT) break;
                     timer.mark(1);
-                    hipLaunchKernelGGL(k_kryb_spmv, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, (int64_t)n, (const double *)zk, d_w, C,
-                                       act); // W = A_new Z_k
+                    O::product_blk(*this, STREAM, (int64_t)n, (const double *)zk, d_w, C, act); // W = A_new Z_k
                     timer.mark(2);
                     const int32_t nv = k + 1;
                     const int64_t rstr = 2 * (int64_t)D * nv + 2; // the step's record of a column: both coefficient sets, the two squared norms
@@ -4016,7 +4128,7 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
                         lsq[(size_t)c].push(k, hcol.data(), hn);
                         const double est = std::abs(lsq[(size_t)c].g[(size_t)k + 1]);
                         if (guard.verbose)
-                            fprintf(stderr, "hipmf: %s: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label_many, j0 + c, (long long)updated_cycles, k + 1, est,
+                            fprintf(stderr, "hipmf: %s%s: column %d cycle %lld step %d: residual estimate %.3e (|b| = %.3e)\n", P::label_many, O::tag, j0 + c, (long long)updated_cycles, k + 1, est,
                                     bnorm[c]);
                         kc[c] = k + 1;
                         if (est <= par.tol * bnorm[c] || !(hn > 0.0) || steps[c] >= par.step_limit) newly |= 1u << c;
@@ -4050,7 +4162,7 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
                 for (int32_t c = 0; c < C; c++) {
                     if (!((moved >> c) & 1u)) continue;
                     const double now = sqrt(h_res[2 * c]);
-                    if (guard.verbose) fprintf(stderr, "hipmf: %s: column %d cycle %lld: |r| %.3e -> %.3e\n", P::label_many, j0 + c, (long long)updated_cycles, rnorm[c], now);
+                    if (guard.verbose) fprintf(stderr, "hipmf: %s%s: column %d cycle %lld: |r| %.3e -> %.3e\n", P::label_many, O::tag, j0 + c, (long long)updated_cycles, rnorm[c], now);
                     if (!(now < rnorm[c])) { // no gain (or not a number): the column's cycle is taken back, x_c is the best iterate
                         back |= 1u << c, done |= 1u << c;
                         continue;
@@ -4070,6 +4182,12 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
                 }
             }
             if (code != SUCCESSFUL_EXIT) break;
+            if (conj_pairs) { // (a column without a step is the zeros of the entry, kept +0.0 as the other forms return them)
+                uint32_t stepped = 0;
+                for (int32_t c = 0; c < C; c++)
+                    if (steps[c] > 0) stepped |= 1u << c;
+                if (stepped) hipLaunchKernelGGL(k_tr_conj_cols, gconj, b256, 0, STREAM, n, d_xx, xstr, stepped, C);
+            }
             for (int32_t c = 0; c < C; c++) {
                 const double rel = nan_rhs[c] ? NAN : (bnorm[c] > 0.0 ? rnorm[c] / bnorm[c] : 0.0);
                 if (steps_out) steps_out[j0 + c] = steps[c];
@@ -4307,6 +4425,18 @@ int32_t Solver::tr_prepare() {
     HIPC(d_ttptr.upload(tp), ERROR_HIP_MALLOC);
     HIPC(d_ttrow.upload(trow), ERROR_HIP_MALLOC);
     HIPC(d_ttmap.upload(tmap), ERROR_HIP_MALLOC);
+    {
+        // the row blocks of the transposed solve_updated products: consecutive rows of A^T with at most KRYT_CAP stored entries (a
+        // longer row -- a dense column of A -- stands alone, closed by the next row)
+        std::vector<int32_t> tb(1, 0);
+        int32_t start = 0;
+        for (int32_t i = 0; i < n; i++)
+            if (tp[(size_t)i + 1] - tp[(size_t)start] > KRYT_CAP && i > start) tb.push_back(i), start = i;
+        tb.push_back(n);
+        tt_blocks = (int32_t)tb.size() - 1;
+        HIPC(d_ttblk.upload(tb), ERROR_HIP_MALLOC);
+        HIPC(d_tt_part.alloc(2 * (size_t)std::max(tt_blocks, 1) * KRYB_COLS), ERROR_HIP_MALLOC);
+    }
     HIPC(d_work_t.alloc((size_t)std::max<int64_t>(work_up, 1) + 64), ERROR_HIP_MALLOC);
     HIPC(d_tvec.alloc(6 * (size_t)n), ERROR_HIP_MALLOC);
     HIPC(d_tnrm.alloc(2), ERROR_HIP_MALLOC);
@@ -4353,6 +4483,20 @@ int32_t Solver::tr_pass(double *y, const double *v) {
     int32_t code = run_transposed<TrSingle>(xp);
     if (code != SUCCESSFUL_EXIT) return code;
     hipLaunchKernelGGL(k_perm_out, g, b, 0, STREAM, n, d_rperm, d_rs, xp, y, 0);
+    return SUCCESSFUL_EXIT;
+}
+
+// the same for C <= TR_KB contiguous columns at stride n through the blocked kernels (after tr_prepare_blocked(); the entry kernel fills
+// the columns from C on with zeros)
+int32_t Solver::tr_pass_blk(double *Z, const double *V, int32_t C) {
+    const int32_t n = S.n;
+    const dim3 gp((n + 255) / 256, TR_KB / PERM_CW), b(256);
+    const uint64_t all = (1ull << C) - 1ull;
+    double *XP = d_tblk + 2 * (size_t)n * TR_KB;
+    hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, V, (int64_t)n, XP, (int64_t)n, all, C);
+    const int32_t code = run_transposed<TrBlocked>(XP);
+    if (code != SUCCESSFUL_EXIT) return code;
+    hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, Z, (int64_t)n, 0, all, C);
     return SUCCESSFUL_EXIT;
 }
 
@@ -4506,18 +4650,20 @@ int32_t Solver::tr_prepare_blocked() {
 // nrhs columns of A^T X = B, TR_KB at a time.  Per block: entry (column permutation and scaling), the two passes, exit (row ones), then
 // the refinement rule for the block's columns (tr_refine), then the transposed FGMRES rescue of solve_transpose for the columns that need
 // it.  One column, A^T = A, HIPMF_TRANSPOSE_BLOCKED=0 or no memory for the block buffers: solve_transpose (transposed_blocks stays 0).
-int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device) {
+// conj_pairs (the complex twin's A^T through the A^H solve of the real-equivalent system): every block's right-hand sides are staged and
+// conjugated on entry, its solutions on exit (k_tr_conj_cols); refinement and rescue run in between, on the A^H system.
+int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs) {
     transposed_blocks = 0;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !rhs) return ERROR_NULL_POINTER;
     if (nrhs < 1 || ldx < S.n) return ERROR_HIPMF_INVALID_VALUE;
-    if (nrhs == 1 || S.sym_mode || d_tptr) return solve_transpose(x, rhs, nrhs, ldx, on_device);
+    if (nrhs == 1 || S.sym_mode || d_tptr) return solve_transpose(x, rhs, nrhs, ldx, on_device, conj_pairs);
     DeviceScope dev_scope(device);
     {
         const int32_t code = tr_prepare();
         if (code != SUCCESSFUL_EXIT) return code;
         const char *e = getenv("HIPMF_TRANSPOSE_BLOCKED");
-        if ((e && e[0] == '0') || tr_prepare_blocked() != SUCCESSFUL_EXIT) return solve_transpose(x, rhs, nrhs, ldx, on_device);
+        if ((e && e[0] == '0') || tr_prepare_blocked() != SUCCESSFUL_EXIT) return solve_transpose(x, rhs, nrhs, ldx, on_device, conj_pairs);
     }
     const int32_t n = S.n, nstep = opt.refinement_nstep;
     const size_t nb = sizeof(double) * (size_t)n, nz = (size_t)n;
@@ -4533,9 +4679,11 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
         const double *B = rhs + (int64_t)j0 * ldx;
         double *X = x + (int64_t)j0 * ldx;
         int64_t bs = ldx, xs = ldx;
-        if (!on_device || aliased) {
+        const dim3 gconj((unsigned)((n / 2 + 255) / 256), (unsigned)nk);
+        if (!on_device || aliased || conj_pairs) {
             for (int32_t c = 0; c < nk; c++)
                 HIPC(hipMemcpyAsync(TB + nz * c, B + (int64_t)c * ldx, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            if (conj_pairs) hipLaunchKernelGGL(k_tr_conj_cols, gconj, b, 0, STREAM, n, TB, (int64_t)n, (uint32_t)all, nk);
             B = TB, bs = n;
         }
         if (!on_device) X = TX, xs = n;
@@ -4558,6 +4706,7 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
                 HIPC(hipMemcpyAsync(X + (int64_t)c * xs, tx, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
             }
         }
+        if (conj_pairs) hipLaunchKernelGGL(k_tr_conj_cols, gconj, b, 0, STREAM, n, X, xs, (uint32_t)all, nk);
         if (!on_device)
             for (int32_t c = 0; c < nk; c++)
                 HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ldx, TX + nz * c, nb, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);

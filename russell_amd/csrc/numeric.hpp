@@ -127,6 +127,11 @@ struct SolverTransposed {
     std::vector<TrLevel> tr_levels;
     bool tr_ready = false;
     DeviceArray<int32_t> d_tr_list, d_ttptr, d_ttrow, d_ttmap;
+    // the transposed solve_updated forms (kernels_krylov_transpose.hpp): the rows of A^T cut into blocks of at most KRYT_CAP stored
+    // entries, and the partial sums of their residual kernels (2 tt_blocks per column of a block of 16)
+    DeviceArray<int32_t> d_ttblk;
+    DeviceArray<double> d_tt_part;
+    int32_t tt_blocks = 0;
     DeviceArray<SolveTask> d_tr_tasks;
     DeviceArray<double> d_work_t, d_tvec; // d_tvec: six n-vectors (b, x, xp, r, v, z)
     DeviceArray<double> d_anl;            // error analysis: twelve n-vectors + reduction words (allocated at its first option-1/2 call)
@@ -324,7 +329,8 @@ class Solver : public SolverDevice {
     int32_t solve_transpose(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs = false);
     // The same for many columns, 16 at a time through the blocked kernels (kernels_solve_transpose_blocked.hpp): every factor entry is read
     // once per block.  One column, A^T = A or no memory for the block buffers: solve_transpose.
-    int32_t solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device);
+    // conj_pairs: as in solve_transpose, the staged columns of every block conjugated on entry and exit (k_tr_conj_cols)
+    int32_t solve_transpose_many(double *x, const double *rhs, int32_t nrhs, int64_t ldx, bool on_device, bool conj_pairs = false);
     int64_t transposed_blocks = 0;   // 16-column blocks the last solve_transpose_many ran through the blocked kernels (0: it went to solve_transpose)
     // MUMPS-style error analysis of a solution xbar of A x = b (host vectors; option 1: all eight values, 2: entries 0 - 4), see numeric.cpp
     int32_t error_analysis(const double *xbar, const double *rhs, double *out, int32_t option);
@@ -359,8 +365,11 @@ class Solver : public SolverDevice {
     // the host.  values: CSR order of the caller (mapped = false) or the inputs of the installed value map (mapped = true); on_device:
     // x, rhs and values are device pointers.  Returns SUCCESSFUL_EXIT (converged) or WARNING_NOT_CONVERGED.  d_vals, the factor and the
     // statistics of the ordinary solves are left as they were.  See numeric.cpp.
+    // transposed: A_new^T x = rhs -- the same iteration with A_new^T as operator (kernels_krylov_transpose.hpp) and the unrefined
+    // transposed pass pair of the kept factor as preconditioner; the statistics of the transposed solves stay as they were too.  A^T = A
+    // (L D L^T fronts, symmetric storage): the plain form and its bits.
     int32_t solve_updated(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
-                          bool on_device);
+                          bool on_device, bool transposed = false);
     int64_t updated_steps = 0, updated_cycles = 0; // of the last solve_updated
     int64_t updated_basis_bytes() const { return up_m > 0 ? (int64_t)(2 * (int64_t)up_m + 1) * S.n * 8 : 0; }
     double updated_ms[3] = {0.0, 0.0, 0.0}; // HIPMF_UPDATED_TIMING=1: HIP-event time of the last call's pass pairs, SpMVs, Arnoldi kernels
@@ -369,17 +378,19 @@ class Solver : public SolverDevice {
     // the host or nullptr.  SUCCESSFUL_EXIT when every column converged, else WARNING_NOT_CONVERGED.  nrhs == 1 is solve_updated.  After
     // the call updated_steps counts blocked pass pairs and updated_cycles the cycles, both summed over the blocks.
     int32_t solve_updated_many(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps,
-                               int32_t *steps, double *relres, bool on_device);
+                               int32_t *steps, double *relres, bool on_device, bool transposed = false);
     // The single form for the real-equivalent system of a COMPLEX matrix (S.n = 2 nc, vectors of interleaved (re, im) pairs; the
     // complex C-ABI): the same iteration in complex arithmetic -- <v, w> = sum conj(v_i) w_i, complex Hessenberg matrix and rotations
     // (kernels_krylov_complex.hpp) -- on the same bases and vectors.  values: always the inputs of the installed (signed) value map.
+    // transposed: the transposed real-equivalent system, A_new^H z = c; with conj_pairs A_new^T z = c -- the same iteration on conjugated
+    // data (the imaginary parts of c negated on entry, those of z on exit; steps and relres are those of the A^H iteration on conj(c)).
     int32_t solve_updated_complex(double *x, const double *rhs, const double *values, double rel_tol, int32_t max_steps, int32_t *steps, double *relres,
-                                  bool on_device);
+                                  bool on_device, bool transposed = false, bool conj_pairs = false);
     bool updated_complex = false; // the last solve_updated_complex orthogonalised in complex arithmetic (false before the first)
     // solve_updated_many for that system (the complex C-ABI): x, rhs column-major with ld DOUBLES (even, >= S.n) between columns; every
     // column its own flexible GMRES in complex arithmetic (kernels_krylov_complex_blocked.hpp).  nrhs == 1 is solve_updated_complex.
     int32_t solve_updated_many_complex(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, double rel_tol, int32_t max_steps, int32_t *steps,
-                                       double *relres, bool on_device);
+                                       double *relres, bool on_device, bool transposed = false, bool conj_pairs = false);
     int64_t updated_blocks = 0, updated_column_steps = 0; // of the last solve_updated_many: 16-column blocks (0: single form), sum of the columns' steps
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
@@ -570,13 +581,20 @@ class Solver : public SolverDevice {
     std::vector<int32_t> h_emap;
     // values (CSR order of the caller, or the inputs of the value map: mapped) -> dst, nnz doubles in the handle's CSR order
     int32_t stage_values(double *dst, const double *values, bool mapped, bool on_device);
-    // the flexible GMRES of solve_updated and solve_updated_complex; P: the arithmetic (UpdatedReal, UpdatedComplex in numeric.cpp)
-    template <class P>
-    int32_t solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, bool on_device);
-    // the block driver of solve_updated_many and solve_updated_many_complex; P as above
-    template <class P>
+    struct OpPlain;      // the operator policies of the solve_updated cores (numeric.cpp)
+    struct OpTransposed;
+    // the flexible GMRES of solve_updated and solve_updated_complex; P: the arithmetic (UpdatedReal, UpdatedComplex in numeric.cpp), O: the
+    // operator (OpPlain: A_new, OpTransposed: A_new^T -- preconditioner call, product and residual); conj_pairs: rhs and x are conjugated
+    // on the way in and out (interleaved complex pairs)
+    template <class P, class O>
+    int32_t solve_updated_core(double *x, const double *rhs, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps, double *relres, bool on_device,
+                               bool conj_pairs);
+    // the block driver of solve_updated_many and solve_updated_many_complex; P, O and conj_pairs as above
+    template <class P, class O>
     int32_t solve_updated_many_core(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps,
-                                    double *relres, bool on_device);
+                                    double *relres, bool on_device, bool conj_pairs);
+    // the blocked transposed pass pair on C <= 16 contiguous columns (stride n): Z = A^{-T} V, unrefined (buffers of tr_prepare_blocked())
+    int32_t tr_pass_blk(double *Z, const double *V, int32_t C);
     // the error analysis of both forms; P: what differs (EaReal, EaComplex in numeric.cpp)
     template <class P>
     int32_t error_analysis_core(const double *xbar, const double *rhs, double *out, int32_t option);

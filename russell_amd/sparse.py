@@ -172,6 +172,8 @@ def _L():
         "rh_linsolver_inverse_entries_by_rows": (cp, [vp, vp, i64, vp, vp, i32]),
         "rh_linsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
         "rh_linsolver_solve_updated_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
+        "rh_linsolver_solve_updated_transpose": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
+        "rh_linsolver_solve_updated_transpose_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
         "rh_linsolver_times": (None, [vp, pp(C.c_uint64)]),
         "rh_linsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(i32), pp(i32), pp(i32)]),
         "rh_linsolver_stats_json": (cp, [vp, vp, cp, vp, vp]),
@@ -190,6 +192,9 @@ def _L():
         "rh_clinsolver_solve_updated": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32]),
         "rh_clinsolver_solve_many": (cp, [vp, vp, vp, i64, i64]),
         "rh_clinsolver_solve_updated_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32]),
+        "rh_clinsolver_solve_updated_transpose": (cp, [vp, vp, i64, vp, vp, i64, f64, i32, pp(i32), pp(f64), i32, i32]),
+        "rh_clinsolver_solve_updated_transpose_many": (cp, [vp, vp, vp, vp, i64, i64, f64, i32, vp, vp, i32, i32]),
+        "rh_clinsolver_solve_transpose_many": (cp, [vp, vp, vp, i64, i64, i32]),
         "rh_clinsolver_outputs": (None, [vp, pp(f64), pp(f64), pp(f64), pp(f64), pp(i32)]),
         "rh_clinsolver_mumps_stats": (None, [vp, vp]),
         "rh_error_string": (cp, [i32]),
@@ -536,8 +541,9 @@ class _Actual:
         _check(fn(self._h, _ptr(v), r.size, _ptr(r), _ptr(c), int(verbose)))
         return v
 
-    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
-        """A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES on the device: `mat` is a CooMatrix with
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False, transpose=False):
+        """A_new x = rhs (transpose: A_new^T x = rhs) with the factor of the last factorize as preconditioner of a flexible GMRES on the
+        device: `mat` is a CooMatrix with
         the structure of the factorised matrix and new values.  Returns (x, steps, relres); raises StrError("Error(2): ...") when the
         tolerance was not reached."""
         if self._ndim is None:
@@ -545,11 +551,11 @@ class _Actual:
         b = _vec(rhs)
         x = np.zeros(self._ndim)
         steps, relres = C.c_int32(0), C.c_double(0.0)
-        _check(_L().rh_linsolver_solve_updated(self._h, _ptr(x), x.size, mat._h, _ptr(b), b.size, float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres),
-                                               int(verbose)))
+        fn = _L().rh_linsolver_solve_updated_transpose if transpose else _L().rh_linsolver_solve_updated
+        _check(fn(self._h, _ptr(x), x.size, mat._h, _ptr(b), b.size, float(rel_tol), int(max_steps), C.byref(steps), C.byref(relres), int(verbose)))
         return x, int(steps.value), float(relres.value)
 
-    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False, transpose=False):
         """solve_updated for the right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim), as solve_many takes them), 16 per blocked
         pass pair, every column its own iteration.  Returns (x, steps, relres) with x in the shape of rhs_rows and one entry of steps and
         relres per right-hand side; raises StrError("Error(2): ...") when any of them did not reach the tolerance."""
@@ -561,7 +567,8 @@ class _Actual:
         nrhs, n = b.shape
         x = np.zeros_like(b)
         steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
-        _check(_L().rh_linsolver_solve_updated_many(self._h, _ptr(x), mat._h, _ptr(b), n, nrhs, float(rel_tol), int(max_steps), _ptr(steps), _ptr(relres), int(verbose)))
+        fn = _L().rh_linsolver_solve_updated_transpose_many if transpose else _L().rh_linsolver_solve_updated_many
+        _check(fn(self._h, _ptr(x), mat._h, _ptr(b), n, nrhs, float(rel_tol), int(max_steps), _ptr(steps), _ptr(relres), int(verbose)))
         return x, steps, relres
 
     def get_ns(self):
@@ -610,13 +617,13 @@ class LinSolver:
         """extension of the HIPMF backend, see `actual.inverse_entries`"""
         return self.actual.inverse_entries(rows, cols, verbose, by_rows)
 
-    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False, transpose=False):
         """extension of the HIPMF backend, see `actual.solve_updated`"""
-        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
+        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose, transpose)
 
-    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False, transpose=False):
         """extension of the HIPMF backend, see `actual.solve_updated_many`"""
-        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose)
+        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose, transpose)
 
     @staticmethod
     def compute(genie, mat, rhs, params=None):
@@ -713,16 +720,35 @@ class _ComplexActual:
             x[:] = z
         return z
 
-    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False, transpose=False, conjugate=False):
         """A_new x = rhs with the factor of the last factorize as preconditioner of a flexible GMRES in complex arithmetic on the device:
-        `mat` is a ComplexCooMatrix with the structure of the factorised matrix and new values.  Returns (x, steps, relres); raises
+        `mat` is a ComplexCooMatrix with the structure of the factorised matrix and new values.  transpose: A_new^T x = rhs, or
+        A_new^H x = rhs with conjugate=True (the default of `conjugate` is False as in solve_transpose, so transpose=True alone is A_new^T;
+        conjugate without transpose is refused).  Returns (x, steps, relres); raises
         StrError("Error(2): ...") when the tolerance was not reached."""
+        if conjugate and not transpose:
+            raise StrError("solve_updated: conjugate=True needs transpose=True")
         r = np.ascontiguousarray(np.asarray(rhs, dtype=np.complex128)).view(np.float64)
         out = np.zeros(2 * mat.nrow)
         steps, relres = C.c_int32(0), C.c_double(0.0)
-        _check(_L().rh_clinsolver_solve_updated(self._h, _ptr(out), out.size, mat._h, _ptr(r), r.size, float(rel_tol), int(max_steps), C.byref(steps),
-                                                C.byref(relres), int(verbose)))
+        if transpose:
+            _check(_L().rh_clinsolver_solve_updated_transpose(self._h, _ptr(out), out.size, mat._h, _ptr(r), r.size, float(rel_tol), int(max_steps), C.byref(steps),
+                                                              C.byref(relres), int(bool(conjugate)), int(verbose)))
+        else:
+            _check(_L().rh_clinsolver_solve_updated(self._h, _ptr(out), out.size, mat._h, _ptr(r), r.size, float(rel_tol), int(max_steps), C.byref(steps),
+                                                    C.byref(relres), int(verbose)))
         return out.view(np.complex128), int(steps.value), float(relres.value)
+
+    def solve_transpose_many(self, rhs_rows, conjugate=False):
+        """A^T X = B, or A^H X = B with conjugate=True, for the complex right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim)), 16
+        per transposed pass pair over the factor.  Returns x in the shape of rhs_rows."""
+        b = np.ascontiguousarray(np.asarray(rhs_rows, dtype=np.complex128))
+        if b.ndim != 2:
+            raise StrError("solve_transpose_many expects an array of shape (nrhs, ndim)")
+        nrhs, n = b.shape
+        x = np.zeros_like(b)
+        _check(_L().rh_clinsolver_solve_transpose_many(self._h, _ptr(x.view(np.float64)), _ptr(b.view(np.float64)), n, nrhs, int(bool(conjugate))))
+        return x
 
     def solve_many(self, rhs_rows):
         """A X = B for the complex right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim)), 16 per pass pair over the factor.
@@ -735,19 +761,25 @@ class _ComplexActual:
         _check(_L().rh_clinsolver_solve_many(self._h, _ptr(x.view(np.float64)), _ptr(b.view(np.float64)), n, nrhs))
         return x
 
-    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False, transpose=False, conjugate=False):
         """solve_updated for the complex right-hand sides in the rows of `rhs_rows` (shape (nrhs, ndim), as solve_many takes them), 16 per
-        blocked pass pair, every column its own iteration in complex arithmetic.  Returns (x, steps, relres) with x in the shape of
+        blocked pass pair, every column its own iteration in complex arithmetic; transpose / conjugate as in solve_updated.  Returns (x, steps, relres) with x in the shape of
         rhs_rows and one entry of steps and relres per right-hand side; raises StrError("Error(2): ...") when any of them did not reach
         the tolerance."""
+        if conjugate and not transpose:
+            raise StrError("solve_updated_many: conjugate=True needs transpose=True")
         b = np.ascontiguousarray(np.asarray(rhs_rows, dtype=np.complex128))
         if b.ndim != 2:
             raise StrError("solve_updated_many expects an array of shape (nrhs, ndim)")
         nrhs, n = b.shape
         x = np.zeros_like(b)
         steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
-        _check(_L().rh_clinsolver_solve_updated_many(self._h, _ptr(x.view(np.float64)), mat._h, _ptr(b.view(np.float64)), n, nrhs, float(rel_tol), int(max_steps),
-                                                     _ptr(steps), _ptr(relres), int(verbose)))
+        if transpose:
+            _check(_L().rh_clinsolver_solve_updated_transpose_many(self._h, _ptr(x.view(np.float64)), mat._h, _ptr(b.view(np.float64)), n, nrhs, float(rel_tol),
+                                                                   int(max_steps), _ptr(steps), _ptr(relres), int(bool(conjugate)), int(verbose)))
+        else:
+            _check(_L().rh_clinsolver_solve_updated_many(self._h, _ptr(x.view(np.float64)), mat._h, _ptr(b.view(np.float64)), n, nrhs, float(rel_tol), int(max_steps),
+                                                         _ptr(steps), _ptr(relres), int(verbose)))
         return x, steps, relres
 
     def outputs(self):
@@ -776,17 +808,21 @@ class ComplexLinSolver:
         _check(err.value)
         self.actual = _ComplexActual(h)
 
-    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_updated(self, mat, rhs, rel_tol=0.0, max_steps=0, verbose=False, transpose=False, conjugate=False):
         """extension of the HIPMF backend, see `actual.solve_updated`"""
-        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose)
+        return self.actual.solve_updated(mat, rhs, rel_tol, max_steps, verbose, transpose, conjugate)
 
     def solve_many(self, rhs_rows):
         """extension of the HIPMF backend, see `actual.solve_many`"""
         return self.actual.solve_many(rhs_rows)
 
-    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False):
+    def solve_transpose_many(self, rhs_rows, conjugate=False):
+        """extension of the HIPMF backend, see `actual.solve_transpose_many`"""
+        return self.actual.solve_transpose_many(rhs_rows, conjugate)
+
+    def solve_updated_many(self, mat, rhs_rows, rel_tol=0.0, max_steps=0, verbose=False, transpose=False, conjugate=False):
         """extension of the HIPMF backend, see `actual.solve_updated_many`"""
-        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose)
+        return self.actual.solve_updated_many(mat, rhs_rows, rel_tol, max_steps, verbose, transpose, conjugate)
 
 
 def handle_hipmf_error_code(code):

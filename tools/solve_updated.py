@@ -40,7 +40,15 @@ complex columns, three median wall times from the same run:
     (b) N complex_solver_hipmf_solve_updated_device calls on the same columns (that code is not touched by the block form),
     (c) complex_solver_hipmf_factorize_mapped + complex_solver_hipmf_solve_many(nrhs = N) on a second handle (host pointers),
 with the per-column step counts, UPDATED_STEPS (blocked pass pairs), UPDATED_COLUMN_STEPS and the split of (a) into pass pair / SpMV /
-Arnoldi kernels (HIP events, calls of their own).  The figures of merit are (a)/N, (b)/N and (c)/N."""
+Arnoldi kernels (HIP events, calls of their own).  The figures of merit are (a)/N, (b)/N and (c)/N.
+
+    python tools/solve_updated.py --transpose [--complex] [--nrhs N] [--conjugate 0|1]
+
+The transposed forms (profiles/r17_solve_updated_transpose.txt, appended to when --out is not given): the same matrices, changes and
+measurements as the four modes above with A_new^T as the system -- solver_hipmf_solve_updated_transpose_device / _many_device,
+complex_solver_hipmf_solve_updated_transpose_device / _many_device (--conjugate 1: A_new^H, the default; 0: A_new^T) -- the caller's
+alternative being factorize + solve_transpose (block form: solve_transpose_many) on the new values, and, in the same run, the median
+wall time of the non-transposed call on the same inputs ("plain").  The pass pair / SpMV / Arnoldi split is that of the transposed call."""
 import argparse
 import os
 import sys
@@ -90,10 +98,11 @@ def run(name, n, rp, ci, v, args, out):
         res = {}
 
         def call():
-            res["r"] = s.solve_updated_device(d_x, d_b, d_v, rel_tol=args.tol)
+            res["r"] = s.solve_updated_device(d_x, d_b, d_v, rel_tol=args.tol, transpose=args.transpose)
         os.environ.pop("HIPMF_UPDATED_TIMING", None)
         med, lo, hi = timed(call, args.reps, args.warmup)
         steps, relres, status = res["r"]
+        plain = timed(lambda: s.solve_updated_device(d_x, d_b, d_v, rel_tol=args.tol), args.reps, args.warmup)[0] if args.transpose else None
         os.environ["HIPMF_UPDATED_TIMING"] = "1"
         parts = []
         for _ in range(3):
@@ -104,11 +113,15 @@ def run(name, n, rp, ci, v, args, out):
 
         def alternative():
             alt.factorize_device(d_v)
-            alt.solve_device(d_x, d_b)
+            if args.transpose:
+                alt.solve_transpose_device(d_x, d_b)
+            else:
+                alt.solve_device(d_x, d_b)
         amed, alo, ahi = timed(alternative, args.reps, args.warmup)
         per_step = med / max(steps, 1)
-        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %12.3f %10.1f   (status %d, relres %.1e; call %.3f-%.3f, alternative %.3f-%.3f ms)" %
-            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, lo, hi, alo, ahi))
+        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %12.3f %10.1f   (status %d, relres %.1e; call %.3f-%.3f, alternative %.3f-%.3f ms%s)" %
+            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, lo, hi, alo, ahi,
+             "; plain form %.3f ms/call" % plain if args.transpose else ""))
     for p in (d_x, d_b, d_v):
         s.dev_free(p)
     s.close()
@@ -141,10 +154,10 @@ def run_many(name, n, rp, ci, v, args, out):
         res = {}
 
         def blocked():
-            res["a"] = s.solve_updated_many_device(d_x, d_b, nrhs, d_v, rel_tol=args.tol)
+            res["a"] = s.solve_updated_many_device(d_x, d_b, nrhs, d_v, rel_tol=args.tol, transpose=args.transpose)
 
         def looped():
-            res["b"] = [s.solve_updated_device(d_x + 8 * n * c, d_b + 8 * n * c, d_v, rel_tol=args.tol) for c in range(nrhs)]
+            res["b"] = [s.solve_updated_device(d_x + 8 * n * c, d_b + 8 * n * c, d_v, rel_tol=args.tol, transpose=args.transpose) for c in range(nrhs)]
         os.environ.pop("HIPMF_UPDATED_TIMING", None)
         a_med, a_lo, a_hi = timed(blocked, args.reps, args.warmup)
         steps, relres, status = res["a"]
@@ -161,14 +174,20 @@ def run_many(name, n, rp, ci, v, args, out):
 
         def alternative():
             alt.factorize_device(d_v)
-            alt.solve_device(d_x, d_b, nrhs=nrhs)
+            if args.transpose:
+                alt.solve_transpose_many_device(d_x, d_b, nrhs)
+            else:
+                alt.solve_device(d_x, d_b, nrhs=nrhs)
         c_med, c_lo, c_hi = timed(alternative, args.reps, args.warmup)
+        plain = timed(lambda: s.solve_updated_many_device(d_x, d_b, nrhs, d_v, rel_tol=args.tol), args.reps, args.warmup)[0] if args.transpose else None
         out("  %-10s | %9.3f %9.3f | %9.3f %9.3f | %7.3f | %12.3f | %6d %8d | %8.3f %8.3f %8.3f" %
             (label, a_med, a_med / nrhs, b_med, b_med / nrhs, a_med / b_med, c_med, pairs, colsteps, parts[0], parts[1], parts[2]))
         out("      status %d / %s, max relres %.1e / %.1e; %d block(s); (a) %.3f-%.3f, (b) %.3f-%.3f, (c) %.3f-%.3f ms" %
             (status, sorted(set(r[2] for r in res["b"])), float(np.max(relres)), max(r[1] for r in res["b"]), blocks, a_lo, a_hi, b_lo, b_hi, c_lo, c_hi))
         out("      steps per column (a): %s" % " ".join(str(int(k)) for k in steps))
         out("      steps per column (b): %s" % " ".join(str(int(k)) for k in b_steps))
+        if plain is not None:
+            out("      plain form (solve_updated_many_device) on the same inputs: %.3f ms, %.3f per column" % (plain, plain / nrhs))
     for p in (d_x, d_b, d_v):
         s.dev_free(p)
     s.close()
@@ -229,11 +248,19 @@ def run_complex(args, out):
 
         def call():
             steps, relres = C.c_int32(0), C.c_double(0.0)
-            code = lib.complex_solver_hipmf_solve_updated_device(s, d_x, d_b, d_v, 0, args.tol, 0, C.byref(steps), C.byref(relres))
+            if args.transpose:
+                code = lib.complex_solver_hipmf_solve_updated_transpose_device(s, d_x, d_b, d_v, 0, args.tol, 0, C.byref(steps), C.byref(relres), args.conjugate)
+            else:
+                code = lib.complex_solver_hipmf_solve_updated_device(s, d_x, d_b, d_v, 0, args.tol, 0, C.byref(steps), C.byref(relres))
             res["r"] = (steps.value, relres.value, code)
+
+        def plain_call():
+            steps, relres = C.c_int32(0), C.c_double(0.0)
+            lib.complex_solver_hipmf_solve_updated_device(s, d_x, d_b, d_v, 0, args.tol, 0, C.byref(steps), C.byref(relres))
         os.environ.pop("HIPMF_UPDATED_TIMING", None)
         med, lo, hi = timed(call, args.reps, args.warmup)
         steps, relres, status = res["r"]
+        plain = timed(plain_call, args.reps, args.warmup)[0] if args.transpose else None
         os.environ["HIPMF_UPDATED_TIMING"] = "1"
         parts = []
         for _ in range(3):
@@ -244,11 +271,15 @@ def run_complex(args, out):
 
         def alternative():
             assert lib.complex_solver_hipmf_factorize_mapped(alt, None, None, None, None, 0, v1) == 0
-            assert lib.complex_solver_hipmf_solve(alt, xh, b, 0) == 0
+            if args.transpose:
+                assert lib.complex_solver_hipmf_solve_transpose(alt, xh, b, args.conjugate, 0) == 0
+            else:
+                assert lib.complex_solver_hipmf_solve(alt, xh, b, 0) == 0
         amed, alo, ahi = timed(alternative, args.reps, args.warmup)
         per_step = med / max(steps, 1)
-        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %14.3f %10.1f   (status %d, relres %.1e, complex arithmetic %d; call %.3f-%.3f, alternative %.3f-%.3f ms)" %
-            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, counter(37), lo, hi, alo, ahi))
+        out("  %-10s %5d %9.3f %9.3f | %8.3f %8.3f %8.3f | %14.3f %10.1f   (status %d, relres %.1e, complex arithmetic %d; call %.3f-%.3f, alternative %.3f-%.3f ms%s)" %
+            (label, steps, med, per_step, parts[0], parts[1], parts[2], amed, amed / per_step, status, relres, counter(37), lo, hi, alo, ahi,
+             "; plain form %.3f ms/call" % plain if args.transpose else ""))
     for p_ in (d_x, d_b, d_v):
         lib.hipmf_device_free(p_)
     for h in handles:
@@ -279,13 +310,21 @@ def run_complex_many(args, out):
     steps, relres = np.zeros(nrhs, np.int32), np.zeros(nrhs)
 
     def blocked():
-        res["a"] = lib.complex_solver_hipmf_solve_updated_many_device(s, d_x, d_b, nrhs, n, d_v, 0, args.tol, 0, steps.ctypes.data, relres.ctypes.data)
+        if args.transpose:
+            res["a"] = lib.complex_solver_hipmf_solve_updated_transpose_many_device(s, d_x, d_b, nrhs, n, d_v, 0, args.tol, 0, steps.ctypes.data, relres.ctypes.data,
+                                                                                    args.conjugate)
+        else:
+            res["a"] = lib.complex_solver_hipmf_solve_updated_many_device(s, d_x, d_b, nrhs, n, d_v, 0, args.tol, 0, steps.ctypes.data, relres.ctypes.data)
 
     def looped():
         r = []
         for c in range(nrhs):
             st, rel = C.c_int32(0), C.c_double(0.0)
-            code = lib.complex_solver_hipmf_solve_updated_device(s, d_x + col * c, d_b + col * c, d_v, 0, args.tol, 0, C.byref(st), C.byref(rel))
+            if args.transpose:
+                code = lib.complex_solver_hipmf_solve_updated_transpose_device(s, d_x + col * c, d_b + col * c, d_v, 0, args.tol, 0, C.byref(st), C.byref(rel),
+                                                                               args.conjugate)
+            else:
+                code = lib.complex_solver_hipmf_solve_updated_device(s, d_x + col * c, d_b + col * c, d_v, 0, args.tol, 0, C.byref(st), C.byref(rel))
             r.append((st.value, rel.value, code))
         res["b"] = r
     os.environ.pop("HIPMF_UPDATED_TIMING", None)
@@ -304,8 +343,14 @@ def run_complex_many(args, out):
 
     def alternative():
         assert lib.complex_solver_hipmf_factorize_mapped(alt, None, None, None, None, 0, v1) == 0
-        assert lib.complex_solver_hipmf_solve_many(alt, X.reshape(-1), B.reshape(-1), nrhs, n, 0) == 0
+        if args.transpose:
+            assert lib.complex_solver_hipmf_solve_transpose_many(alt, X.reshape(-1), B.reshape(-1), nrhs, n, args.conjugate, 0) == 0
+        else:
+            assert lib.complex_solver_hipmf_solve_many(alt, X.reshape(-1), B.reshape(-1), nrhs, n, 0) == 0
     c_med, c_lo, c_hi = timed(alternative, args.reps, args.warmup)
+    plain = None
+    if args.transpose:
+        plain = timed(lambda: lib.complex_solver_hipmf_solve_updated_many_device(s, d_x, d_b, nrhs, n, d_v, 0, args.tol, 0, None, None), args.reps, args.warmup)[0]
     out("  %9s %9s | %9s %9s | %9s %9s | %7s | %6s %8s | %8s %8s %8s" % ("(a) ms", "(a)/N", "(b) ms", "(b)/N", "(c) ms", "(c)/N", "(a)/(b)", "pairs", "colsteps", "passpair",
                                                                         "spmv", "arnoldi"))
     out("  %9.3f %9.3f | %9.3f %9.3f | %9.3f %9.3f | %7.3f | %6d %8d | %8.3f %8.3f %8.3f" %
@@ -315,6 +360,8 @@ def run_complex_many(args, out):
          c_lo, c_hi))
     out("      steps per column (a): %s" % " ".join(str(int(k)) for k in a_steps))
     out("      steps per column (b): %s" % " ".join(str(r[0]) for r in res["b"]))
+    if plain is not None:
+        out("      plain form (complex_solver_hipmf_solve_updated_many_device) on the same inputs: %.3f ms, %.3f per column" % (plain, plain / nrhs))
     for p_ in (d_x, d_b, d_v):
         lib.hipmf_device_free(p_)
     for h in handles:
@@ -325,6 +372,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--complex", action="store_true", help="the complex form on the 500 x 500 complex shifted grid (see the module docstring)")
     ap.add_argument("--nrhs", type=int, default=0, help="N > 0: the block form on N columns against N single calls (see the module docstring)")
+    ap.add_argument("--transpose", action="store_true", help="the transposed forms (A_new^T; complex: see --conjugate) against factorize + solve_transpose(_many)")
+    ap.add_argument("--conjugate", type=int, default=1, choices=[0, 1], help="with --complex --transpose: 1 = A_new^H (default), 0 = A_new^T")
     ap.add_argument("--matrix", default="both", choices=["2d", "3d", "both"])
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
@@ -332,11 +381,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     args = ap.parse_args()
+    if args.transpose and args.out is None:
+        args.out, args.append = os.path.join(ROOT, "profiles", "r17_solve_updated_transpose.txt"), True
     lines = []
 
     def out(line):
         print(line, flush=True)
         lines.append(line)
+    if args.transpose:
+        out("TRANSPOSED forms%s: the calls named below are their _transpose twins, the alternative ends in solve_transpose%s" %
+            ((" (conjugate = %d)" % args.conjugate) if args.complex else "", "_many" if args.nrhs > 0 else ""))
     if args.complex and args.nrhs > 0:
         out("(a) one complex_solver_hipmf_solve_updated_many_device call, (b) %d complex_solver_hipmf_solve_updated_device calls, (c) complex_solver_hipmf_factorize_mapped + "
             "complex_solver_hipmf_solve_many(nrhs = %d), one MI355X; median of %d after %d warm-up" % (args.nrhs, args.nrhs, args.reps, args.warmup))
