@@ -46,7 +46,7 @@ extern "C" {
 #define ERROR_ALREADY_INITIALIZED 700000
 
 #define HIPMF_WARNING_SINGULAR_MATRIX 1
-#define HIPMF_WARNING_NOT_CONVERGED 2 /* solver_hipmf_solve_updated / _device only: the tolerance was not reached; x holds the best iterate */
+#define HIPMF_WARNING_NOT_CONVERGED 2 /* the solve_updated and solve_extra_precise forms only: the tolerance was not reached; x holds the best iterate */
 #define ERROR_HIP_MALLOC 100
 #define ERROR_HIP_MEMCPY 200
 #define ERROR_HIP_SYNCHRONIZE 300
@@ -296,6 +296,45 @@ int32_t solver_hipmf_solve_updated_transpose_many_device(struct InterfaceHIPMF *
                                                          const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
                                                          double *relres);
 
+/* EXTRA-PRECISE iterative refinement with forward error bounds (Demmel, Hida, Kahan, Li, Mukherjee & Riedy 2006; the scheme of LAPACK's
+ * xGERFSX).  solver_hipmf_solve refines on a residual in working precision and stops on the backward error: its x is backward stable, its
+ * forward error about cond(A) eps.  Here r = b - A (x + tail) is accumulated in twice the working precision (every product by an FMA,
+ * every sum by TwoSum, rounded once) and the iteration watches the corrections: while cond(A) eps < 1 the forward error reaches the order of
+ * eps, normwise and componentwise.  A: the values of the last factorize.  Per column, in the user's space:
+ *   x <- one unrefined pass pair of b, tail <- 0; per step r as above, dx <- one unrefined pass pair of r,
+ *   dn = |dx|_inf / |x|_inf, dc = max_i |dx_i| / |x_i| (0 / 0 counts 0, nonzero / 0 +infinity), rho = dn / dn of the step before;
+ *   dn > dn of the step before (or a dx that is not finite): the step is NOT applied, state "no progress".  Else x <- x + dx -- with a
+ *   tail (x, tail) <- the renormalised TwoSum of x + dx + tail -- and: dn <= dx_tol converged; not the first step and dn > dn_prev / 2
+ *   "no progress"; max_steps steps "step limit".
+ * dx_tol <= 0 selects eps, max_steps <= 0 selects 10.  x_tail (NULL allowed): the solution is kept as the unevaluated sum x + x_tail,
+ * x the nearest double, and the residual includes the tail -- the error of x + x_tail goes below eps (order cond eps^2); its columns are laid
+ * out as those of x.  rhs = 0 gives x = 0 (and tail = 0) in zero steps with every info entry 0.
+ * info, 8 doubles per column on the host (info_len_8 of the single forms; NULL allowed):
+ *   [0] steps taken (pass pairs after the first)  [1] dn of the last applied step  [2] normwise forward error bound dn / (1 - rho_max)
+ *   [3] dc of the last applied step  [4] componentwise bound dc / (1 - rho_max)  [5] rho_max, the largest rho over the applied steps (0 when
+ *   there was one)  [6] state: 0 converged, 1 no progress, 2 step limit  [7] 1 when a tail was carried.
+ *   Without a tail both bounds are floored by max(10, sqrt(n)) eps; with no applied step or rho_max >= 1 they are +infinity.
+ * Returns 0 when every column converged, HIPMF_WARNING_NOT_CONVERGED otherwise (x: the best iterate).
+ * _many / _device: column-major ld x nrhs, ld >= ndim (entries ndim .. ld - 1 of a column are not touched), blocks of 16 columns: ONE
+ * blocked pass pair, ONE pass over the matrix and ONE update launch per block step, ONE host read of the measures; a finished column is
+ * masked out and rides through the pass pairs as zeros.  _device: x, x_tail and rhs are device pointers, info stays on the host.
+ * HIPMF_COUNTER_EXTRA_PRECISE_STEPS / _BLOCKS report the last call.  Bit-reproducible from call to call (no floating-point atomics).
+ * NO SIDE EFFECTS on the factor, the values, the refinement statistics, any counter, statistic or timer of the ordinary solves, or the
+ * bits of a later solve.  After a factorisation that replaced pivots the pass pair is a weaker approximate inverse: the iteration then
+ * needs more steps or ends as "no progress"; there is no Krylov rescue inside.
+ * WHAT IT COSTS (tools/extra_precise.py, one MI355X, profiles/r18_extra_precise.txt): the start pass pair plus per
+ * step one pass pair, one pass over the matrix and one update launch -- at 1M unknowns 0.459 + 0.035 + 0.018 ms -- and a host round
+ * trip: 1.51 ms against 0.93 ms for solver_hipmf_solve_device at default refinement (two steps), 7.06 against 4.60 ms for 16 columns; on a
+ * shifted Laplacian of 90 000 unknowns with cond 4e10 1.26 against 0.66 ms (four steps).  Host-pointer calls are not yet timed.
+ * ERROR_NULL_POINTER (solver, x, rhs), ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order; ERROR_HIPMF_INVALID_VALUE for
+ * nrhs < 1 or ld < ndim. */
+int32_t solver_hipmf_solve_extra_precise(struct InterfaceHIPMF *solver, double *x, double *x_tail, const double *rhs, double dx_tol, int32_t max_steps,
+                                         double *info_len_8, C_BOOL verbose);
+int32_t solver_hipmf_solve_extra_precise_many(struct InterfaceHIPMF *solver, double *x, double *x_tail, const double *rhs, int32_t nrhs, int32_t ld,
+                                              double dx_tol, int32_t max_steps, double *info, C_BOOL verbose);
+int32_t solver_hipmf_solve_extra_precise_device(struct InterfaceHIPMF *solver, double *d_x, double *d_x_tail, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                double dx_tol, int32_t max_steps, double *info);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -407,6 +446,11 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES 36  /* device bytes held for the block bases of those calls (UPDATED_BASIS_BYTES stays the single form's) */
 #define HIPMF_COUNTER_UPDATED_COMPLEX_ARITHMETIC 37 /* complex handle: 1 when its last solve_updated / _device orthogonalised in complex arithmetic (0 before the first) */
 #define HIPMF_COUNTER_PRUNED_TRANSPOSED_BLOCKS 38   /* blocks of the last solver_hipmf_solve_sparse_transpose / _device / solver_hipmf_inverse_entries_by_rows (complex: trans = 1, 2) that ran the transposed pruned launches (0: A^T = A or everything fell back) */
+#define HIPMF_COUNTER_EXTRA_PRECISE_STEPS 39        /* pass pairs after the first of the last solver_hipmf_solve_extra_precise / _many / _device (complex: _solve_extra_precise), summed over its block steps */
+#define HIPMF_COUNTER_EXTRA_PRECISE_BLOCKS 40       /* 16-column blocks of that call */
+#define HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US 41  /* HIPMF_EXTRA_TIMING=1 (environment, read per call; else 0): microseconds between HIP events around the doubled residuals of that call ... */
+#define HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US 42   /* ... its correction pass pairs ... */
+#define HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US 43    /* ... and its update launches (tools/extra_precise.py) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -621,6 +665,12 @@ int32_t complex_solver_hipmf_solve_updated_many(struct InterfaceComplexHIPMF *so
 int32_t complex_solver_hipmf_solve_updated_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs, int32_t ld,
                                                        const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps, int32_t *steps,
                                                        double *relres);
+/* solver_hipmf_solve_extra_precise for the complex handle: the same iteration on the real-equivalent system, the residual in twice the
+ * working precision per real component; x, x_tail (NULL allowed), rhs: interleaved complex vectors (2 n doubles).  The measures dn and dc
+ * take the MODULI of the complex components, not their real and imaginary parts; the floor of the bounds is max(10, sqrt(n)) eps with
+ * the complex order n.  info, the return codes and the argument checks as for the real handle. */
+int32_t complex_solver_hipmf_solve_extra_precise(struct InterfaceComplexHIPMF *solver, double *x, double *x_tail, const double *rhs, double dx_tol,
+                                                 int32_t max_steps, double *info_len_8, C_BOOL verbose);
 /* The TRANSPOSED forms for the complex handle: A_new^H z = c (conjugate = 1) or A_new^T z = c (conjugate = 0) on the kept factor, as
  * solver_hipmf_solve_updated_transpose and its three siblings for the real handle, in the complex arithmetic of the forms above.
  * conjugate = 1 is the transposed real-equivalent system: operator A_new^H, preconditioner the unrefined transposed pass pair.

@@ -209,6 +209,37 @@ class Hipmf:
             raise self._err(code, name)
         return x, steps, relres, code
 
+    def solve_extra_precise(self, rhs, tail=False, dx_tol=0.0, max_steps=0, verbose=False):
+        """Extra-precise iterative refinement of A x = rhs (the residual in twice the working precision, solver_hipmf_solve_extra_precise).
+        Returns (x, x_tail or None, info, status): info the eight values of include/russell_hipmf.h (steps, dn, normwise bound, dc,
+        componentwise bound, rho_max, state, tail carried); tail=True keeps the solution as x + x_tail; status 0 = converged,
+        2 = HIPMF_WARNING_NOT_CONVERGED (x is the best iterate); any other status raises."""
+        x, info = np.zeros(self.n), np.zeros(8)
+        t = np.zeros(self.n) if tail else None
+        code = self.lib.solver_hipmf_solve_extra_precise(self.h, x, None if t is None else t.ctypes.data, np.ascontiguousarray(rhs, dtype=np.float64),
+                                                         float(dx_tol), int(max_steps), info.ctypes.data, int(verbose))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_extra_precise")
+        return x, t, info, code
+
+    def solve_extra_precise_many(self, rhs_colmajor, tail=False, dx_tol=0.0, max_steps=0, ld=None, verbose=False, x=None, x_tail=None):
+        """solve_extra_precise for the right-hand sides of an array of shape (nrhs, ld) as solve_many takes it, 16 columns per pass pair.
+        Returns (x, x_tail or None, info, status) with x and x_tail in that layout and info of shape (nrhs, 8); x / x_tail: arrays of
+        that shape to write into (their entries n .. ld - 1 of every row are left alone)."""
+        b = np.ascontiguousarray(rhs_colmajor, dtype=np.float64)
+        ld = self.n if ld is None else int(ld)
+        if b.ndim != 2 or b.shape[1] != ld:
+            raise ValueError("solve_extra_precise_many expects an array of shape (nrhs, ld) with ld = %d, got %r" % (ld, b.shape))
+        nrhs = b.shape[0]
+        x = np.zeros_like(b) if x is None else x
+        t = (np.zeros_like(b) if x_tail is None else x_tail) if (tail or x_tail is not None) else None
+        info = np.zeros((nrhs, 8))
+        code = self.lib.solver_hipmf_solve_extra_precise_many(self.h, x, None if t is None else t.ctypes.data, b, nrhs, ld, float(dx_tol), int(max_steps),
+                                                              info.ctypes.data, int(verbose))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_extra_precise_many")
+        return x, t, info, code
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -232,7 +263,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -344,6 +375,16 @@ class Hipmf:
         if code not in (0, self.WARNING_NOT_CONVERGED):
             raise self._err(code, name)
         return int(steps.value), float(relres.value), code
+
+    def solve_extra_precise_device(self, d_x, d_x_tail, d_rhs, nrhs=1, dx_tol=0.0, max_steps=0, ld=None):
+        """solve_extra_precise_many with x, x_tail (None: no tail) and rhs (column-major ld x nrhs) resident on the device; returns (info, status)"""
+        nrhs = int(nrhs)
+        info = np.zeros((max(nrhs, 1), 8))
+        code = self.lib.solver_hipmf_solve_extra_precise_device(self.h, d_x, d_x_tail, d_rhs, nrhs, int(ld or self.n), float(dx_tol), int(max_steps),
+                                                                info.ctypes.data)
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_solve_extra_precise_device")
+        return info[:nrhs], code
 
     def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, transpose=False):
         """solve_updated_many with x, rhs (column-major ld x nrhs) and values resident on the device; returns (steps, relres, status)"""

@@ -392,6 +392,25 @@ int32_t complex_solver_hipmf_solve_updated_many_device(struct InterfaceComplexHI
     });
 }
 
+// Extra-precise iterative refinement for the complex handle (Solver::solve_extra_precise in pairs mode: the loop of the real handle on the
+// real-equivalent system, the measures on the moduli of the complex components).  Status codes in the order of the real entry point.
+static int32_t c_solve_extra_precise_body(struct InterfaceComplexHIPMF *h, double *x, double *x_tail, const double *rhs, double dx_tol, int32_t max_steps,
+                                          double *info, C_BOOL verbose) {
+    if (!h || !x || !rhs) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_extra_precise(x, x_tail, rhs, 1, 2 * (int64_t)h->n, dx_tol, max_steps, info, false, true);
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("complex_solver_hipmf_solve_extra_precise: %s after %lld step(s)\n", code == SUCCESSFUL_EXIT ? "converged" : "NOT converged", (long long)h->solver.extra_steps);
+    return code;
+}
+
+int32_t complex_solver_hipmf_solve_extra_precise(struct InterfaceComplexHIPMF *h, double *x, double *x_tail, const double *rhs, double dx_tol, int32_t max_steps,
+                                                 double *info_len_8, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_extra_precise_body(h, x, x_tail, rhs, dx_tol, max_steps, info_len_8, verbose); });
+}
+
 // A^T z = c (conjugate = 0) or A^H z = c (conjugate = 1): the transpose of the real-equivalent form [a -b; b a] is the real-equivalent form
 // of A^H, so the real transposed solve of the 2n system IS the A^H solve; A^T is the same solve with the imaginary parts of c and z negated
 // on the way in and out (a device kernel).  Reference: umfpack_zi_solve's UMFPACK_At / UMFPACK_Aat systems (the complex shim calls it with
@@ -617,6 +636,11 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_UPDATED_BLOCKS: return s.updated_blocks;
     case HIPMF_COUNTER_UPDATED_COLUMN_STEPS: return s.updated_column_steps;
     case HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES: return s.updated_block_basis_bytes();
+    case HIPMF_COUNTER_EXTRA_PRECISE_STEPS: return s.extra_steps;
+    case HIPMF_COUNTER_EXTRA_PRECISE_BLOCKS: return s.extra_blocks;
+    case HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US: return (int64_t)(1e3 * s.extra_ms[0]);
+    case HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US: return (int64_t)(1e3 * s.extra_ms[1]);
+    case HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US: return (int64_t)(1e3 * s.extra_ms[2]);
     default: return -1;
     }
 }

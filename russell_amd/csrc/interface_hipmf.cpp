@@ -663,6 +663,42 @@ int32_t solver_hipmf_solve_updated_transpose_many_device(struct InterfaceHIPMF *
     });
 }
 
+// Extra-precise iterative refinement (Solver::solve_extra_precise): the residual in twice the working precision, forward error bounds
+// in info (8 doubles per column, host).  Status codes in the order of solver_hipmf_solve_updated_many.
+static int32_t solve_extra_precise_body(struct InterfaceHIPMF *h, double *x, double *x_tail, const double *rhs, int32_t nrhs, int32_t ld, double dx_tol,
+                                        int32_t max_steps, double *info, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h || !x || !rhs) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_extra_precise(x, x_tail, rhs, nrhs, ld, dx_tol, max_steps, info, on_device);
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %d column(s) %s: %lld block step(s) in %lld block(s)\n", who, nrhs, code == SUCCESSFUL_EXIT ? "converged" : "NOT all converged",
+               (long long)h->solver.extra_steps, (long long)h->solver.extra_blocks);
+    return code;
+}
+
+int32_t solver_hipmf_solve_extra_precise(struct InterfaceHIPMF *h, double *x, double *x_tail, const double *rhs, double dx_tol, int32_t max_steps,
+                                         double *info_len_8, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_extra_precise_body(h, x, x_tail, rhs, 1, h ? h->solver.S.n : 0, dx_tol, max_steps, info_len_8, verbose, false, "solver_hipmf_solve_extra_precise");
+    });
+}
+
+int32_t solver_hipmf_solve_extra_precise_many(struct InterfaceHIPMF *h, double *x, double *x_tail, const double *rhs, int32_t nrhs, int32_t ld, double dx_tol,
+                                              int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_extra_precise_body(h, x, x_tail, rhs, nrhs, ld, dx_tol, max_steps, info, verbose, false, "solver_hipmf_solve_extra_precise_many");
+    });
+}
+
+int32_t solver_hipmf_solve_extra_precise_device(struct InterfaceHIPMF *h, double *d_x, double *d_x_tail, const double *d_rhs, int32_t nrhs, int32_t ld,
+                                                double dx_tol, int32_t max_steps, double *info) {
+    return guarded(h, [&]() {
+        return solve_extra_precise_body(h, d_x, d_x_tail, d_rhs, nrhs, ld, dx_tol, max_steps, info, 0, true, "solver_hipmf_solve_extra_precise_device");
+    });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -774,6 +810,11 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_UPDATED_BLOCKS: return s.updated_blocks;
     case HIPMF_COUNTER_UPDATED_COLUMN_STEPS: return s.updated_column_steps;
     case HIPMF_COUNTER_UPDATED_BLOCK_BASIS_BYTES: return s.updated_block_basis_bytes();
+    case HIPMF_COUNTER_EXTRA_PRECISE_STEPS: return s.extra_steps;
+    case HIPMF_COUNTER_EXTRA_PRECISE_BLOCKS: return s.extra_blocks;
+    case HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US: return (int64_t)(1e3 * s.extra_ms[0]);
+    case HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US: return (int64_t)(1e3 * s.extra_ms[1]);
+    case HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US: return (int64_t)(1e3 * s.extra_ms[2]);
     default: return -1;
     }
 }

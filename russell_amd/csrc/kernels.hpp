@@ -13,3 +13,4 @@
 #include "kernels_solve_tree.hpp"
 #include "kernels_solve_leaf.hpp"
 #include "kernels_vector.hpp"
+#include "kernels_refine_extra.hpp"

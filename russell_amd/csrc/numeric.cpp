@@ -4203,6 +4203,183 @@ int32_t Solver::solve_updated_many_core(double *x, const double *rhs, int32_t nr
     return all_converged ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
 }
 
+// ---- extra-precise iterative refinement (solver_hipmf_solve_extra_precise; kernels_refine_extra.hpp) ----
+// solve() refines on a residual computed in working precision and stops on the backward error: its x is backward stable, its forward
+// error about cond(A) eps.  Here the residual is accumulated in twice the working precision and rounded once, and the iteration watches
+// the corrections themselves (Demmel, Hida, Kahan, Li, Mukherjee & Riedy 2006; LAPACK's xGERFSX): while cond(A) eps < 1 the forward
+// error goes to the order of eps, normwise and componentwise, and dn / (1 - rho_max) bounds it.  Per column, in the user's space:
+//   x <- one unrefined pass pair of b (solve_core with no refinement: k_perm_in, run_triangular under the device gate, k_perm_out), tail <- 0
+//   step: r <- b - A (x + tail) (k_xr_residual_cols), dx <- one unrefined pass pair of r, then ONE launch (k_xr_update_cols) that leaves
+//         max |dx|, max |x|, max |dx_i / x_i| of the x BEFORE the update, keeps that x (and tail) and applies x <- x + dx, with a tail
+//         (x, tail) <- the renormalised TwoSum of x + dx + tail; the host reads the measures once per block step:
+//         dn = |dx|_inf / |x|_inf, dc = max_i |dx_i| / |x_i|, rho = dn / dn of the step before
+//   dn > dn of the step before, or a component that is not finite: the step is taken back, "no progress"; else, with the step applied:
+//   dn <= dx_tol converged; not the first step and dn > dn_prev / 2 "no progress"; max_steps steps "step limit".
+// The columns of a block of XR_COLS share the pass pairs, the pass over the matrix and the update launch; a finished column leaves the
+// mask: its residual column is zeros and it rides along through the pass pairs.  A column with b = 0 is x = 0 in no step.
+// One core serves the real and the complex handle; P gives the update launch (the complex handle's measures take moduli of pairs).
+namespace {
+constexpr int32_t XR_COLS = 16;
+struct ExtraReal {
+    static constexpr auto update = k_xr_update_cols<false>;
+    static constexpr int32_t W = 1; // doubles per component
+    static constexpr const char *label = "solve_extra_precise";
+};
+struct ExtraPairs {
+    static constexpr auto update = k_xr_update_cols<true>;
+    static constexpr int32_t W = 2;
+    static constexpr const char *label = "solve_extra_precise (complex)";
+};
+} // namespace
+
+template <class P>
+int32_t Solver::solve_extra_precise_core(double *x, double *tail, const double *rhs, int32_t nrhs, int64_t ld, double dx_tol, int32_t max_steps, double *info,
+                                         bool on_device) {
+    DeviceScope dev_scope(device);
+    const int32_t n = S.n, items = n / P::W;
+    const double EPS = 2.220446049250313e-16;
+    const double tol = dx_tol > 0.0 ? dx_tol : EPS;
+    const int32_t limit = max_steps > 0 ? max_steps : 10;
+    const double bound_floor = tail ? 0.0 : std::max(10.0, sqrt((double)items)) * EPS; // (x alone cannot be nearer than its own rounding)
+    const char *const te = getenv("HIPMF_EXTRA_TIMING");
+    const StepTimer timer{xr_ev, STREAM, te && atoi(te) != 0};
+    extra_steps = extra_blocks = 0;
+    extra_ms[0] = extra_ms[1] = extra_ms[2] = 0.0;
+    if (info)
+        for (int64_t k = 0; k < 8 * (int64_t)nrhs; k++) info[k] = 0.0;
+
+    const int32_t C = std::min(nrhs, XR_COLS);
+    if (xr_cols < C) {
+        xr_cols = 0;
+        HIPC(d_xr_vec.alloc(7 * (size_t)n * C), ERROR_HIP_MALLOC);
+        HIPC(d_xr_nrm.alloc((size_t)XR_NORM_WORDS * C), ERROR_HIP_MALLOC);
+        HIPC(h_xr_nrm.alloc((size_t)XR_NORM_WORDS * C), ERROR_HIP_MALLOC);
+        xr_cols = C;
+    }
+    HIPC(timer.create(), ERROR_HIP_SYNCHRONIZE);
+    const size_t blk = (size_t)n * xr_cols, nb = sizeof(double) * (size_t)n;
+    double *const d_R = d_xr_vec, *const d_DX = d_xr_vec + blk, *const d_XS = d_xr_vec + 2 * blk, *const d_TS = d_xr_vec + 3 * blk;
+    const dim3 b256(256), gu((unsigned)std::max(1, std::min((items + 255) / 256, 1024)));
+    const int64_t stride = on_device ? ld : (int64_t)n;
+
+    // the maxima over the slots of column c: word w of k_xr_update_cols
+    auto slot_max = [&](int32_t c, int32_t w) {
+        double m = 0.0;
+        for (int32_t sl = 0; sl < RES_SLOTS; sl++) m = std::max(m, h_xr_nrm[(size_t)XR_NORM_WORDS * c + (size_t)sl * RES_SLOT_WORDS + w]);
+        return m;
+    };
+    const NestedSolveGuard guard(*this);
+    guard.unrefined_quiet();
+    bool all_converged = true;
+    for (int32_t j0 = 0; j0 < nrhs; j0 += XR_COLS) {
+        const int32_t nk = std::min(XR_COLS, nrhs - j0);
+        extra_blocks++;
+        double *const xb = on_device ? x + (int64_t)j0 * ld : d_xr_vec + 4 * blk;
+        double *const tb = !tail ? nullptr : (on_device ? tail + (int64_t)j0 * ld : d_xr_vec + 5 * blk);
+        const double *bb = on_device ? rhs + (int64_t)j0 * ld : d_xr_vec + 6 * blk;
+        if (!on_device)
+            for (int32_t c = 0; c < nk; c++)
+                HIPC(hipMemcpyAsync(d_xr_vec + 6 * blk + (size_t)c * n, rhs + (int64_t)(j0 + c) * ld, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        const uint32_t all = nk >= 32 ? ~0u : ((1u << nk) - 1u);
+        const size_t nrm_bytes = (size_t)XR_NORM_WORDS * nk * sizeof(unsigned long long);
+        // max |b_i| per column (measures only: nothing is written through the pointer)
+        HIPC(hipMemsetAsync(d_xr_nrm, 0, nrm_bytes, STREAM), ERROR_HIP_MEMCPY);
+        hipLaunchKernelGGL(P::update, dim3(gu.x, nk), b256, 0, STREAM, n, const_cast<double *>(bb), (double *)nullptr, stride, (const double *)nullptr, (int64_t)0,
+                           (double *)nullptr, (double *)nullptr, (int64_t)0, (unsigned long long *)d_xr_nrm, all);
+        HIPC(hipMemcpyAsync(h_xr_nrm, d_xr_nrm, nrm_bytes, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        int32_t code = solve_core(xb, bb, nk, stride, true); // the start (ends with the stream drained: the norms of b are here)
+        if (code != SUCCESSFUL_EXIT) return code;
+        struct Column {
+            bool active = false;
+            int32_t steps = 0, state = 0;
+            double dn_prev = INFINITY, dn = 0.0, dc = 0.0, rho_max = 0.0;
+            bool applied = false, zero = false;
+        } col[XR_COLS];
+        uint32_t mask = 0;
+        for (int32_t c = 0; c < nk; c++) {
+            if (tb) HIPC(hipMemsetAsync(tb + (int64_t)c * stride, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+            if (slot_max(c, 1) == 0.0 && slot_max(c, 3) == 0.0) { // b = 0: x = 0, no step
+                col[c].zero = true;
+                HIPC(hipMemsetAsync(xb + (int64_t)c * stride, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+            } else {
+                col[c].active = true, mask |= 1u << c;
+            }
+        }
+        for (int32_t it = 1; mask != 0; it++) {
+            timer.mark(0);
+            if (tb)
+                hipLaunchKernelGGL(k_xr_residual_cols<true>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, (const double *)xb,
+                                   (const double *)tb, stride, bb, stride, d_R, (int64_t)n, nk, mask);
+            else
+                hipLaunchKernelGGL(k_xr_residual_cols<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, (const double *)xb,
+                                   (const double *)nullptr, stride, bb, stride, d_R, (int64_t)n, nk, mask);
+            timer.mark(1);
+            code = solve_core(d_DX, d_R, nk, n, true);
+            if (code != SUCCESSFUL_EXIT) return code;
+            timer.mark(2);
+            HIPC(hipMemsetAsync(d_xr_nrm, 0, nrm_bytes, STREAM), ERROR_HIP_MEMCPY);
+            hipLaunchKernelGGL(P::update, dim3(gu.x, nk), b256, 0, STREAM, n, xb, tb, stride, (const double *)d_DX, (int64_t)n, d_XS, tb ? d_TS : (double *)nullptr, (int64_t)n,
+                               (unsigned long long *)d_xr_nrm, mask);
+            timer.mark(3);
+            HIPC(hipMemcpyAsync(h_xr_nrm, d_xr_nrm, nrm_bytes, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            timer.add(extra_ms);
+            extra_steps++;
+            for (int32_t c = 0; c < nk; c++) {
+                Column &k = col[c];
+                if (!k.active) continue;
+                k.steps = it;
+                const double mdx = slot_max(c, 0), mx = slot_max(c, 1);
+                const double dn = mdx == 0.0 ? 0.0 : (mx > 0.0 ? mdx / mx : INFINITY), dc = slot_max(c, 2);
+                if (guard.verbose && j0 + c == 0) fprintf(stderr, "hipmf: %s: step %d: dn = %.3e, dc = %.3e\n", P::label, it, dn, dc);
+                if (slot_max(c, 3) != 0.0 || dn > k.dn_prev) { // not a number somewhere, or a larger correction than the last: taken back
+                    HIPC(hipMemcpyAsync(xb + (int64_t)c * stride, d_XS + (size_t)c * n, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                    if (tb) HIPC(hipMemcpyAsync(tb + (int64_t)c * stride, d_TS + (size_t)c * n, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                    k.state = 1, k.active = false;
+                    continue;
+                }
+                if (k.applied) k.rho_max = std::max(k.rho_max, k.dn_prev > 0.0 ? dn / k.dn_prev : 0.0);
+                k.dn = dn, k.dc = dc;
+                if (dn <= tol) k.state = 0, k.active = false;
+                else if (k.applied && dn > 0.5 * k.dn_prev) k.state = 1, k.active = false;
+                else if (it >= limit) k.state = 2, k.active = false;
+                k.applied = true, k.dn_prev = dn;
+            }
+            mask = 0;
+            for (int32_t c = 0; c < nk; c++)
+                if (col[c].active) mask |= 1u << c;
+        }
+        for (int32_t c = 0; c < nk; c++) {
+            const Column &k = col[c];
+            all_converged = all_converged && k.state == 0;
+            if (info && !k.zero) {
+                double *const o = info + 8 * (size_t)(j0 + c);
+                // (no applied step, or corrections that do not contract: nothing bounds the error)
+                const double scale = (k.applied && k.rho_max < 1.0) ? 1.0 / (1.0 - k.rho_max) : INFINITY;
+                o[0] = k.steps, o[1] = k.dn, o[2] = std::max(k.dn * scale, bound_floor), o[3] = k.dc, o[4] = std::max(k.dc * scale, bound_floor);
+                o[5] = k.rho_max, o[6] = k.state, o[7] = tail ? 1.0 : 0.0;
+            }
+            if (!on_device) {
+                HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ld, xb + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+                if (tb) HIPC(hipMemcpyAsync(tail + (int64_t)(j0 + c) * ld, tb + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            }
+        }
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the staging blocks are the next block's)
+    }
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    return all_converged ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
+}
+
+int32_t Solver::solve_extra_precise(double *x, double *tail, const double *rhs, int32_t nrhs, int64_t ld, double dx_tol, int32_t max_steps, double *info, bool on_device,
+                                    bool pairs) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !rhs) return ERROR_NULL_POINTER;
+    if (nrhs < 1 || ld < S.n || (pairs && (S.n & 1))) return ERROR_HIPMF_INVALID_VALUE;
+    return pairs ? solve_extra_precise_core<ExtraPairs>(x, tail, rhs, nrhs, ld, dx_tol, max_steps, info, on_device)
+                 : solve_extra_precise_core<ExtraReal>(x, tail, rhs, nrhs, ld, dx_tol, max_steps, info, on_device);
+}
+
 int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (nnz_lower < 1 || (int64_t)emap.size() != S.nnz_a) return ERROR_HIPMF_INVALID_VALUE;

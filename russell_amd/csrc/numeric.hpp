@@ -203,10 +203,21 @@ struct SolverUpdated {
     int32_t ub_d = 0;              // ... and the doubles per coefficient (1 real, 2 complex) the partial sums and the record are sized for
 };
 
+// solver_hipmf_solve_extra_precise (allocated at its first call, regrown for a wider block; kernels_refine_extra.hpp): seven n x C blocks
+// -- the residual, the correction, the x and tail a step can be taken back from, and the staging of x, tail and b of a host-pointer
+// call (the device form works on the caller's) --, the measure slots of a block step and their pinned mirror
+struct SolverExtraPrecise {
+    DeviceArray<double> d_xr_vec;
+    DeviceArray<unsigned long long> d_xr_nrm;
+    PinnedArray<double> h_xr_nrm;
+    int32_t xr_cols = 0;  // columns the blocks are allocated for (0: not allocated)
+    EventOwner xr_ev[4];  // HIPMF_EXTRA_TIMING=1: around the residual, the pass pair and the update of a step
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated {
+struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -392,6 +403,17 @@ class Solver : public SolverDevice {
     int32_t solve_updated_many_complex(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, double rel_tol, int32_t max_steps, int32_t *steps,
                                        double *relres, bool on_device, bool transposed = false, bool conj_pairs = false);
     int64_t updated_blocks = 0, updated_column_steps = 0; // of the last solve_updated_many: 16-column blocks (0: single form), sum of the columns' steps
+    // Extra-precise iterative refinement of A x = rhs on the kept factor (A: the values of the last factorize): per column x <- one
+    // unrefined pass pair, then steps r = b - A (x + tail) in twice the working precision (kernels_refine_extra.hpp), dx = one unrefined
+    // pass pair of r, x (and tail) updated, until dn = |dx|_inf / |x|_inf <= dx_tol (<= 0: eps), a step fails to halve dn, or max_steps
+    // (<= 0: 10).  x, tail (nullptr: none carried), rhs: column-major ld x nrhs, blocks of 16 columns per pass pair; pairs: interleaved
+    // complex vectors, the measures on moduli.  info: 8 doubles per column on the host (nullptr allowed), see include/russell_hipmf.h.
+    // SUCCESSFUL_EXIT when every column converged, else WARNING_NOT_CONVERGED (x: the best iterate).  The factor, d_vals and the
+    // statistics of the ordinary solves are left as they were.  See numeric.cpp.
+    int32_t solve_extra_precise(double *x, double *tail, const double *rhs, int32_t nrhs, int64_t ld, double dx_tol, int32_t max_steps, double *info, bool on_device,
+                                bool pairs = false);
+    int64_t extra_steps = 0, extra_blocks = 0; // of the last solve_extra_precise: pass pairs after the first summed over the block steps, 16-column blocks
+    double extra_ms[3] = {0.0, 0.0, 0.0};      // HIPMF_EXTRA_TIMING=1: HIP-event time of the last call's residuals, correction pass pairs, updates
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
@@ -593,6 +615,9 @@ class Solver : public SolverDevice {
     template <class P, class O>
     int32_t solve_updated_many_core(double *x, const double *rhs, int32_t nrhs, int64_t ld, const double *values, bool mapped, double rel_tol, int32_t max_steps, int32_t *steps,
                                     double *relres, bool on_device, bool conj_pairs);
+    // the loop of solve_extra_precise, single and blocked (one column is a block of one); P: the measures (ExtraReal, ExtraPairs in numeric.cpp)
+    template <class P>
+    int32_t solve_extra_precise_core(double *x, double *tail, const double *rhs, int32_t nrhs, int64_t ld, double dx_tol, int32_t max_steps, double *info, bool on_device);
     // the blocked transposed pass pair on C <= 16 contiguous columns (stride n): Z = A^{-T} V, unrefined (buffers of tr_prepare_blocked())
     int32_t tr_pass_blk(double *Z, const double *V, int32_t C);
     // the error analysis of both forms; P: what differs (EaReal, EaComplex in numeric.cpp)
