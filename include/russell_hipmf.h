@@ -335,6 +335,59 @@ int32_t solver_hipmf_solve_extra_precise_many(struct InterfaceHIPMF *solver, dou
 int32_t solver_hipmf_solve_extra_precise_device(struct InterfaceHIPMF *solver, double *d_x, double *d_x_tail, const double *d_rhs, int32_t nrhs, int32_t ld,
                                                 double dx_tol, int32_t max_steps, double *info);
 
+/* BORDERED SYSTEMS on the kept factor: block elimination, refined on the whole system.
+ *     [ A   B ] [x]   [f]      A: the factorised ndim x ndim matrix (the values of the last factorize)
+ *     [ C^T D ] [z] = [g]      B, C: ndim x k dense, D: k x k dense, 1 <= k <= HIPMF_BORDER_MAX
+ * -- the bordering branch of russell_nonlin's arc-length continuation (k = 1), mean-value and periodicity constraints, fold and
+ * branch-point systems, a few Lagrange multipliers, and rank-k changes outside A's pattern: (A + U V^T) x = b is the bordered system with
+ * B = U, C = V, D = -I, g = 0 (Woodbury), called as set_border(k, U, V, -I) and solve_bordered(x, NULL, b, NULL, ...).  A symmetric-lower
+ * handle keeps its L D L^T factor, which assembling the augmented matrix would give up.
+ * solver_hipmf_set_border: B, C column-major ndim x k (ldb, ldc >= ndim; border ROW i of the system is COLUMN i of C), D column-major
+ * k x k (ldd >= k).  Copies them to the device, computes W = A^{-1} B with the handle's ordinary blocked refined solve (16 columns per
+ * block), S = D - C^T W on the device and the LU of S with partial pivoting in one workgroup; B, C, D, W, LU(S) and the pivots stay in
+ * device memory.  border_info (NULL allowed): [0] min |u_ii| / max |u_ii| of S's LU  [1] mantissa and [2] base-10 exponent of det S
+ * (the form of solver_hipmf_factorize's determinant: det [A B; C^T D] = det A det S, and [1] x 10^[2] is the arc-length loop's
+ * "denominator" for k = 1)  [3] bytes of device memory held for the border.  An exactly zero pivot of S returns
+ * HIPMF_WARNING_SINGULAR_MATRIX and leaves NO border set.  k = 0 drops the border and frees its memory (the pointers may be NULL).
+ * The border belongs to ONE factorisation: every factorize*, initialize and adopt_factor drops it.
+ * solver_hipmf_solve_bordered: x, f column-major ldx x nrhs (ldx >= ndim), z, g column-major ldz x nrhs (ldz >= k); entries beyond
+ * ndim (k) of a column are not touched; g NULL means g = 0, z NULL means z is not returned.  Per block of up to 16 columns
+ *   y <- one unrefined blocked pass pair of f, t <- g - C^T y, z <- S^{-1} t, x <- y - W z,
+ * then iterative refinement on the bordered system: r_f = f - A x - B z, r_g = g - C^T x - D z, the componentwise backward error omega
+ * over all ndim + k rows as solver_hipmf_solve defines it (denominators |A||x| + |B||z| + |f| and |C|^T|x| + |D||z| + |g|), (r_f, r_g)
+ * through the same four lines, the correction added.  Stop by solve's rule: omega <= eps, or the step did not halve omega (a step that
+ * did not lower it is taken back), or after max_steps steps (<= 0 selects 4).  Two separately refined solves with A are NOT backward
+ * stable for the bordered system when A is ill-conditioned -- near a fold, where bordering is used; this refinement is (DESIGN.md
+ * section 15).  A that is singular to rounding converges slowly or not at all (deflated block elimination is not implemented).
+ * info (NULL allowed), 4 doubles per column on the host: [0] steps taken  [1] the last omega  [2] omega before the first step
+ * [3] state: 0 converged, 1 no progress, 2 step limit.  Returns 0 whatever the state, as solver_hipmf_solve does after refinement.
+ * Per block step ONE blocked pass pair, ONE pass over A, ONE launch per border product, ONE host read of the omegas; a finished column
+ * rides on masked out.  Bit-reproducible from call to call (no floating-point atomics).  NO SIDE EFFECTS on the factor, the values, any
+ * counter, statistic or timer of the ordinary solves, or the bits of a later solve; no Krylov rescue inside (after a factorisation that
+ * replaced pivots the iteration needs more steps or ends as "no progress").
+ * _device: B, C, D (x, z, f, g) are device pointers; border_info / info stay on the host.  The host and _device forms give the same bits.
+ * HIPMF_COUNTER_BORDER_COLUMNS / _BORDERED_STEPS / _BORDERED_BLOCKS report the border in force and the last call.
+ * The residual of a step is accumulated beyond twice the working precision and rounded once (the error-free sums of
+ * solver_hipmf_solve_extra_precise): omega <= eps sits at the noise of a residual evaluated in working precision, which would decide by
+ * chance between "converged" and "no progress"; with it a refined (x, z) is the exact solution rounded.
+ * WHAT IT COSTS (tools/bordered.py, one MI355X, 1M unknowns, profiles/r19_bordered.txt; one step after the start in every case):
+ * set_border_device 2.2 / 6.2 / 26.8 ms for k = 1 / 16 / 64; solve_bordered_device, one column: 1.90 / 2.35 / 4.87 ms against 0.92 ms
+ * for solver_hipmf_solve_device; 16 columns: 7.4 / 12.5 / 38.7 ms against 6.5 ms -- a wide border is dear, the compensated residual and
+ * not the pass pairs is then what is paid for.  k = 1 on host vectors: 2.47 ms against 5.57 ms for two solve calls, two inner products
+ * and the combination by hand, and against 6.6 ms per solve (after 472 + 241 ms of analysis and factorisation) for the assembled matrix.
+ * ERROR_NULL_POINTER (solver; B, C, D when k > 0; x, f), ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order; then
+ * ERROR_HIPMF_INVALID_VALUE for k outside 0 .. HIPMF_BORDER_MAX, a leading dimension that is too small, nrhs < 1, or no border in force
+ * (none set, dropped with k = 0, or dropped by a later factorisation). */
+#define HIPMF_BORDER_MAX 64
+int32_t solver_hipmf_set_border(struct InterfaceHIPMF *solver, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D, int32_t ldd,
+                                double *border_info_len_4, C_BOOL verbose);
+int32_t solver_hipmf_set_border_device(struct InterfaceHIPMF *solver, int32_t k, const double *d_B, int32_t ldb, const double *d_C, int32_t ldc, const double *d_D,
+                                       int32_t ldd, double *border_info_len_4, C_BOOL verbose);
+int32_t solver_hipmf_solve_bordered(struct InterfaceHIPMF *solver, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx, int32_t ldz,
+                                    int32_t max_steps, double *info, C_BOOL verbose);
+int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *solver, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs, int32_t ldx,
+                                           int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -451,6 +504,9 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US 41  /* HIPMF_EXTRA_TIMING=1 (environment, read per call; else 0): microseconds between HIP events around the doubled residuals of that call ... */
 #define HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US 42   /* ... its correction pass pairs ... */
 #define HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US 43    /* ... and its update launches (tools/extra_precise.py) */
+#define HIPMF_COUNTER_BORDER_COLUMNS 44             /* k of the border in force (solver_hipmf_set_border), 0 when none */
+#define HIPMF_COUNTER_BORDERED_STEPS 45             /* refinement steps of the last solver_hipmf_solve_bordered / _device, summed over its blocks */
+#define HIPMF_COUNTER_BORDERED_BLOCKS 46            /* 16-column blocks of that call */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

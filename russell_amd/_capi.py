@@ -64,6 +64,12 @@ SYMBOLS = {
     "solver_hipmf_solve_extra_precise_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                                             C.c_void_p]),
     "complex_solver_hipmf_solve_extra_precise": (C.c_int32, [C.c_void_p, f64p, C.c_void_p, f64p, C.c_double, C.c_int32, C.c_void_p, C.c_int32]),
+    "solver_hipmf_set_border": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "solver_hipmf_set_border_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_bordered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_int32]),
+    "solver_hipmf_solve_bordered_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                       C.c_void_p, C.c_int32]),
     "solver_hipmf_solve_with_error_analysis": (C.c_int32, [C.c_void_p, f64p, f64p, f64p, C.c_int32, C.c_int32]),
     "solver_hipmf_mat_vec_mul": (C.c_int32, [C.c_void_p, f64p, C.c_double, f64p]),
     "solver_hipmf_get_permutation": (C.c_int32, [C.c_void_p, i32p]),

@@ -240,6 +240,48 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_extra_precise_many")
         return x, t, info, code
 
+    WARNING_SINGULAR_MATRIX = 1
+
+    def set_border(self, B, C_, D, verbose=False):
+        """The border of [A B; C^T D] on the kept factor (solver_hipmf_set_border): B, C_ of shape (n, k), D of shape (k, k); k = 0 (or
+        B None) drops it.  Returns (border_info, status): min / max |u_ii| of S = D - C^T A^{-1} B, mantissa and base-10 exponent of
+        det S, device bytes held; status 0 or WARNING_SINGULAR_MATRIX (an exactly zero pivot of S: no border is set); others raise."""
+        info = np.zeros(4)
+        if B is None or np.asarray(B).size == 0:
+            code = self.lib.solver_hipmf_set_border(self.h, 0, None, 0, None, 0, None, 0, info.ctypes.data, int(verbose))
+        else:
+            Bf, Cf, Df = (np.asfortranarray(np.asarray(a, dtype=np.float64).reshape(np.shape(a)[0], -1)) for a in (B, C_, D))
+            k = Bf.shape[1]
+            if Bf.shape != (self.n, k) or Cf.shape != (self.n, k) or Df.shape != (k, k):
+                raise ValueError("set_border expects B, C of shape (%d, k) and D of shape (k, k), got %r, %r, %r" % (self.n, Bf.shape, Cf.shape, Df.shape))
+            code = self.lib.solver_hipmf_set_border(self.h, k, Bf.ctypes.data, self.n, Cf.ctypes.data, self.n, Df.ctypes.data, k, info.ctypes.data, int(verbose))
+        if code not in (0, self.WARNING_SINGULAR_MATRIX):
+            raise self._err(code, "solver_hipmf_set_border")
+        return info, code
+
+    def solve_bordered(self, f, g=None, want_z=True, max_steps=0, ldx=None, ldz=None, verbose=False, x=None, z=None):
+        """[A B; C^T D] [x; z] = [f; g] with the border of set_border, refined on the whole system (solver_hipmf_solve_bordered).
+        f: (n,) or (nrhs, ldx) as solve_many takes it; g: (k,) or (nrhs, ldz), None: g = 0; want_z False: z is not returned.
+        x / z: arrays of those shapes to write into (their padding is left alone).  Returns (x, z or None, info of shape (nrhs, 4))."""
+        k = self.counter("border_columns")
+        fa = np.ascontiguousarray(f, dtype=np.float64)
+        single = fa.ndim == 1
+        fa = fa.reshape(1, -1) if single else fa
+        nrhs = fa.shape[0]
+        ldx = fa.shape[1] if ldx is None else int(ldx)
+        ga = None if g is None else np.ascontiguousarray(g, dtype=np.float64).reshape(nrhs, -1)
+        ldz = (k if ga is None else ga.shape[1]) if ldz is None else int(ldz)
+        x = np.zeros((nrhs, ldx)) if x is None else x
+        z = (np.zeros((nrhs, max(ldz, 1))) if z is None else z) if want_z else None
+        info = np.zeros((nrhs, 4))
+        code = self.lib.solver_hipmf_solve_bordered(self.h, x.ctypes.data, None if z is None else z.ctypes.data, fa.ctypes.data, None if ga is None else ga.ctypes.data,
+                                                    nrhs, ldx, ldz, int(max_steps), info.ctypes.data, int(verbose))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_bordered")
+        if single:
+            return x[0], (None if z is None else z[0]), info[0]
+        return x, z, info
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -263,7 +305,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -385,6 +427,24 @@ class Hipmf:
         if code not in (0, self.WARNING_NOT_CONVERGED):
             raise self._err(code, "solver_hipmf_solve_extra_precise_device")
         return info[:nrhs], code
+
+    def set_border_device(self, k, d_B, d_C, d_D, ldb=None, ldc=None, ldd=None):
+        """set_border with B, C (column-major ld x k) and D (ldd x k) resident on the device; returns (border_info, status)"""
+        info = np.zeros(4)
+        code = self.lib.solver_hipmf_set_border_device(self.h, int(k), d_B, int(ldb or self.n), d_C, int(ldc or self.n), d_D, int(ldd or k), info.ctypes.data, 0)
+        if code not in (0, self.WARNING_SINGULAR_MATRIX):
+            raise self._err(code, "solver_hipmf_set_border_device")
+        return info, code
+
+    def solve_bordered_device(self, d_x, d_z, d_f, d_g, nrhs=1, max_steps=0, ldx=None, ldz=None):
+        """solve_bordered with x, f (column-major ldx x nrhs) and z, g (ldz x nrhs; None allowed) resident on the device; returns info"""
+        nrhs = int(nrhs)
+        info = np.zeros((max(nrhs, 1), 4))
+        code = self.lib.solver_hipmf_solve_bordered_device(self.h, d_x, d_z, d_f, d_g, nrhs, int(ldx or self.n), int(ldz or max(self.counter("border_columns"), 1)),
+                                                           int(max_steps), info.ctypes.data, 0)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_bordered_device")
+        return info[:nrhs]
 
     def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, transpose=False):
         """solve_updated_many with x, rhs (column-major ld x nrhs) and values resident on the device; returns (steps, relres, status)"""

@@ -699,6 +699,52 @@ int32_t solver_hipmf_solve_extra_precise_device(struct InterfaceHIPMF *h, double
     });
 }
 
+// Bordered systems on the kept factor (Solver::set_border, Solver::solve_bordered; kernels_border.hpp).  Status codes in this order:
+// ERROR_NULL_POINTER (the handle; B, C, D with k > 0; x, f), ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION, then
+// ERROR_HIPMF_INVALID_VALUE (k outside 0 .. HIPMF_BORDER_MAX, a leading dimension that is too small, nrhs < 1, no border in force).
+static int32_t set_border_body(struct InterfaceHIPMF *h, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D, int32_t ldd,
+                               double *border_info, C_BOOL verbose, bool on_device) {
+    if (!h) return ERROR_NULL_POINTER;
+    if (k > 0 && k <= HIPMF_BORDER_MAX && (!B || !C || !D)) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    return h->solver.set_border(k, B, ldb, C, ldc, D, ldd, border_info, on_device);
+}
+
+int32_t solver_hipmf_set_border(struct InterfaceHIPMF *h, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D, int32_t ldd,
+                                double *border_info_len_4, C_BOOL verbose) {
+    return guarded(h, [&]() { return set_border_body(h, k, B, ldb, C, ldc, D, ldd, border_info_len_4, verbose, false); });
+}
+
+int32_t solver_hipmf_set_border_device(struct InterfaceHIPMF *h, int32_t k, const double *d_B, int32_t ldb, const double *d_C, int32_t ldc, const double *d_D, int32_t ldd,
+                                       double *border_info_len_4, C_BOOL verbose) {
+    return guarded(h, [&]() { return set_border_body(h, k, d_B, ldb, d_C, ldc, d_D, ldd, border_info_len_4, verbose, true); });
+}
+
+static int32_t solve_bordered_body(struct InterfaceHIPMF *h, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx, int32_t ldz,
+                                   int32_t max_steps, double *info, C_BOOL verbose, bool on_device, const char *who) {
+    if (!h || !x || !f) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    const int32_t code = h->solver.solve_bordered(x, z, f, g, nrhs, ldx, ldz, max_steps, info, on_device);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("%s: %d column(s), border of %d: %lld block step(s) in %lld block(s)\n", who, nrhs, h->solver.bd_k, (long long)h->solver.bordered_steps,
+               (long long)h->solver.bordered_blocks);
+    return code;
+}
+
+int32_t solver_hipmf_solve_bordered(struct InterfaceHIPMF *h, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx, int32_t ldz,
+                                    int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_bordered_body(h, x, z, f, g, nrhs, ldx, ldz, max_steps, info, verbose, false, "solver_hipmf_solve_bordered"); });
+}
+
+int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *h, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs, int32_t ldx,
+                                           int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_bordered_body(h, d_x, d_z, d_f, d_g, nrhs, ldx, ldz, max_steps, info, verbose, true, "solver_hipmf_solve_bordered_device"); });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -815,6 +861,9 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US: return (int64_t)(1e3 * s.extra_ms[0]);
     case HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US: return (int64_t)(1e3 * s.extra_ms[1]);
     case HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US: return (int64_t)(1e3 * s.extra_ms[2]);
+    case HIPMF_COUNTER_BORDER_COLUMNS: return s.bd_k;
+    case HIPMF_COUNTER_BORDERED_STEPS: return s.bordered_steps;
+    case HIPMF_COUNTER_BORDERED_BLOCKS: return s.bordered_blocks;
     default: return -1;
     }
 }

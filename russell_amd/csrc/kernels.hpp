@@ -14,3 +14,4 @@
 #include "kernels_solve_leaf.hpp"
 #include "kernels_vector.hpp"
 #include "kernels_refine_extra.hpp"
+#include "kernels_border.hpp"

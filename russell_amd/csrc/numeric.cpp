@@ -2137,6 +2137,7 @@ int32_t Solver::run_factor() {
     const int32_t n = S.n;
     const int64_t nnz = S.nnz_a;
     int64_t launches = 0;
+    bd_k = 0; // (a border belongs to the factorisation it was set for: Solver::set_border)
     HIPC(hipEventRecord((hipEvent_t)ev[0], STREAM), ERROR_HIP_SYNCHRONIZE);
     // (with a matching in force the scalings dr, dc of initialize stay: the structure was chosen for them)
     if (!matched)
@@ -4380,6 +4381,237 @@ int32_t Solver::solve_extra_precise(double *x, double *tail, const double *rhs, 
                  : solve_extra_precise_core<ExtraReal>(x, tail, rhs, nrhs, ld, dx_tol, max_steps, info, on_device);
 }
 
+// ---- bordered systems on the kept factor (solver_hipmf_set_border, solver_hipmf_solve_bordered; kernels_border.hpp) ----
+//     [ A   B ] [x]   [f]
+//     [ C^T D ] [z] = [g]      B, C: n x k dense, D: k x k dense, k <= BORDER_MAX
+// Block elimination with W = A^{-1} B and S = D - C^T W needs one pass pair per right-hand side, but with an ill-conditioned A (near a
+// fold: the case bordering exists for) it loses cond(A) eps even when every solve with A is refined on its own.  Iterative refinement
+// on the bordered system as a whole, with the elimination as the approximate inverse, repairs that (Govaerts & Pryce 1993; Govaerts,
+// Numerical Methods for Bifurcations of Dynamical Equilibria, 2000, ch. 3).  Per block of BORDER_COLS columns, in the user's space:
+//   eliminate(r_f, r_g): y <- one unrefined pass pair of r_f (solve_core without refinement under the nested solve guard),
+//                        t <- r_g - C^T y (k_border_gram + k_border_reduce), dz <- S^{-1} t (k_border_small_solve), dx <- y - W dz (k_border_apply)
+//   start: (x, z) <- eliminate(f, g)
+//   measure: r_f = f - A x - B z with den = |A||x| + |B||z| + |f| (k_border_residual_n), r_g = g - C^T x - D z with den =
+//            |C|^T|x| + |D||z| + |g| (k_border_rows_part, k_border_rows), every row accumulated beyond twice the working precision and
+//            rounded once (why: kernels_border.hpp); ONE host read of the omegas of the block's columns, omega = the maximum over all n + k rows
+//   the rule of solve() per column: omega <= eps converged; a step that did not lower omega is taken back, "no progress"; a step that
+//   did not halve it stays, "no progress"; max_steps steps "step limit"; else (x, z) += eliminate(r_f, r_g), the old (x, z) kept.
+// A finished column leaves the mask: its residual columns are zeros through the next pass pair, the correction leaves it alone.
+namespace {
+// the border in force is given up unless the call that sets it reaches its end
+struct BorderUndo {
+    Solver &s;
+    bool keep = false;
+    ~BorderUndo() {
+        if (!keep) s.drop_border();
+    }
+};
+} // namespace
+
+void Solver::drop_border() {
+    DeviceScope dev_scope(device);
+    static_cast<SolverBorder &>(*this) = SolverBorder();
+}
+
+int32_t Solver::set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (k < 0 || k > BORDER_MAX) return ERROR_HIPMF_INVALID_VALUE;
+    if (info) info[0] = info[1] = info[2] = info[3] = 0.0;
+    if (k == 0) {
+        drop_border();
+        return SUCCESSFUL_EXIT;
+    }
+    if (!B || !C || !D) return ERROR_NULL_POINTER;
+    const int32_t n = S.n;
+    if (ldb < n || ldc < n || ldd < k) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    drop_border();
+    BorderUndo undo{*this};
+    const int32_t kp = (k + 15) / 16 * 16, nch = (n + BORDER_CHUNK - 1) / BORDER_CHUNK;
+    const size_t npk = (size_t)n * kp, kk2 = (size_t)kp * kp, tile = (size_t)kp * BORDER_COLS, nb = sizeof(double) * (size_t)n;
+    DeviceArray<double> d_cols, d_wcol, d_gs; // the border's columns as they came (C, then B), a block of W, C^T W
+    HIPC(d_bd_B.alloc(npk), ERROR_HIP_MALLOC);
+    HIPC(d_bd_C.alloc(npk), ERROR_HIP_MALLOC);
+    HIPC(d_bd_W.alloc(npk), ERROR_HIP_MALLOC);
+    HIPC(d_bd_D.alloc(kk2), ERROR_HIP_MALLOC);
+    HIPC(d_bd_LU.alloc(kk2), ERROR_HIP_MALLOC);
+    HIPC(d_bd_piv.alloc((size_t)kp), ERROR_HIP_MALLOC);
+    HIPC(d_bd_rec.alloc(BORDER_REC), ERROR_HIP_MALLOC);
+    HIPC(d_bd_part.alloc(BORDER_PART * (size_t)nch * tile), ERROR_HIP_MALLOC); // (the widest user: k_border_rows_part)
+    HIPC(d_cols.alloc((size_t)n * k), ERROR_HIP_MALLOC);
+    HIPC(d_wcol.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
+    HIPC(d_gs.alloc(kk2), ERROR_HIP_MALLOC);
+    const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const dim3 b256(256), gp((unsigned)(((int64_t)n * k + 255) / 256));
+    HIPC(hipMemsetAsync(d_bd_B, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(d_bd_C, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(d_bd_W, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(d_bd_D, 0, sizeof(double) * kk2, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(d_bd_piv, 0, sizeof(int32_t) * (size_t)kp, STREAM), ERROR_HIP_MEMCPY);
+    for (int32_t j = 0; j < k; j++) {
+        HIPC(hipMemcpyAsync(d_cols + (size_t)j * n, C + (int64_t)j * ldc, nb, in, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipMemcpyAsync(d_bd_D + (size_t)j * kp, D + (int64_t)j * ldd, sizeof(double) * (size_t)k, in, STREAM), ERROR_HIP_MEMCPY);
+    }
+    hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, k, kp, 0, (const double *)d_cols, (int64_t)n, (double *)d_bd_C);
+    for (int32_t j = 0; j < k; j++) HIPC(hipMemcpyAsync(d_cols + (size_t)j * n, B + (int64_t)j * ldb, nb, in, STREAM), ERROR_HIP_MEMCPY);
+    hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, k, kp, 0, (const double *)d_cols, (int64_t)n, (double *)d_bd_B);
+    {
+        const NestedSolveGuard guard(*this); // (W comes from ordinary refined solves: their statistics are not the caller's)
+        for (int32_t j0 = 0; j0 < k; j0 += BORDER_COLS) {
+            const int32_t nk = std::min(BORDER_COLS, k - j0);
+            const int32_t code = solve(d_wcol, d_cols + (size_t)j0 * n, nk, n, true);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)n * nk + 255) / 256)), b256, 0, STREAM, n, nk, kp, j0, (const double *)d_wcol, (int64_t)n,
+                               (double *)d_bd_W);
+            hipLaunchKernelGGL(k_border_gram, dim3((unsigned)nch, (unsigned)(kp / 16)), dim3(64), 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)d_wcol,
+                               (int64_t)n, nk, (double *)d_bd_part);
+            hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, nch, kp, (const double *)d_bd_part, d_gs + (size_t)j0 * kp);
+        }
+    }
+    hipLaunchKernelGGL(k_border_lu, dim3(1), b256, 0, STREAM, k, kp, (const double *)d_bd_D, (const double *)d_gs, (double *)d_bd_LU, (int32_t *)d_bd_piv, (double *)d_bd_rec);
+    double rec[BORDER_REC];
+    HIPC(hipMemcpyAsync(rec, d_bd_rec, sizeof rec, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    if (rec[4] != 0.0) return WARNING_SINGULAR_MATRIX; // (an exactly zero pivot of S: no border is left set)
+    bd_k = k, bd_kp = kp, bd_chunks = nch;
+    bd_bytes = (int64_t)(sizeof(double) * (3 * npk + 2 * kk2 + BORDER_PART * (size_t)nch * tile + BORDER_REC) + sizeof(int32_t) * (size_t)kp);
+    if (info) info[0] = rec[1] > 0.0 ? rec[0] / rec[1] : 0.0, info[1] = rec[2], info[2] = rec[3], info[3] = (double)bd_bytes;
+    if (opt.verbose)
+        fprintf(stderr, "hipmf: set_border: k = %d, min / max |u_ii| of S = %.3e, det S = %.6f x 10^%.0f, %.1f MB on the device\n", k, rec[1] > 0.0 ? rec[0] / rec[1] : 0.0,
+                rec[2], rec[3], 1e-6 * (double)bd_bytes);
+    undo.keep = true;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::solve_bordered(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                               bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!x || !f) return ERROR_NULL_POINTER;
+    const int32_t n = S.n, k = bd_k, kp = bd_kp, nch = bd_chunks;
+    if (k < 1 || nrhs < 1 || ldx < n || ((z || g) && ldz < k)) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    const double EPS = 2.220446049250313e-16;
+    const int32_t limit = max_steps > 0 ? max_steps : 4;
+    bordered_steps = bordered_blocks = 0;
+    if (info)
+        for (int64_t q = 0; q < 4 * (int64_t)nrhs; q++) info[q] = 0.0;
+    const int32_t C = std::min(nrhs, BORDER_COLS);
+    const size_t tile = (size_t)kp * BORDER_COLS;
+    if (bd_cols < C || bd_small_kp != kp) {
+        bd_cols = 0;
+        HIPC(d_bd_vec.alloc(5 * (size_t)n * C), ERROR_HIP_MALLOC);
+        HIPC(d_bd_small.alloc(6 * tile), ERROR_HIP_MALLOC);
+        HIPC(d_bd_nrm.alloc((size_t)RES_NORM_WORDS * C + BORDER_COLS), ERROR_HIP_MALLOC);
+        HIPC(h_bd_nrm.alloc((size_t)RES_NORM_WORDS * C + BORDER_COLS), ERROR_HIP_MALLOC);
+        bd_cols = C, bd_small_kp = kp;
+    }
+    const size_t blk = (size_t)n * bd_cols, nb = sizeof(double) * (size_t)n, kb = sizeof(double) * (size_t)k;
+    double *const d_R = d_bd_vec, *const d_Y = d_bd_vec + blk, *const d_XS = d_bd_vec + 2 * blk;
+    double *const d_GG = d_bd_small, *const d_Z = d_bd_small + tile, *const d_ZS = d_bd_small + 2 * tile, *const d_DZ = d_bd_small + 3 * tile;
+    double *const d_RG = d_bd_small + 4 * tile, *const d_G = d_bd_small + 5 * tile;
+    const dim3 b256(256), b64(64), gt((unsigned)((n + 63) / 64)), gg((unsigned)nch, (unsigned)(kp / 16));
+    const int64_t stride = on_device ? ldx : (int64_t)n;
+    const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+
+    const NestedSolveGuard guard(*this);
+    guard.unrefined_quiet();
+    for (int32_t j0 = 0; j0 < nrhs; j0 += BORDER_COLS) {
+        const int32_t nk = std::min(BORDER_COLS, nrhs - j0);
+        bordered_blocks++;
+        double *const xb = on_device ? x + (int64_t)j0 * ldx : d_bd_vec + 3 * blk;
+        const double *const fb = on_device ? f + (int64_t)j0 * ldx : d_bd_vec + 4 * blk;
+        HIPC(hipMemsetAsync(d_bd_small, 0, sizeof(double) * 6 * tile, STREAM), ERROR_HIP_MEMCPY); // (the rows k .. kp - 1 stay zero: g = 0 without a g)
+        for (int32_t c = 0; c < nk; c++) {
+            if (!on_device) HIPC(hipMemcpyAsync(d_bd_vec + 4 * blk + (size_t)c * n, f + (int64_t)(j0 + c) * ldx, nb, in, STREAM), ERROR_HIP_MEMCPY);
+            if (g) HIPC(hipMemcpyAsync(d_GG + (size_t)c * kp, g + (int64_t)(j0 + c) * ldz, kb, in, STREAM), ERROR_HIP_MEMCPY);
+        }
+        const size_t nrm_words = (size_t)RES_NORM_WORDS * nk + BORDER_COLS;
+        unsigned long long *const d_nrm = d_bd_nrm;
+        double *const d_omega_g = reinterpret_cast<double *>(d_nrm + (size_t)RES_NORM_WORDS * nk);
+        const double *const h_omega_g = h_bd_nrm + (size_t)RES_NORM_WORDS * nk;
+        uint32_t mask = nk >= 32 ? ~0u : ((1u << nk) - 1u);
+
+        // (dx, dz) of the residual (rf, rg), dx = y - W dz with y left in ydst by the pass pair; fresh: (x, z) <- (dx, dz), else (x, z) += (dx, dz)
+        auto eliminate = [&](double *ydst, int64_t ystr, const double *rf, const double *rg, bool fresh) -> int32_t {
+            const int32_t code = solve_core(ydst, rf, nk, ystr, true);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_border_gram, gg, b64, 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)ydst, ystr, nk, (double *)d_bd_part);
+            hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, nch, kp, (const double *)d_bd_part, d_G);
+            hipLaunchKernelGGL(k_border_small_solve, dim3((unsigned)nk), b64, 0, STREAM, k, kp, (const double *)d_bd_LU, (const int32_t *)d_bd_piv, rg, (const double *)d_G,
+                               d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
+            hipLaunchKernelGGL(k_border_apply, gt, b256, 0, STREAM, n, k, kp, (const double *)d_bd_W, (const double *)d_DZ, nk, mask, (const double *)ydst, ystr, xb, stride,
+                               fresh ? (double *)nullptr : d_XS, (int64_t)n);
+            return SUCCESSFUL_EXIT;
+        };
+        // the residual of (x, z) over all n + k rows into (d_R, d_RG), the omegas of the columns of the mask to the host
+        auto measure = [&]() -> int32_t {
+            HIPC(hipMemsetAsync(d_nrm, 0, nrm_words * sizeof(unsigned long long), STREAM), ERROR_HIP_MEMCPY);
+            hipLaunchKernelGGL(k_border_residual_n, dim3((unsigned)((n + 255) / 256)), b256, 0, STREAM, n, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, k, kp,
+                               (const double *)d_bd_B, (const double *)d_Z, (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
+            hipLaunchKernelGGL(k_border_rows_part, dim3((unsigned)nch, (unsigned)nk), b256, 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)xb, stride, mask,
+                               (double *)d_bd_part);
+            hipLaunchKernelGGL(k_border_rows, dim3((unsigned)nk), b64, 0, STREAM, k, kp, nch, (const double *)d_bd_D, (const double *)d_GG, (const double *)d_bd_part,
+                               (const double *)d_Z, d_RG, d_omega_g, mask);
+            HIPC(hipMemcpyAsync(h_bd_nrm, d_nrm, nrm_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+            return SUCCESSFUL_EXIT;
+        };
+
+        int32_t code = eliminate(xb, stride, fb, d_GG, true);
+        if (code != SUCCESSFUL_EXIT) return code;
+        struct Column {
+            bool active = true;
+            int32_t steps = 0, state = 0;
+            double prev = INFINITY, omega = 0.0, omega0 = 0.0;
+        } col[BORDER_COLS];
+        for (int32_t it = 0; mask != 0; it++) {
+            code = measure();
+            if (code != SUCCESSFUL_EXIT) return code;
+            for (int32_t c = 0; c < nk; c++) {
+                Column &q = col[c];
+                if (!q.active) continue;
+                double omega = h_omega_g[c];
+                for (int32_t sl = 0; sl < RES_SLOTS; sl++) omega = std::max(omega, h_bd_nrm[(size_t)RES_NORM_WORDS * c + (size_t)sl * RES_SLOT_WORDS + 1]);
+                if (guard.verbose && j0 + c == 0) fprintf(stderr, "hipmf: solve_bordered: after %d step(s): omega = %.3e\n", it, omega);
+                if (it == 0) q.omega0 = omega;
+                if (it > 0 && !(omega < q.prev)) { // the step did not lower omega: taken back
+                    HIPC(hipMemcpyAsync(xb + (int64_t)c * stride, d_XS + (size_t)c * n, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                    HIPC(hipMemcpyAsync(d_Z + (size_t)c * kp, d_ZS + (size_t)c * kp, sizeof(double) * (size_t)kp, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+                    q.state = 1, q.active = false;
+                    continue;
+                }
+                q.omega = omega;
+                if (omega <= EPS) q.state = 0, q.active = false;
+                else if (it > 0 && omega > 0.5 * q.prev) q.state = 1, q.active = false;
+                else if (it >= limit) q.state = 2, q.active = false;
+                else q.prev = omega;
+            }
+            mask = 0;
+            for (int32_t c = 0; c < nk; c++)
+                if (col[c].active) mask |= 1u << c, col[c].steps = it + 1;
+            if (!mask) break;
+            code = eliminate(d_Y, (int64_t)n, d_R, d_RG, false);
+            if (code != SUCCESSFUL_EXIT) return code;
+            bordered_steps++;
+        }
+        for (int32_t c = 0; c < nk; c++) {
+            const Column &q = col[c];
+            if (info) {
+                double *const o = info + 4 * (size_t)(j0 + c);
+                o[0] = q.steps, o[1] = q.omega, o[2] = q.omega0, o[3] = q.state;
+            }
+            if (!on_device) HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ldx, xb + (size_t)c * n, nb, out, STREAM), ERROR_HIP_MEMCPY);
+            if (z) HIPC(hipMemcpyAsync(z + (int64_t)(j0 + c) * ldz, d_Z + (size_t)c * kp, kb, out, STREAM), ERROR_HIP_MEMCPY);
+        }
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the staging blocks are the next block's)
+    }
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    return SUCCESSFUL_EXIT;
+}
+
 int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (nnz_lower < 1 || (int64_t)emap.size() != S.nnz_a) return ERROR_HIPMF_INVALID_VALUE;
@@ -4399,7 +4631,7 @@ int32_t Solver::adopt_factor(const double *d_values) {
     if (lc != SUCCESSFUL_EXIT) return lc;
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
     n_perturbed = n_zero_pivot = 0;
-    factorized = true;
+    factorized = true, bd_k = 0;
     return SUCCESSFUL_EXIT;
 }
 

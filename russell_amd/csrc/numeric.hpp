@@ -214,10 +214,27 @@ struct SolverExtraPrecise {
     EventOwner xr_ev[4];  // HIPMF_EXTRA_TIMING=1: around the residual, the pass pair and the update of a step
 };
 
+// solver_hipmf_set_border / solver_hipmf_solve_bordered (kernels_border.hpp).  The border in force: B, C and W = A^{-1} B packed row-major
+// n x kp (kp = k rounded up to a multiple of 16), D, the LU of S = D - C^T W (column-major, leading dimension kp) and its pivots, the
+// scratch of the Gram products' partial tiles.  Allocated by set_border, freed by set_border(0) or with the handle; a factorisation
+// only clears bd_k.  The blocks of solve_bordered are allocated at its first call and regrown for a wider block: five n x C blocks -- the
+// residual, the pass pair's result, the x a step can be taken back from, and the staging of x and f of a host-pointer call --, the vectors of order kp of a block, the omegas of a block step and their pinned mirror.
+struct SolverBorder {
+    int32_t bd_k = 0, bd_kp = 0;   // border columns in force (0: none), and what the arrays are padded to
+    int32_t bd_chunks = 0;         // partial sums per entry of a Gram product: ceil(n / BORDER_CHUNK)
+    int64_t bd_bytes = 0;          // device memory held for the border
+    DeviceArray<double> d_bd_B, d_bd_C, d_bd_W, d_bd_D, d_bd_LU, d_bd_part, d_bd_rec;
+    DeviceArray<int32_t> d_bd_piv;
+    DeviceArray<double> d_bd_vec, d_bd_small;
+    DeviceArray<unsigned long long> d_bd_nrm;
+    PinnedArray<double> h_bd_nrm;
+    int32_t bd_cols = 0, bd_small_kp = 0; // columns and border width the blocks of solve_bordered are allocated for (0: not allocated)
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise {
+struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise, SolverBorder {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -414,6 +431,22 @@ class Solver : public SolverDevice {
                                 bool pairs = false);
     int64_t extra_steps = 0, extra_blocks = 0; // of the last solve_extra_precise: pass pairs after the first summed over the block steps, 16-column blocks
     double extra_ms[3] = {0.0, 0.0, 0.0};      // HIPMF_EXTRA_TIMING=1: HIP-event time of the last call's residuals, correction pass pairs, updates
+    // The bordered system [A B; C^T D] [x; z] = [f; g] on the kept factor (kernels_border.hpp; B, C: column-major n x k, D: k x k).
+    // set_border copies the border to the device, computes W = A^{-1} B with solve() in blocks of 16 columns, S = D - C^T W and its LU
+    // with partial pivoting in one workgroup; info (nullptr allowed): min / max |u_ii| of S, det S as mantissa and base-10 exponent,
+    // bytes held.  k == 0 frees the border.  WARNING_SINGULAR_MATRIX for an exactly zero pivot of S: no border is left set.
+    // Every factorisation drops the border (bd_k = 0).
+    int32_t set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device);
+    // Block elimination refined on the whole system, per block of 16 columns: y = one unrefined pass pair of f, t = g - C^T y,
+    // z = S^{-1} t, x = y - W z; then steps on the residual (f - A x - B z, g - C^T x - D z) by the stopping rule of solve() on the
+    // componentwise backward error omega over all n + k rows, at most max_steps (<= 0: 4).  x, f: column-major ldx x nrhs; z, g:
+    // ldz x nrhs (nullptr: z is not returned, g = 0).  info: 4 doubles per column on the host (steps, omega, omega before the first
+    // step, state 0 converged / 1 no progress / 2 step limit).  The factor, d_vals and the statistics of the ordinary solves are
+    // left as they were.  See numeric.cpp.
+    int32_t solve_bordered(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                           bool on_device);
+    void drop_border(); // frees the border's device memory
+    int64_t bordered_steps = 0, bordered_blocks = 0; // of the last solve_bordered: block steps summed over the blocks, 16-column blocks
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
@@ -443,7 +476,7 @@ class Solver : public SolverDevice {
     int32_t set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap);
     int64_t expansion_inputs() const { return nnz_low; }
     const std::vector<int32_t> &expansion_map() const { return h_emap; }
-    void mark_factor_adopted(int32_t root_perturbed = 0) { n_perturbed = root_perturbed, n_zero_pivot = 0, factorized = true; } // ... including the matrix values; the root's count of replaced pivots decides about the Krylov rescue here too
+    void mark_factor_adopted(int32_t root_perturbed = 0) { n_perturbed = root_perturbed, n_zero_pivot = 0, factorized = true, bd_k = 0; } // ... including the matrix values; the root's count of replaced pivots decides about the Krylov rescue here too
     void *d_diag_ptr() const { return d_diag; }
     // FNV-1a over what two handles must share to exchange a factor: the fill-reducing permutation, the matching's row permutation, the
     // layout of the pool (computed at initialize / after a re-matching factorize)
