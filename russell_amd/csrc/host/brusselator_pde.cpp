@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "russell_host.hpp"
+#include "../tunables.hpp" // (env_text: the sources read the environment in one place)
 
 using namespace russell;
 using Vec = std::vector<double>;
@@ -270,7 +271,7 @@ class Radau5 {
             }
             if (er) return er;
             if (ec) return ec;
-            if (getenv("BRUS_DEBUG")) {
+            if (hipmf::env_text("BRUS_DEBUG")) {
                 VerifyLinSys vr, vc;
                 VerifyLinSys::from(vr, kk_real, dw0, v0);
                 VerifyLinSys::from_complex(vc, kk_comp, dw12, v12);
@@ -447,7 +448,7 @@ StrError solve(Radau5 &actual, const Params &params, Work &work, Vec &y, double 
         work.stats.n_steps++;
         StrError e = actual.step(work, x, y, h);
         if (e) return e;
-        if (getenv("BRUS_DEBUG")) fprintf(stderr, "step %zu x=%.6g h=%.6g div=%d rel_error=%.4g newt=%zu\n", work.stats.n_steps, x, h, (int)work.iterations_diverging, work.rel_error, work.stats.n_iterations);
+        if (hipmf::env_text("BRUS_DEBUG")) fprintf(stderr, "step %zu x=%.6g h=%.6g div=%d rel_error=%.4g newt=%zu\n", work.stats.n_steps, x, h, (int)work.iterations_diverging, work.rel_error, work.stats.n_iterations);
         if (work.iterations_diverging) {
             work.iterations_diverging = false;
             work.follows_reject_step = true;

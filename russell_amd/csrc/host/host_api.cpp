@@ -17,6 +17,7 @@
 #include <sstream>
 
 #include "../../../include/russell_hipmf.h"
+#include "../tunables.hpp" // (env_text: the sources read the environment in one place)
 
 namespace russell {
 
@@ -784,7 +785,7 @@ bool load_backend() {
     g_backend.tried = true;
     std::string path = g_lib_path;
     if (path.empty()) {
-        const char *env = getenv("RUSSELL_HIPMF_LIB");
+        const char *env = hipmf::env_text("RUSSELL_HIPMF_LIB");
         if (env) path = env;
     }
     if (path.empty()) {

@@ -166,8 +166,7 @@ static int32_t c_initialize_body(struct InterfaceComplexHIPMF *h, int32_t orderi
     if (pivot_epsilon >= 0.0) no.pivot_epsilon = pivot_epsilon;
     if (refinement_nstep >= 0) no.refinement_nstep = refinement_nstep;
     no.verbose = verbose == 1;
-    no.complex_pairs = true;
-    if (const char *e = getenv("HIPMF_COMPLEX_PAIRS")) no.complex_pairs = atoi(e) != 0;
+    no.complex_pairs = Tunables::now(&Tunables::complex_pairs);
     h->effective_ordering = (ordering == HIPMF_ORDERING_NONE || ordering == HIPMF_ORDERING_AMD || ordering == HIPMF_ORDERING_BEST) ? ordering : HIPMF_ORDERING_NESTED_DISSECTION; // (BEST: resolved once the analysis has chosen)
     // the values (when given) let the analysis apply the maximum-product matching to a weak diagonal, as for real matrices
     std::vector<double> v2;

@@ -192,8 +192,7 @@ static int32_t initialize_body(struct InterfaceHIPMF *h, int32_t ordering, int32
     // The caller's interface does not change: it keeps passing lower-triangle values (HIPMF_COUNTER_SYM_EXPANDED tells).
     bool expand = false;
     if (sym_lower && values && ndim > 1 && no.matching > 0 && row_pointers[0] == 0 && validate_csr(ndim, row_pointers, col_indices) == 0) {
-        const char *e = getenv("HIPMF_SYM_EXPAND");
-        if (!e || atoi(e) != 0) expand = sym_lower_diagonal_is_weak(ndim, row_pointers, col_indices, values);
+        if (Tunables::now(&Tunables::sym_expand)) expand = sym_lower_diagonal_is_weak(ndim, row_pointers, col_indices, values);
     }
     h->so_keep = so;
     // (no values yet: with HIPMF_OPTION_SYM_RECHECK the first factorize looks at the diagonal)
@@ -303,9 +302,8 @@ static int32_t finish_factorize(struct InterfaceHIPMF *h, int32_t code, int32_t 
 static int32_t recheck_symmetric_diagonal(struct InterfaceHIPMF *h, const double *host_values, bool verbose) {
     if (!h->sym_unchecked) return SUCCESSFUL_EXIT;
     h->sym_unchecked = false;
-    const char *e = getenv("HIPMF_SYM_EXPAND");
     const Solver &sv = h->solver;
-    if ((!e || atoi(e) != 0) && sv.S.sym_lower && !h->expanded && sv.nnz_in_values() == 0 && sv.S.n > 1 &&
+    if (Tunables::now(&Tunables::sym_expand) && sv.S.sym_lower && !h->expanded && sv.nnz_in_values() == 0 && sv.S.n > 1 &&
         sym_lower_diagonal_is_weak(sv.S.n, sv.kept_row_pointers().data(), sv.kept_col_indices().data(), host_values)) {
         const std::vector<int32_t> rp = sv.kept_row_pointers(), ci = sv.kept_col_indices();
         const NumericOptions no = sv.opt;
@@ -1025,10 +1023,9 @@ static int32_t broadcast_factor_body(struct InterfaceHIPMF *h, void *comm, int32
     // above), so every rank computes the same slices; the bytes past the last whole slice and the small parts use ncclBroadcast.
     // HIPMF_BCAST_SLICES=0 keeps the plain broadcast.
     int nranks = 1;
-    const bool want_slices = !(getenv("HIPMF_BCAST_SLICES") && atoi(getenv("HIPMF_BCAST_SLICES")) == 0);
+    const bool want_slices = Tunables::now(&Tunables::bcast_slices);
     if (g_rccl.p2p() && g_rccl.comm_count((ncclComm_t)comm, &nranks) != ncclSuccess) nranks = 1;
-    int64_t slice_min = 64ll << 20;
-    if (const char *e = getenv("HIPMF_BCAST_SLICE_MIN")) slice_min = std::max<int64_t>(4096, atoll(e));
+    const int64_t slice_min = (int64_t)Tunables::now(&Tunables::bcast_slice_min);
     const int64_t chunk = 256ll << 20; // (plain broadcast: large messages keep the links of a ring busy)
     int64_t total = 0;
     for (int i = 0; i < 6; i++) {

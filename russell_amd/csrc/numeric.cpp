@@ -68,6 +68,7 @@ struct DeviceScope {
     }
 };
 
+static_assert(Tunables::MID_MMAX_CAP == MID_MMAX && Tunables::BLOCK_GROUPS_CAP == SF_GMAX, "tunables.hpp clamps by the kernels' constants");
 constexpr int32_t MAX_LDS_DOUBLES = 7936; // 62 KiB of dynamic LDS for the w1 / v vectors of the big-front solves
 
 Solver::Solver() {}
@@ -90,9 +91,6 @@ void Solver::release() {
     static_cast<SolverDevice &>(*this) = SolverDevice();
     initialized = factorized = false, matched = false;
     tree_active = tag_active = tags_armed = false, work_up = work_arm0 = 0;
-    // (a hand-off time-out sends ONE analysis to the level-set launches -- the next initialize of this handle starts over with the
-    //  dependency-driven solves; HIPMF_FUSED_SOLVE=0 is read again there)
-    use_fused = true;
     sym_diag_looked = sym_weak_diag_seen = false;
     block_groups_last = 0;
 }
@@ -100,6 +98,7 @@ void Solver::release() {
 int32_t Solver::initialize(int32_t n, const int32_t *rp, const int32_t *ci, bool sym_lower, const SymbolicOptions &sopt,
                            const NumericOptions &nopt, const double *values) {
     if (initialized) return ERROR_ALREADY_INITIALIZED;
+    requested = Tunables::from_env(); // (the one place: a re-matching factorize re-plans under the knobs of this call)
     // any failure leaves the handle as new: nothing allocated on the device, initialize may be tried again -- also when the failure
     // is an exception of the calling thread (a host allocation in the matching or the analysis: the device set-up thread has allocated
     // streams, events and structure arrays by then)
@@ -121,6 +120,9 @@ int32_t Solver::initialize(int32_t n, const int32_t *rp, const int32_t *ci, bool
 int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci, bool sym_lower, const SymbolicOptions &sopt,
                                 const NumericOptions &nopt, const double *values) {
     opt = nopt;
+    // the effective knobs start over from what initialize() was asked for (a hand-off time-out, like a failed graph capture,
+    // sends ONE analysis to the fallback launches); the adjustments for this matrix follow below and in upload_plan
+    static_cast<Tunables &>(*this) = requested;
     // (verbose: wall-clock of the host-side pieces of initialize, printed at the end)
     auto lap_t = std::chrono::steady_clock::now();
     std::vector<std::pair<const char *, double>> laps;
@@ -176,7 +178,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
                 int rtv = 0;
                 const bool known = hipGetDeviceProperties(&prop, device) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0 &&
                                    hipRuntimeGetVersion(&rtv) == hipSuccess && rtv / 10000000 == 7;
-                event_fence_free = known && !(getenv("HIPMF_EVENT_FENCE") && atoi(getenv("HIPMF_EVENT_FENCE")) != 0);
+                event_fence_free = known && !event_fence;
                 if (event_fence_free) xflags |= hipEventDisableSystemFence;
             }
 #endif
@@ -195,7 +197,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
                 const double limit = 0.95 * (double)free_b;
                 live_pool_limit.store(limit);
             }
-            if (const char *e = getenv("HIPMF_POOL_LIMIT_GB")) live_pool_limit.store(0.95e9 * atof(e)); // (tests: force the refusal)
+            if (given(&Tunables::pool_limit_gb)) live_pool_limit.store(0.95e9 * pool_limit_gb); // (tests: force the refusal)
         }
         // matrix structure (kept for the refinement SpMV) and per-entry row/col indices
         const int64_t nnz = rp[n];
@@ -263,100 +265,22 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
     so.augment_above = SMALL_F;
     // symmetric-lower input (general_symmetric / positive_definite, interface_cudss.cu:324-333): the big fronts are factorised
     // as L D L^T on their lower triangle -- half the flops, half the factor (HIPMF_SYM_LDLT=0: LU of the mirrored matrix)
-    so.symmetric_ldlt = sym_lower;
-    if (const char *e = getenv("HIPMF_SYM_LDLT")) so.symmetric_ldlt = sym_lower && atoi(e) != 0;
+    so.symmetric_ldlt = sym_lower && sym_ldlt;
     if (opt.complex_pairs && (sym_lower || n % 2 != 0)) {
         last_error = "complex pairs need general storage and an even order";
         return ERROR_HIPMF_INVALID_MATRIX;
     }
     so.pair_blocks = opt.complex_pairs;
-    // fewer, fatter fronts: nested-dissection leaves of <= 16 vertices become single dense supernodes
-    // (1000^2 Poisson: 503 796 -> 113 068 fronts, 29 -> 20 levels, nnz(L) +18 %); see DESIGN.md section 4
-    so.nd_leaf = 16;
-    so.dense_leaves = true;
-    if (const char *e = getenv("HIPMF_ND_LEAF")) { // tuning knob: leaf size (1..64); 0 = classic minimum-degree leaves of 64
-        int v = atoi(e);
-        so.dense_leaves = v > 0;
-        so.nd_leaf = v > 0 ? std::min(v, 64) : 64;
-    }
-    solve_lanes_auto = true;
+    so.nd_leaf = nd_leaf, so.dense_leaves = dense_leaves;
+    so.split_pivots = split_pivots, so.dense_row_factor = dense_row_factor;
+    so.nd_threads = nd_threads, so.parallel_min_n = par_min, so.parallel_chunk_min = par_chunk;
+    for (int k = 0; k < 3; k++) so.relax_ncol[k] = relax_ncol[k], so.relax_zeros[k] = relax_zeros[k];
+    so.relax_big_front = relax_big_front;
+    so.arena_reuse = arena_reuse, so.align_panels = align_panels;
     // (HIPMF_SOLVE_LANES: read and ignored since round 5 -- two lanes are two dependency-driven launches resident together, the very thing
     //  the device gate of solve() rules out; one lane has been as fast since round 4, profiles/r04_solve_lanes.txt)
     solve_lanes = 1, solve_lanes_auto = false;
-    if (const char *e = getenv("HIPMF_SMALL_WIDE")) small_wide_max = atoi(e);
-    if (const char *e = getenv("HIPMF_SMALL_SPLIT")) small_split = atoi(e);
-    if (const char *e = getenv("HIPMF_UPD_G4")) upd_g4 = std::max(65, atoi(e));
-    if (const char *e = getenv("HIPMF_UPD_G8")) upd_g8 = std::max(upd_g4, atoi(e));
-    if (const char *e = getenv("HIPMF_UPD_G16")) upd_g16 = std::max(upd_g8, atoi(e));
-    if (const char *e = getenv("HIPMF_SPLIT_PIVOTS")) so.split_pivots = std::max(0, atoi(e)); // tuning knob: chain links of the big supernodes
-    if (const char *e = getenv("HIPMF_DENSE_ROWS")) so.dense_row_factor = atof(e); // degree threshold factor of the hub vertices (0: off)
-    if (const char *e = getenv("HIPMF_ND_THREADS")) so.nd_threads = std::max(1, atoi(e)); // host threads of the ordering (same result for any count)
-    if (const char *e = getenv("HIPMF_PAR_MIN")) so.parallel_min_n = std::max(0, atoi(e)); // (tests: the threaded pieces of the analysis on small matrices)
-    if (const char *e = getenv("HIPMF_RELAX")) { // "n0,n1,n2,z0,z1,z2": relaxed amalgamation (columns of the merged supernode, share of explicit zeros it may hold)
-        int a, b, c;
-        double x, y, z;
-        if (sscanf(e, "%d,%d,%d,%lf,%lf,%lf", &a, &b, &c, &x, &y, &z) == 6)
-            so.relax_ncol[0] = a, so.relax_ncol[1] = b, so.relax_ncol[2] = c, so.relax_zeros[0] = x, so.relax_zeros[1] = y, so.relax_zeros[2] = z;
-    }
-    if (const char *e = getenv("HIPMF_RELAX_BIG")) so.relax_big_front = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_PAR_CHUNK")) so.parallel_chunk_min = std::max(1, atoi(e)); // (tests: several subtrees per thread on small matrices)
-    if (const char *e = getenv("HIPMF_FUSED_SOLVE")) use_fused = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_OVERLAP_SMALL")) overlap_small = atoi(e) != 0;
-    small_pair = false;
-    if (const char *e = getenv("HIPMF_SMALL_PAIR")) small_pair = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_TREE_SOLVE")) use_tree = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_TAG_SOLVE")) use_tag = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_LEAF_KERNELS")) leaf_kernels = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_SPLIT_TASKS")) split_tasks = std::max(0, atoi(e));
-    split_minlen_env = false;
-    if (const char *e = getenv("HIPMF_SPLIT_MINLEN")) split_minlen = std::max(64, atoi(e)), split_minlen_env = true; // (small values: tests)
-    if (const char *e = getenv("HIPMF_BLOCK_GROUPS_BYTES")) block_groups_max_bytes = atof(e);
-    if (const char *e = getenv("HIPMF_PLAIN_BAND")) plain_band = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_REARM_TAGS")) rearm_tags = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_KRYLOV")) krylov_enabled = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_KRYLOV_RESTART")) krylov_restart = std::max(4, atoi(e));
-    if (const char *e = getenv("HIPMF_KRYLOV_TOL")) krylov_tol = atof(e);
-    if (const char *e = getenv("HIPMF_KRYLOV_OMEGA")) krylov_omega_ok = atof(e);
-    if (const char *e = getenv("HIPMF_WAVE_FRONTS")) wave_fronts = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_WAVE_FRONTS_BWD")) wave_fronts_bwd = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_HOST_DIRECT")) host_direct = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MID_BWD_LEN4")) mid_bwd_len4 = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_MID_BWD_LEN5")) mid_bwd_len5 = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_WT_FRONTS")) wt_max_fronts = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_WT_KB")) wt_max_kb = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_UP_STAGE")) up_stage = std::max(0, std::min(64, atoi(e) / 8 * 8));
-    if (const char *e = getenv("HIPMF_UP_STAGE_BWD")) up_stage_bwd = std::max(8, std::min(64, atoi(e) / 8 * 8));
-    if (const char *e = getenv("HIPMF_UP_TOP_FRONTS")) up_top_fronts = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_UP_REPLICAS")) use_rep = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_UP_PAIR_XCD")) up_pair_xcd = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_UP_MAX_GROUPS")) up_max_groups = std::max(2, std::min(32, atoi(e)));
-    blocked_slabs_env = false;
-    if (const char *e = getenv("HIPMF_BLOCKED_SLABS")) blocked_slabs = atoi(e) != 0, blocked_slabs_env = true;
-    if (const char *e = getenv("HIPMF_UP_STAGE_MID")) up_stage_mid = std::max(0, std::min(32, atoi(e) / 8 * 8));
-    if (const char *e = getenv("HIPMF_SF_BIG_ROWS")) sf_big_rows = std::max(0, std::min(7, atoi(e))); // log2 of the forward slab rows of the largest fronts (0: by dot length only)
-    if (const char *e = getenv("HIPMF_SF_BIG_FRONT")) sf_big_front = std::max(65, atoi(e));
-    if (const char *e = getenv("HIPMF_SF_ASM_FRONT")) sf_asm_front = atoi(e); // forward solve: fronts with at least this many rows assemble their vector once (0: never)
-    if (const char *e = getenv("HIPMF_FACTOR_CHAIN")) use_chain = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_CHAIN_FINE")) chain_fine = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_CHAIN_MAX_WGS")) chain_max_update = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_CHAIN_MIN_WGS")) chain_min_update = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_CHAIN_MAX_STEPS")) chain_max_steps = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_UPD32_MAXF")) upd32_max_front = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_FACTOR_GRAPH")) use_graph = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_UPD_SPLIT")) upd_split_min = std::max(0, atoi(e));
-    if (const char *e = getenv("HIPMF_BLOCK_INV")) use_binv = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_EA_LDS")) use_ea_lds = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_EA_LU")) use_ea_lu = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_UPD_XCD")) upd_xcd = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_UPD_LA_FIRST")) upd_la_first = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MID_LU_SPLIT")) mid_lu_split = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MID_FRONT")) use_mid = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MID_MMAX")) mid_mmax = std::max(0, std::min(MID_MMAX, atoi(e)));
-    if (const char *e = getenv("HIPMF_MID_LU")) use_mid_lu = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MID_LU_MMAX")) mid_lu_mmax = std::max(1, atoi(e));
-    if (const char *e = getenv("HIPMF_DIAG0_MIN")) diag0_min_panels = atoi(e); // tuning knob: panel workgroups of a level's step 0 from which k_diag0 runs
-    if (const char *e = getenv("HIPMF_SOLVE_SLAB64")) slab64 = atoi(e) != 0;
-    if (const char *e = getenv("HIPMF_MATCHING")) opt.matching = atoi(e);
+    if (given(&Tunables::matching)) opt.matching = matching;
     if (opt.complex_pairs) {
         // the pivot searches of k_front (opt-in), of the chained launch and of the block-inverse step do not pair
         use_chain = false, use_binv = false, mid_mmax = 0;
@@ -462,10 +386,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
         const bool two = !S.amap2.empty();
         int npiece = 1;
         {
-            int thr = (int)std::min<unsigned>(4u, std::max(1u, std::thread::hardware_concurrency()));
-            if (const char *e = getenv("HIPMF_ND_THREADS")) thr = std::max(1, std::min(4, atoi(e)));
-            int64_t par_min = 200000;
-            if (const char *e = getenv("HIPMF_PAR_MIN")) par_min = std::max(0, atoi(e));
+            const int thr = given(&Tunables::nd_threads) ? std::min(4, nd_threads) : (int)std::min<unsigned>(4u, std::max(1u, std::thread::hardware_concurrency()));
             if (nnz_a >= par_min && nnz_a >= 64) npiece = thr;
         }
         const int passes = two ? 2 : 1, P = npiece * passes;
@@ -710,7 +631,7 @@ int32_t Solver::initialize_impl(int32_t n, const int32_t *rp, const int32_t *ci,
             // (joined below: the lists were computed beside upload_plan)
             if (asm_thread.joinable()) asm_thread.join();
             if (opt.verbose) fprintf(stderr, "hipmf: initialize: the assembly-list thread worked %.3f s beside the launch plans\n", AL.seconds);
-            if (getenv("HIPMF_PLAN_DIGEST")) { // (the thread's lists join the digest of the plans: thread-count independence test)
+            if (want_digest) { // (the thread's lists join the digest of the plans: thread-count independence test)
                 uint64_t h = (uint64_t)plan_digest ^ 1469598103934665603ull;
                 auto eat = [&](const void *p, size_t bytes) {
                     const unsigned char *b = (const unsigned char *)p;
@@ -820,17 +741,17 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
     // right-hand side; config 4's 84 GB with its 32-column shard: 398 -> 381 ms) but still gain: no size limit by default; the block
     // buffers never take more than half of the free device memory (solve()).  HIPMF_BLOCK_GROUPS=1..4 overrides.
     block_groups_plan = 8.0 * (double)S.persist_doubles <= block_groups_max_bytes ? SF_GMAX : 1;
-    if (const char *e = getenv("HIPMF_BLOCK_GROUPS")) block_groups_plan = std::max(1, std::min((int)SF_GMAX, atoi(e)));
+    if (given(&Tunables::block_groups_ask)) block_groups_plan = block_groups_ask;
     // (the split dot products of the blocked backward slabs were tuned with ONE block per launch; several groups per launch fill the levels
     //  of few slabs by themselves, and every split costs a scratch round trip: with four groups, fronts from 8 192 rows on instead of 2 048 --
     //  config 4's shard 0.318 -> 0.303 s, 144^3 2.97 -> 2.91, 100^3 0.80 -> 0.78 ms per right-hand side, profiles/r06_block_groups.txt)
-    if (!split_minlen_env) split_minlen = 2048 * block_groups_plan;
+    if (!given(&Tunables::split_minlen)) split_minlen = 2048 * block_groups_plan;
     // Wider slabs for the blocked instances (64 rows, 128 forward for long dot products: every slab stages the whole vector block of its
     // front, so wide slabs re-read it less often) lost with one block per launch (round 3: 144^3 4.92 -> 7.06 ms per right-hand side) and
     // win on the LARGE 3D factors once several groups share a launch -- config 4's shard 0.304 -> 0.290 s, 144^3 2.91 -> 2.79 ms per
     // right-hand side -- while the smaller ones lose (100^3 0.788 -> 0.822, the 1M-DOF 2D factor 0.217 -> 0.284): on from a largest front
     // of 16 384 rows (144^3: 20 736, 100^3: 10 000); HIPMF_BLOCKED_SLABS=0 / 1 overrides.  (profiles/r06_block_groups.txt)
-    if (!blocked_slabs_env) blocked_slabs = block_groups_plan > 1 && S.max_front >= 16384;
+    if (!given(&Tunables::blocked_slabs)) blocked_slabs = block_groups_plan > 1 && S.max_front >= 16384;
     auto pl_t = std::chrono::steady_clock::now();
     std::string pl_log;
     auto pl_lap = [&](const char *what) { // (verbose: where the plan + upload time of initialize goes)
@@ -945,6 +866,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
     // four to a workgroup (one per wavefront), big fronts one workgroup per slab of 2^kind rows
     int32_t sp_code = SUCCESSFUL_EXIT;
     auto solve_plans = [&]() -> int32_t {
+        const bool tracing = given(&Tunables::sf_trace); // (HIPMF_SF_TRACE: the task lists stay on the host for the dump of solve())
         std::vector<SfTask> sf;
         std::vector<int32_t> need((size_t)2 * ns, 1);
         // rows per slab by the length of the dot products (forward: p columns, backward: f columns): long ones get
@@ -1102,7 +1024,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             band++;
         }
         int32_t fwd_limit = S.nlevels; // profiling knob: run the forward pass up to this level only (the result is then meaningless)
-        if (const char *e = getenv("HIPMF_SF_FWD_LEVELS")) fwd_limit = std::max(1, std::min(S.nlevels, atoi(e)));
+        if (given(&Tunables::sf_fwd_levels)) fwd_limit = std::max(1, std::min(S.nlevels, sf_fwd_levels));
         sf_fwd_launch = 0;
         sf_fwd_band = 0;
         for (int32_t l = 0; l < S.nlevels; l++) {
@@ -1181,14 +1103,14 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
                 HIPC(hipMemset(d_split_cnt, 0, sizeof(int32_t) * (size_t)split_units * (size_t)block_groups_plan), ERROR_HIP_MALLOC);
             }
             sfk_host.clear();
-            if (getenv("HIPMF_SF_TRACE"))
+            if (tracing)
                 for (const SfTask &t : sf) sfk_host.push_back(t.kind), sfk_host.push_back(t.a);
             HIPC(d_sfk.upload(sf), ERROR_HIP_MALLOC);
             HIPC(d_needk.upload(need), ERROR_HIP_MALLOC);
             sf.swap(keep);
             need.swap(need_keep);
         }
-        if (getenv("HIPMF_SF_TRACE")) { // profiling aid: four device-clock stamps per task of the upper (mixed) launches
+        if (tracing) { // profiling aid: four device-clock stamps per task of the upper (mixed) launches
             const size_t ntr = (size_t)(sf_fwd_cnt - sf_fwd_band) + (size_t)sf_bwd_top;
             HIPC(d_trace.alloc(8 * std::max<size_t>(ntr, 1)), ERROR_HIP_MALLOC);
             HIPC(hipMemset(d_trace, 0, sizeof(unsigned long long) * 8 * std::max<size_t>(ntr, 1)), ERROR_HIP_MALLOC);
@@ -1379,7 +1301,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
         tag_active = tree_active && tag_plan;
         // (the backward slabs below the top levels: with the tagged hand-offs the small parked share of E' no longer pays -- 217 against
         //  221 us per backward pass at 1000 x 1000, profiles/r05_solve_variants_c2.txt; an explicit HIPMF_UP_STAGE_MID is kept)
-        if (tag_active && !getenv("HIPMF_UP_STAGE_MID")) up_stage_mid = 0;
+        if (tag_active && !given(&Tunables::up_stage_mid)) up_stage_mid = 0;
         if (tree_active && up_stage > 0) {
             HIPMF_ALLOW_LDS((k_fwd_fused<false, 1, true>), sizeof(double) * 256 * (size_t)up_stage);
             HIPMF_ALLOW_LDS((k_bwd_fused<false, 1, false, true>), sizeof(double) * 256 * (size_t)up_stage_bwd);
@@ -1392,7 +1314,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
         HIPC(hipMemset(d_sync, 0, sizeof(int32_t) * SF_GMAX * (2 * (size_t)(SF_SYNC_HEADER + ns) + 1)), ERROR_HIP_MALLOC);
         return SUCCESSFUL_EXIT;
     };
-    const bool sp_async = !(getenv("HIPMF_PLAN_THREAD") && atoi(getenv("HIPMF_PLAN_THREAD")) == 0); // (0: in line, for timing comparisons)
+    const bool sp_async = plan_thread; // (HIPMF_PLAN_THREAD=0: in line, for timing comparisons)
     if (!sp_async) sp_code = solve_plans();
     std::thread sp_thread([&]() {
         if (!sp_async) return;
@@ -1499,7 +1421,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
         {
             int32_t fmax_big = 0;
             for (int32_t a : big) fmax_big = std::max(fmax_big, S.fsize(a));
-            const bool forced = getenv("HIPMF_UPD32_MAXF") != nullptr; // (an explicit setting also applies to the symmetric fronts)
+            const bool forced = given(&Tunables::upd32_max_front); // (an explicit setting also applies to the symmetric fronts)
             L.upd_ts = (!big.empty() && fmax_big <= upd32_max_front && (!S.sym_mode || forced)) ? UPD_T_SMALL : UPD_T;
         }
         const int64_t UT = L.upd_ts;
@@ -1788,11 +1710,8 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
             const int64_t f = S.fsize(P.s);
             tiles_bound += f <= 64 ? 1 : ((f + 31) / 32) * ((f + 63) / 64);
         }
-        int ea_threads = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-        if (const char *e = getenv("HIPMF_ND_THREADS")) ea_threads = std::max(1, atoi(e));
-        int64_t ea_par_min = 200000; // (below: not worth the thread start-up)
-        if (const char *e = getenv("HIPMF_PAR_MIN")) ea_par_min = std::max(0, atoi(e));
-        if (tiles_bound < ea_par_min) ea_threads = 1;
+        int ea_threads = given(&Tunables::nd_threads) ? nd_threads : (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+        if (tiles_bound < par_min) ea_threads = 1; // (not worth the thread start-up)
         ea_pass(false, ea_threads);
         if (ea_oom.load()) return ERROR_MALLOC;
         // layout: level by level, a level's first tiles (nhead) in front of its other tasks, both in the order of the level's fronts
@@ -1819,7 +1738,7 @@ int32_t Solver::upload_plan(const std::function<int32_t()> &tail) {
         if (ea_oom.load()) return ERROR_MALLOC;
     }
     plan_digest = 0;
-    if (getenv("HIPMF_PLAN_DIGEST")) {
+    if (want_digest) {
         // (diagnostic / tests: one number over what the threaded pieces of initialize produce -- row structures, relative indices, pool
         //  layout, extend-add task lists -- to compare thread counts and builds; a pass over gigabytes at 200^3, hence opt-in)
         uint64_t h = 1469598103934665603ull;
@@ -2022,8 +1941,7 @@ struct DeviceGate {
     void open_shared(int device) {
         state = -1;
 #ifndef HIPMF_EMULATED
-        if (const char *e = getenv("HIPMF_PROCESS_GATE"))
-            if (atoi(e) == 0) return;
+        if (!Tunables::now(&Tunables::process_gate)) return;
         constexpr uint32_t MAGIC = 0x48504d47u; // "HPMG"
         char bus[64] = {0};
         if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, device) != hipSuccess) return;
@@ -3048,10 +2966,7 @@ int32_t Solver::solve_core(double *x, const double *rhs, int32_t nrhs, int64_t l
             if (need_b(1) > 0.9 * (double)free_b) KB = SF_KMID, GB = 1;
         }
     }
-    if (const char *e = getenv("HIPMF_BLOCK_COLS")) {
-        const int v = atoi(e);
-        if (KB > 1 && block_cols == 0 && (v == SF_KMID || v == SF_KMAX)) KB = v;
-    }
+    if (const int v = Tunables::now(&Tunables::block_cols_ask); KB > 1 && block_cols == 0 && (v == SF_KMID || v == SF_KMAX)) KB = v;
     if (KB != SF_KMAX) GB = 1;
     if (KB > 1) block_cols = KB, block_groups = GB, block_groups_last = GB;
     const int32_t KS = KB * GB; // columns of a block of the driver below
@@ -3285,7 +3200,7 @@ int32_t Solver::solve_core(double *x, const double *rhs, int32_t nrhs, int64_t l
         const size_t nb = tr_tree ? (size_t)sf2_bwd_cnt : (size_t)(tr_k ? sfk_bwd_top : sf_bwd_top);
         std::vector<unsigned long long> tr(8 * (nf + nb));
         (void)hipMemcpy(tr.data(), d_trace, sizeof(unsigned long long) * tr.size(), hipMemcpyDeviceToHost);
-        if (FILE *fp = fopen(getenv("HIPMF_SF_TRACE"), "w")) {
+        if (FILE *fp = fopen(sf_trace.c_str(), "w")) {
             for (size_t k = 0; k < nf + nb; k++) {
                 const size_t ti = tr_tree ? k : (k < nf ? (size_t)band0 + k : (size_t)fwd_all + (k - nf));
                 if (2 * ti + 1 >= host.size()) break;
@@ -3361,13 +3276,12 @@ namespace {
 // whether the phases of a step are timed (HIPMF_UPDATED_TIMING=1)
 struct UpdatedParams {
     double tol;
-    int32_t restart = 30, step_limit;
+    int32_t restart, step_limit;
     bool timing;
     UpdatedParams(double rel_tol, int32_t max_steps) : tol(rel_tol > 0.0 ? rel_tol : 1e-12) {
-        const char *const r = getenv("HIPMF_UPDATED_RESTART"), *const t = getenv("HIPMF_UPDATED_TIMING");
-        if (r && atoi(r) >= 4 && atoi(r) <= 200) restart = atoi(r);
+        restart = Tunables::now(&Tunables::updated_restart);
         step_limit = max_steps > 0 ? max_steps : 4 * restart;
-        timing = t && atoi(t) != 0;
+        timing = Tunables::now(&Tunables::updated_timing);
     }
 };
 
@@ -4242,8 +4156,7 @@ int32_t Solver::solve_extra_precise_core(double *x, double *tail, const double *
     const double tol = dx_tol > 0.0 ? dx_tol : EPS;
     const int32_t limit = max_steps > 0 ? max_steps : 10;
     const double bound_floor = tail ? 0.0 : std::max(10.0, sqrt((double)items)) * EPS; // (x alone cannot be nearer than its own rounding)
-    const char *const te = getenv("HIPMF_EXTRA_TIMING");
-    const StepTimer timer{xr_ev, STREAM, te && atoi(te) != 0};
+    const StepTimer timer{xr_ev, STREAM, Tunables::now(&Tunables::extra_timing)};
     extra_steps = extra_blocks = 0;
     extra_ms[0] = extra_ms[1] = extra_ms[2] = 0.0;
     if (info)
@@ -5071,8 +4984,7 @@ int32_t Solver::solve_transpose_many(double *x, const double *rhs, int32_t nrhs,
     {
         const int32_t code = tr_prepare();
         if (code != SUCCESSFUL_EXIT) return code;
-        const char *e = getenv("HIPMF_TRANSPOSE_BLOCKED");
-        if ((e && e[0] == '0') || tr_prepare_blocked() != SUCCESSFUL_EXIT) return solve_transpose(x, rhs, nrhs, ldx, on_device, conj_pairs);
+        if (!Tunables::now(&Tunables::transpose_blocked) || tr_prepare_blocked() != SUCCESSFUL_EXIT) return solve_transpose(x, rhs, nrhs, ldx, on_device, conj_pairs);
     }
     const int32_t n = S.n, nstep = opt.refinement_nstep;
     const size_t nb = sizeof(double) * (size_t)n, nz = (size_t)n;
@@ -5364,9 +5276,7 @@ int32_t Solver::solve_sparse(double *x_sel, int64_t ldx, int32_t nrhs, const int
         }
         ostr = nout;
     }
-    double theta = 0.25, min_bytes_1col = 2e9; // (defaults from the measurement of profiles/r09_sparse_rhs.txt)
-    if (const char *e = getenv("HIPMF_PRUNE_MAX_SHARE")) theta = atof(e);
-    if (const char *e = getenv("HIPMF_PRUNE_MIN_BYTES")) min_bytes_1col = atof(e);
+    const double theta = Tunables::now(&Tunables::prune_max_share), min_bytes_1col = Tunables::now(&Tunables::prune_min_bytes);
     const bool never_pruned = n_perturbed > 0;
     const std::vector<int32_t> &pos_in = tr ? sp_ipos_c : sp_ipos_r, &pos_out = tr ? sp_ipos_r : sp_ipos_c; // where b enters, where x leaves
     const int32_t *const d_ipr = d_sp_ipos_r, *const d_ipc = d_sp_ipos_c;
@@ -5682,6 +5592,9 @@ int32_t Solver::download_pattern(std::vector<int32_t> &rp, std::vector<int32_t> 
 }
 
 } // namespace hipmf
+
+// debug hook (tests, docs): "NAME=value when status\n" for every row of the knob table as the environment reads NOW; returns the bytes needed
+extern "C" int64_t hipmf_debug_knobs(char *buf, int64_t cap) { return hipmf::Tunables::from_env().dump(buf, cap); }
 
 #ifdef HIPMF_STAMPS
 extern "C" int32_t hipmf_debug_read_stamps(unsigned long long *out, int64_t n) {

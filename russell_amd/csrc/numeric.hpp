@@ -8,6 +8,7 @@
 
 #include "device_owner.hpp"
 #include "symbolic.hpp"
+#include "tunables.hpp"
 
 namespace hipmf {
 
@@ -332,9 +333,13 @@ struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtra
     StreamOwner stream4; // ... and the bulk of a split trailing update (HIPMF_UPD_SPLIT)
 };
 
-class Solver : public SolverDevice {
+// The Tunables base is the EFFECTIVE set of knobs of the current analysis: initialize_impl() starts it from `requested` and adjusts it for
+// the matrix (complex pairs, plan-dependent defaults); the run-time fallbacks (a hand-off time-out, a failed graph capture) write it
+// alone, so they last for ONE analysis.  Like SolverDevice, assigning a fresh instance resets everything.
+class Solver : public SolverDevice, public Tunables {
   public:
     Solver();
+    Tunables requested; // what the environment asked for at the last initialize() call: assigned there and nowhere else
     ~Solver();
     int32_t initialize(int32_t n, const int32_t *rp, const int32_t *ci, bool sym_lower, const SymbolicOptions &sopt,
                        const NumericOptions &nopt, const double *values = nullptr);
@@ -455,13 +460,9 @@ class Solver : public SolverDevice {
     int32_t refinement_steps_done_t = 0;
     int32_t singular_verdict();      // exactly zero pivots were met: singular (status 1), or only an unlucky static order (0)?  One probe solve decides
     int64_t zero_pivots_absorbed = 0; // exactly zero pivots of factorisations that the probe solve found NOT singular (summed)
-    bool krylov_enabled = true;      // HIPMF_KRYLOV=0: no rescue (the refined solution is returned as it is)
     bool in_rescue = false;
-    int32_t krylov_restart = 40;     // directions per cycle (HIPMF_KRYLOV_RESTART)
     int32_t krylov_cycles = 4;       // restarts at most
-    double krylov_omega_ok = 1e-13;  // a column whose refined solution has a componentwise backward error up to this is not looked at by the rescue (HIPMF_KRYLOV_OMEGA)
     std::vector<double> col_omega;   // per column of the last solve: omega of its final solution as the refinement measured it
-    double krylov_tol = 1e-13;       // |b - A x|_2 <= tol |b|_2 ends the rescue (and is what triggers it)
     int64_t krylov_iterations = 0;   // FGMRES steps of the last solve (0: no rescue ran or was needed)
     double krylov_last_relres = 0.0; // |b - A x|_2 / |b|_2 after the last rescue
     int32_t prepare_many(int32_t nrhs); // the block buffers of a later many-RHS solve, ahead of time
@@ -512,10 +513,6 @@ class Solver : public SolverDevice {
     int64_t persist_bytes() const { return S.persist_doubles * 8; }
     double last_residual_inf = 0.0, last_omega = 0.0;
     int device = 0;
-    // the launches of a factorisation's levels, captured once and replayed (HIPMF_FACTOR_GRAPH=0: eager launches)
-    bool use_graph = false; // (measured: no gain at 1000 x 1000 -- the gaps at the level boundaries are the cross-stream edges themselves, not host latency)
-    bool use_binv = false;            // HIPMF_BLOCK_INV=1: LU fronts of the tiled path take ONE launch per step (kernels_factor_binv.hpp) instead of k_panel + k_update; measured slower (profiles/r04_rejected_experiments.txt)
-    int32_t upd_split_min = 0;        // HIPMF_UPD_SPLIT=n: full steps (two-launch form) with at least n update workgroups are split (0: never; measured: no gain)
     std::string last_error;
     std::mutex err_mutex; // (the planning thread of initialize and the calling thread both report through last_error)
 
@@ -539,25 +536,8 @@ class Solver : public SolverDevice {
     int32_t run_triangular(double *xp, int32_t nk, double *wrk, int64_t xstr, int64_t wstr, void *lane_stream, int32_t *lane_sync, bool timed, int32_t lane_id, uint32_t gmask = 0xffffffffu);
     void harvest_tri();
     int32_t build_level_tasks();
-    // optional task list of the blocked (many-RHS) instances with wider slabs (HIPMF_BLOCKED_SLABS=1).  Measured and NOT the default:
-    // 64 / 128-row slabs re-read the vector block of a front less often, but lose more in parallelism -- 144^3, 64 right-hand sides:
-    // 4.92 -> 7.06 ms per right-hand side; 200^3, 256 right-hand sides: 4.58 -> 6.86 s (profiles/r03_rejected_experiments.txt)
-    bool blocked_slabs = false;
-    bool blocked_slabs_env = false; // HIPMF_BLOCKED_SLABS was given (else: on for factors whose largest front has >= 16 384 rows when several groups share a launch)
-    // round 5: the leaves of the tree leave the task lists of the blocked (many-RHS) solves: one wavefront carries sixteen columns through
-    // LEAF_PER_WAVE leaves (kernels_solve_leaf.hpp).  HIPMF_LEAF_KERNELS=0: every small front stays a task.
-    bool leaf_kernels = true;
-    // blocked instances, backward pass, levels of few slabs with long dot products (the top of a 3D factor): a slab's dot products are
-    // split over Q consecutive tasks (k_bwd_fused); forward, the largest fronts of such levels get narrower slabs.  A level qualifies
-    // below split_tasks slabs (HIPMF_SPLIT_TASKS, 0: never), a front from split_minlen rows on (HIPMF_SPLIT_MINLEN).
-    int32_t split_tasks = 512, split_minlen = 2048; // (split_minlen: 2 048 x the planned block groups unless HIPMF_SPLIT_MINLEN says otherwise)
-    bool split_minlen_env = false;
     int32_t sfk_fwd_cnt = 0, sfk_bwd_cnt = 0, sfk_fwd_band = 0, sfk_bwd_top = 0;
-    bool rearm_tags = false;                   // HIPMF_REARM_TAGS=1: k_wt_bwd re-arms the tagged words for the next pass pair instead of a memset before every pass pair
-                                               // (built and measured in round 6: same bits, NOT faster -- pass pair 0.4037 - 0.4076 against 0.4012 - 0.4058 ms, solve
-                                               // 0.94 - 0.95 against 0.91 ms, profiles/r06_rejected_experiments.txt; default off)
     bool tags_armed = false;                   // the tagged words of d_work hold the tag pattern (left by the last pass pair's k_wt_bwd)
-    bool plain_band = true;                    // HIPMF_PLAIN_BAND=0: the all-small band of the blocked solves stays ONE dependency-driven launch per direction
     std::vector<int32_t> sfk_band_f, sfk_band_b; // task offsets of the band's levels in d_sfk (forward: levels ascending from task 0; backward: relative to
                                                // the first backward task, the band's levels descending) -- one PLAIN launch per level (round 6)
     std::vector<int32_t> sf3_lvl, sf3_lvl_b; // task offsets per level: forward (leaves first), backward (root first)
@@ -569,69 +549,20 @@ class Solver : public SolverDevice {
     int32_t sf_fwd_cnt = 0, sf_bwd_cnt = 0; // forward tasks first, then the backward tasks
     int32_t sf_fwd_band = 0, sf_bwd_top = 0; // tasks of the all-small bottom band (forward: first; backward: after sf_bwd_top)
     int32_t sf_fwd_launch = 0;              // == sf_fwd_cnt unless the profiling knob HIPMF_SF_FWD_LEVELS cuts the pass short
-    // bottom of the tree: one wavefront per subtree of small fronts (kernels_solve_tree.hpp); the tasks of everything above it
-    // (single right-hand side; the blocked many-RHS instances keep the task lists above)
-    bool use_tree = true;                   // HIPMF_TREE_SOLVE=0: the round-2 schedule (all-small band + upper band)
-    int32_t wt_max_fronts = 24;             // HIPMF_WT_FRONTS: fronts per wave-subtree at most
-    int32_t wt_max_kb = 64;                 // HIPMF_WT_KB: panel kilobytes per wave-subtree at most
-    int32_t up_stage = 32;                  // HIPMF_UP_STAGE: entries of E per thread of a TOP-level forward slab parked in LDS before the wait (multiple of 8; 0: no top launch)
-    int32_t up_stage_bwd = 48;              // HIPMF_UP_STAGE_BWD: the same for E' in the backward pass (the dot products run over f, not p)
-    int32_t up_stage_mid = 8;               // HIPMF_UP_STAGE_MID: the same for the backward slabs BELOW the top levels (0: none)
-    int32_t up_top_fronts = 40;             // HIPMF_UP_TOP_FRONTS: the top levels are those above which no level has more tiled fronts
     int32_t wt_hdr_fwd = 0, wt_hdr_bwd = 0; // batches of the forward / backward part
     int64_t wt_meta_fwd = 0;                // words of the forward part of d_wt_meta
     int32_t sf2_fwd_mid = 0, sf2_bwd_top = 0; // forward: tasks below the top levels come first; backward: the top levels' tasks come first
-    bool up_pair_xcd = true;                // HIPMF_UP_PAIR_XCD=0: the 8-row slabs of a top-level front in row order (1: neighbours eight tasks apart = same XCD)
-    int32_t up_max_groups = 32;             // HIPMF_UP_MAX_GROUPS: column groups of a top-level slab at most (32: 8-row slabs; 16: 16-row slabs = whole 128-byte lines)
-    bool use_rep = true;                    // HIPMF_UP_REPLICAS=0: every waiter polls the front's counter
     bool tree_active = false;               // the plan above exists for this matrix
-    bool use_tag = true;                    // HIPMF_TAG_SOLVE=0: completion counters instead of data-tagged hand-offs above the wave-subtrees
-    bool wave_fronts = true;                // HIPMF_WAVE_FRONTS=0: the big fronts of few rows / pivots right above the wave-subtrees stay 256-thread slab tasks in the forward pass
-    int32_t mid_bwd_len4 = 256, mid_bwd_len5 = 64; // backward slabs below the top levels, tagged hand-offs: 16 / 32 rows from these dot lengths on (HIPMF_MID_BWD_LEN4 / _LEN5)
-    // host-pointer solves: buffers seen in the previous call are copied without the pinned staging buffer (HIPMF_HOST_DIRECT=0: always staged)
-    bool host_direct = true;
     const double *last_host_rhs = nullptr;
     double *last_host_x = nullptr;
-    bool wave_fronts_bwd = true; // ... and of the backward pass (HIPMF_WAVE_FRONTS_BWD=0: slab tasks there)
     bool tag_active = false;                // the launches above the wave-subtrees run their TAG instances (kernels_solve_fused.hpp, sf_tag_wait)
     int64_t work_arm0 = 0;                  // ... of which the first work_arm0 doubles (the roots of the wave-subtrees) are not armed: k_wt_fwd writes them in a launch of its own
     int64_t work_up = 0;                    // doubles at the head of a solve workspace: the vectors of the fronts outside the wave-subtrees' interiors
                                             // (tag_active: followed by n doubles, the tagged shadow of x)
-    bool overlap_small = true;              // HIPMF_OVERLAP_SMALL=0: everything on one stream
-    bool small_pair = false;                // HIPMF_SMALL_PAIR=1: the two k_small_factor launches of an all-small level side by side (third stream)
-    int32_t sf_big_rows = 6, sf_big_front = 2048; // forward solve: fronts with at least sf_big_front rows use slabs of 2^sf_big_rows rows
-    int32_t sf_asm_front = 2048;                  // forward solve: fronts with at least this many rows assemble their vector once, in tasks of their own (0: never; then sf_big_rows applies)
-    // levels with few tiled steps (the middle of the tree): all steps of a level in one launch with in-launch hand-offs (kernels_factor_chain.hpp)
-    bool use_chain = false;                 // HIPMF_FACTOR_CHAIN=1 switches it on.  Off by default: measured at the end of round 3 it is neutral for LU at
-                                            // 1000 x 1000 (7.35 -> 7.34 ms), -1.6 % for L D L^T there and +1 ... +3 % on smaller problems (profiles/r03_chain_check.txt)
-    bool chain_fine = false;                // HIPMF_CHAIN_FINE=1: a panel waits only for the critical pieces of the update before (measured: no gain)
-    int32_t chain_max_steps = 8;            // a level is chained when it has at most this many steps (HIPMF_CHAIN_MAX_STEPS) ...
-    int32_t chain_max_update = 16384;       // ... no step of it has more update workgroups than this (HIPMF_CHAIN_MAX_WGS: wide steps are bound by throughput, and
-                                            //     the 8-byte agent-scope accesses of the chained form cost more per byte) ...
-    int32_t chain_min_update = 0;           // ... and its widest step has at least this many (HIPMF_CHAIN_MIN_WGS)
-    int32_t upd32_max_front = 256;          // LU: levels whose largest tiled front has at most this many rows update with 32 x 32 tiles, one wave per tile
-                                            // (HIPMF_UPD32_MAXF; 0: never).  Bit-identical to the 64 x 64 instance; 1000 x 1000: 7.30 -> 7.23 ms.  The L D L^T
-                                            // fronts keep the 64 x 64 tiles (measured: 6.32 -> 6.35 ms with the small ones)
-    // LU mode: fronts with f > 64, at most 64 pivots and at most mid_mmax off-diagonal rows whose pivot rows + column panel fit the
-    // LDS budget of k_front are factorised by one workgroup each, one launch per level and size class (HIPMF_MID_FRONT=0: off,
-    // HIPMF_MID_MMAX: rows at most, <= 192)
-    bool use_mid = true;
-    int32_t mid_mmax = 0;  // HIPMF_MID_MMAX: k_front (eight wavefronts, up to 64 pivots) takes the fronts with at most this many off-diagonal rows that
-                           // k_front_lu does not take; off by default -- measured 7.13 ms with it (80 rows) against 7.10 without, 7.28 on tiled launches alone
-    bool use_mid_lu = true; // HIPMF_MID_LU=0: fronts with at most 32 pivots take k_front / the tiled path like the others
-    int32_t mid_lu_mmax = 192; // HIPMF_MID_LU_MMAX: off-diagonal rows of a k_front_lu front at most
     bool is_mid_lu(int32_t s) const;
     bool is_mid(int32_t s) const;
-    int32_t diag0_min_panels = 512;         // step 0 of a level: from this many panel workgroups the first diagonal tiles get their own launch (k_diag0)
     bool level_path_ok = true;              // false: some front is too large for the level-set solves' LDS staging
-    bool use_fused = true;                  // false: level-set launches (HIPMF_FUSED_SOLVE=0, or after a hand-off timeout)
-    // Tiled path: fronts with at least upd_g4 (upd_g8, upd_g16) rows apply 4 (8, 16) panels per pass over the trailing matrix instead of 2:
-    // the read-modify-write of the trailing matrix bounds the large fronts (HIPMF_UPD_G4 / HIPMF_UPD_G8 / HIPMF_UPD_G16)
-    int32_t upd_g4 = 2048, upd_g8 = 4096, upd_g16 = 1 << 30;
     int32_t update_group(int32_t f) const { return f >= upd_g16 ? 16 : (f >= upd_g8 ? 8 : (f >= upd_g4 ? 4 : 2)); }
-    int32_t small_wide_max = 7000; // a k_small_factor launch with at most this many fronts uses four wavefronts per front (HIPMF_SMALL_WIDE, 0: never)
-    int32_t small_split = 28; // small fronts up to this size get their own launch per level (HIPMF_SMALL_SPLIT, 0: one launch)
-    bool slab64 = false;                    // HIPMF_SOLVE_SLAB64=1: same slab shape in both solve paths (bitwise comparable)
     int32_t sf_err[2] = {0, 0};
     std::vector<int32_t> h_emap;
     // values (CSR order of the caller, or the inputs of the value map: mapped) -> dst, nnz doubles in the handle's CSR order
@@ -665,15 +596,9 @@ class Solver : public SolverDevice {
     bool solve_lanes_auto = true; // no HIPMF_SOLVE_LANES given: one lane when the factor exceeds 64 GB (solve())
     bool prepare_only = false;     // solve() stops after its buffers exist (prepare_many)
     int32_t block_groups_plan = 1; // ... what initialize planned for (HIPMF_BLOCK_GROUPS, else by the size of the factor): the split-dot-product scratch is sized by it
-    double block_groups_max_bytes = 1e18; // factors up to this many bytes carry SF_GMAX blocks per launch, larger ones one (HIPMF_BLOCK_GROUPS_BYTES; no limit by default: measured to pay up to config 4's 84 GB, profiles/r06_block_groups.txt)
     int64_t work_blk_doubles = 0;  // stride between the columns of a blocked solve workspace: work_doubles without the tagged shadow xt
     std::vector<int32_t> sf_host, sfk_host; // (kind, front) per task (single-column lists / blocked list), kept only when tracing
-    bool mid_lu_split = false;    // HIPMF_MID_LU_SPLIT=1: the k_front_lu fronts of a level in three launches by LDS class (two or four fronts per CU for the smaller ones); measured slower: 6.58 -> 6.95 ms
-    bool upd_la_first = true;     // HIPMF_UPD_LA_FIRST=0: the look-ahead piece of a front is the last workgroup of its range in a trailing-update launch (1: the look-ahead pieces lead the launch)
-    bool upd_xcd = true;          // HIPMF_UPD_XCD=0: the tiles of a full trailing update in plain order (1: whole tile columns per XCD)
-    bool use_ea_lds = true;       // HIPMF_EA_LDS=0: LU working blocks go back to k_zero + k_scatter + k_extend_add (read-modify-write per child) instead of k_extend_add_lds
     bool ea_lds_active() const { return use_ea_lds; }
-    bool use_ea_lu = true;        // HIPMF_EA_LU=0: the first diagonal tiles go back to k_diag0 / the first panel launch
     bool ea_lu_active() const { return ea_lds_active() && use_ea_lu && !use_binv; }
     int32_t spmv_blocks = 0;
     int32_t tr_prepare();

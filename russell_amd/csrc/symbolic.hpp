@@ -61,6 +61,8 @@ struct SymbolicOptions {
     int32_t relax_ncol[3] = {4, 16, 64};
     double relax_zeros[3] = {0.8, 0.1, 0.05};
     int32_t relax_big_front = 2048;
+    bool arena_reuse = true;      // false (debug): every working block of a tiled front keeps its own storage
+    bool align_panels = true;     // the strides of a big front's E (and working block) and -- above 64 pivots -- of its E' are multiples of 16 doubles
 };
 
 struct Symbolic {
