@@ -388,6 +388,59 @@ int32_t solver_hipmf_solve_bordered(struct InterfaceHIPMF *solver, double *x, do
 int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *solver, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs, int32_t ldx,
                                            int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
 
+/* SENSITIVITIES of the solve with respect to the matrix VALUES: tangent (forward) and adjoint (reverse) mode.
+ * For J = J(x) with A x = b:  forward,  dx = A^{-1} (db - dA x);  reverse, with g = dJ/dx:  lambda = A^{-T} g = dJ/db  and
+ *   dJ/da_ij = -lambda_i x_j  on the sparsity pattern, summed over the right-hand sides,
+ * and the two agree: <g, dx> = <grad_values, dvalues> + <lambda, db>.  The transposed solves above give lambda; these calls add the
+ * product restricted to the pattern, delivered IN THE ORDER OF THE CALLER'S VALUES, and the product with values other than the
+ * factorised ones that the tangent needs.  `mapped` chooses that order as for solver_hipmf_solve_updated:
+ *   mapped = 0: the array handed to solver_hipmf_factorize -- the CSR order of initialize; a symmetric-lower handle: its lower triangle,
+ *               ONE entry for the two positions (i, j) and (j, i): its gradient is dJ/da_ij + dJ/da_ji, so that <grad, dvalues> is dJ --
+ *               also when the handle expanded the matrix to general storage inside (HIPMF_COUNTER_SYM_EXPANDED);
+ *   mapped = 1: the nnz_in inputs handed to solver_hipmf_factorize_mapped: input t receives the sum of the gradients of every CSR entry
+ *               whose segment lists t (duplicate triplets all receive the entry's gradient).  ERROR_HIPMF_INVALID_VALUE without a map.
+ * solver_hipmf_values_outer -- the primitive (needs initialize only; no factor is involved, so it combines with
+ * solver_hipmf_solve_updated_transpose as well):
+ *   grad[k] = beta grad[k] + alpha sum_{c < ncols} u[i_k + c ldu] w[j_k + c ldw]     for every value k = (i_k, j_k) of the caller,
+ *   u, w column-major with ldu, ldw >= ndim; beta == 0: grad is not read (it may hold anything, NaN included).
+ *   One lane per stored entry (kernels_sensitivity.hpp); the sum over the columns is ONE chain of fused multiply-adds in ascending c per
+ *   entry (symmetric-lower off-diagonals: u_i w_j + u_j w_i of a column first, then the chain; several slots per input: summed in
+ *   ascending slot order): the result does not depend on the launch geometry or the device, host and _device forms and repeated calls
+ *   give the same bits, and there are no floating-point atomics.  Error per value: at most ncols eps sum_c |u_i w_j| (both products of a
+ *   symmetric entry and every slot of an input counted, plus eps of the sum per extra addition; alpha other than +-1 and beta != 0 add
+ *   one rounding each).
+ * solver_hipmf_solve_tangent: dx = A^{-1} (db - dA x), dA the matrix `dvalues` describe (any values of the handle's structure), db NULL =
+ *   zero; x, db, dx column-major ld x nrhs, ld >= ndim, entries ndim .. ld - 1 of a column of dx are not written; dx may be x or db.
+ *   dvalues pass through the staging of a factorize into the operator's buffer of the solve_updated forms, the right-hand sides are
+ *   formed by their blocked residual kernel, the solve is solver_hipmf_solve_device's, refined and rescued as the handle is set up.
+ * solver_hipmf_solve_adjoint: lambda = A^{-T} g by solver_hipmf_solve_transpose_many's path (its refinement and rescue; L D L^T /
+ *   symmetric matrices: the ordinary solve), then grad_values = beta grad_values - sum_c lambda_c x_c^T restricted to the pattern, by
+ *   ONE outer product over all nrhs columns (the blocks of 16 of the solve do not cut the chain).  lambda = dJ/db; lambda may be g;
+ *   grad_values NULL: the solve alone (x may then be NULL).
+ * NO SIDE EFFECTS on the factor, the values refinement reads, the determinant, the statistics, the counters of the ordinary and of the
+ * transposed solves, or the bits of later solves.  HIPMF_COUNTER_SENS_OUTER_COLUMNS sums the columns of all outer products of the handle,
+ * HIPMF_COUNTER_SENS_OUTER_US is the HIP-event time of the outer and scatter kernels of the last one.
+ * WHAT IT COSTS (tools/sensitivity.py, one MI355X, one run, 1M unknowns, 5M entries, device-resident operands, profiles/r21_sensitivity.txt;
+ * DESIGN.md section 16): the outer kernel 0.021 ms for one column and 0.136 ms for 16 (repeated calls: the operands of one column stay in
+ * the last-level cache), 0.095 ms more through a value map in random order; solver_hipmf_solve_adjoint_device 2.44 ms against 2.40 ms for
+ * solver_hipmf_solve_transpose_many_device alone, 7.56 against 7.42 ms for 16 columns; the same gradient by hand (lambda and x to the
+ * host, a NumPy gather, the gradient back) 21.8 and 293.5 ms.  The host-pointer forms, solve_tangent and the complex calls are not timed.
+ * ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION (the two solves) in this order, then
+ * ERROR_HIPMF_INVALID_VALUE for ncols / nrhs < 1, a leading dimension below ndim, or mapped = 1 without a map; the solves pass on the
+ * status of the solve they wrap.  _device: every array is a device pointer. */
+int32_t solver_hipmf_values_outer(struct InterfaceHIPMF *solver, double *grad, const double *u, const double *w, int32_t ncols, int32_t ldu, int32_t ldw,
+                                  double alpha, double beta, int32_t mapped);
+int32_t solver_hipmf_values_outer_device(struct InterfaceHIPMF *solver, double *d_grad, const double *d_u, const double *d_w, int32_t ncols, int32_t ldu,
+                                         int32_t ldw, double alpha, double beta, int32_t mapped);
+int32_t solver_hipmf_solve_tangent(struct InterfaceHIPMF *solver, double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs, int32_t ld,
+                                   int32_t mapped);
+int32_t solver_hipmf_solve_tangent_device(struct InterfaceHIPMF *solver, double *d_dx, const double *d_x, const double *d_dvalues, const double *d_db, int32_t nrhs,
+                                          int32_t ld, int32_t mapped);
+int32_t solver_hipmf_solve_adjoint(struct InterfaceHIPMF *solver, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs, int32_t ld,
+                                   double beta, int32_t mapped);
+int32_t solver_hipmf_solve_adjoint_device(struct InterfaceHIPMF *solver, double *d_lambda, double *d_grad_values, const double *d_x, const double *d_g, int32_t nrhs,
+                                          int32_t ld, double beta, int32_t mapped);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -507,6 +560,8 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_BORDER_COLUMNS 44             /* k of the border in force (solver_hipmf_set_border), 0 when none */
 #define HIPMF_COUNTER_BORDERED_STEPS 45             /* refinement steps of the last solver_hipmf_solve_bordered / _device, summed over its blocks */
 #define HIPMF_COUNTER_BORDERED_BLOCKS 46            /* 16-column blocks of that call */
+#define HIPMF_COUNTER_SENS_OUTER_COLUMNS 47         /* columns summed by the pattern-restricted outer products of this handle (solver_hipmf_values_outer / _device, the gradients of solver_hipmf_solve_adjoint / _device; the complex twin's calls), over all calls */
+#define HIPMF_COUNTER_SENS_OUTER_US 48              /* microseconds between HIP events around the outer and scatter kernels of the last such call */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -749,6 +804,30 @@ int32_t complex_solver_hipmf_solve_updated_transpose_many(struct InterfaceComple
 int32_t complex_solver_hipmf_solve_updated_transpose_many_device(struct InterfaceComplexHIPMF *solver, double *d_x, const double *d_rhs, int32_t nrhs,
                                                                  int32_t ld, const double *d_values, int32_t mapped, double rel_tol, int32_t max_steps,
                                                                  int32_t *steps, double *relres, int32_t conjugate);
+/* The sensitivity calls for the complex handle (host pointers; u, w, x, g, dx, lambda interleaved complex columns, leading dimensions in
+ * complex elements >= n; the gradient and dvalues interleaved complex numbers in the order of the values the handle is fed: mapped = 0 the
+ * nnz stored entries of initialize -- a complex-symmetric handle: its lower triangle, an off-diagonal entry standing for both positions --,
+ * mapped = 1 the nnz_in triplets of the value map; `mapped` has to name the map in force, as for complex_solver_hipmf_solve_updated).
+ * complex_solver_hipmf_values_outer:  grad[k] = beta grad[k] + alpha sum_c u[i_k, c] op(w[j_k, c]),  op = conj with conjugate_w = 1,
+ *   alpha and beta real; directly on the complex entries: per entry two chains of fused multiply-adds (real and imaginary part) in
+ *   ascending c, the same bits from call to call.
+ * complex_solver_hipmf_solve_tangent:  dx = A^{-1} (db - dA x), as solver_hipmf_solve_tangent on the real-equivalent system.
+ * complex_solver_hipmf_solve_adjoint, for a REAL-valued J of the complex x, with g = dJ/dRe x + i dJ/dIm x (twice the Wirtinger
+ *   derivative with respect to conj x), so that dJ = Re <g, dx>, <a, b> = sum conj(a_i) b_i.  From A dx = db - dA x,
+ *     dJ = Re g^H A^{-1} (db - dA x) = Re lambda^H db - Re sum_ij conj(lambda_i) dA_ij x_j     with  lambda = A^{-H} g,
+ *   and -conj(lambda_i) x_j = conj(-lambda_i conj(x_j)).  Hence
+ *     lambda = A^{-H} g  (complex_solver_hipmf_solve_transpose_many's conjugate = 1 path),
+ *     grad_k = beta grad_k - sum_c lambda[i_k, c] conj(x[j_k, c]),
+ *     dJ = Re <grad, dA> + Re <lambda, db>:  Re grad is the derivative with respect to Re a_ij, Im grad with respect to Im a_ij.
+ *   grad_values NULL: the solve alone; lambda may be g.
+ * Status codes and their order as for the real handle (the map check comes last); ERROR_HIPMF_INVALID_VALUE also for a conjugate_w other
+ * than 0 or 1.  No side effects on the handle, as for the real handle.  There are no _device forms yet. */
+int32_t complex_solver_hipmf_values_outer(struct InterfaceComplexHIPMF *solver, double *grad, const double *u, const double *w, int32_t ncols, int32_t ldu,
+                                          int32_t ldw, double alpha, double beta, int32_t mapped, int32_t conjugate_w);
+int32_t complex_solver_hipmf_solve_tangent(struct InterfaceComplexHIPMF *solver, double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs,
+                                           int32_t ld, int32_t mapped);
+int32_t complex_solver_hipmf_solve_adjoint(struct InterfaceComplexHIPMF *solver, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs,
+                                           int32_t ld, double beta, int32_t mapped);
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *solver);
 
 /* plain device-memory helpers so that callers need no HIP binding of their own */

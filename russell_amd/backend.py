@@ -282,6 +282,65 @@ class Hipmf:
             return x[0], (None if z is None else z[0]), info[0]
         return x, z, info
 
+    def _value_count(self, mapped):
+        """entries of a value array of this handle: the inputs of the value map (mapped) or what factorize takes"""
+        return int(self.nnz_in) if mapped else int(self.nnz)
+
+    @staticmethod
+    def _columns(a, n, what):
+        """(array of shape (ncols, ld), single) from a vector of n entries or an array of shape (ncols, ld) as solve_many takes it"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        single = a.ndim == 1
+        a = a.reshape(1, -1) if single else a
+        if a.ndim != 2 or a.shape[1] < n:
+            raise ValueError("%s expects a vector of %d entries or an array of shape (ncols, ld >= %d), got %r" % (what, n, n, a.shape))
+        return a, single
+
+    def values_outer(self, u, w, alpha=1.0, beta=0.0, grad=None, mapped=False):
+        """grad = beta grad + alpha sum_c u_c w_c^T restricted to the pattern, in the order of the values handed to factorize (mapped: to
+        factorize_mapped); solver_hipmf_values_outer.  u, w: vectors or arrays of shape (ncols, ld) as solve_many takes them.  grad: the
+        array to update (beta = 0: it is not read), None: a new one.  Needs initialize only."""
+        ua, _ = self._columns(u, self.n, "values_outer")
+        wa, _ = self._columns(w, self.n, "values_outer")
+        if ua.shape[0] != wa.shape[0]:
+            raise ValueError("values_outer: u has %d columns, w %d" % (ua.shape[0], wa.shape[0]))
+        g = np.zeros(self._value_count(mapped)) if grad is None else grad
+        code = self.lib.solver_hipmf_values_outer(self.h, g.ctypes.data, ua.ctypes.data, wa.ctypes.data, ua.shape[0], ua.shape[1], wa.shape[1], float(alpha),
+                                                  float(beta), int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_values_outer")
+        return g
+
+    def solve_tangent(self, x, dvalues, db=None, mapped=False, dx=None):
+        """dx = A^{-1} (db - dA x) for the matrix dA that dvalues describe (solver_hipmf_solve_tangent); x, db (None: zero): vectors or
+        arrays of shape (nrhs, ld); dx: an array of that shape to write into (its padding is left alone), None: a new one."""
+        xa, single = self._columns(x, self.n, "solve_tangent")
+        ba = None if db is None else self._columns(db, self.n, "solve_tangent")[0]
+        if ba is not None and ba.shape != xa.shape:
+            raise ValueError("solve_tangent: x has shape %r, db %r" % (xa.shape, ba.shape))
+        out = np.zeros_like(xa) if dx is None else dx
+        code = self.lib.solver_hipmf_solve_tangent(self.h, out.ctypes.data, xa.ctypes.data, np.ascontiguousarray(dvalues, dtype=np.float64).ctypes.data,
+                                                   None if ba is None else ba.ctypes.data, xa.shape[0], xa.shape[1], int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_tangent")
+        return out.reshape(xa.shape)[0] if single and dx is None else out
+
+    def solve_adjoint(self, g, x=None, beta=0.0, grad=None, mapped=False, want_grad=True, lam=None):
+        """lambda = A^{-T} g and grad = beta grad - sum_c lambda_c x_c^T restricted to the pattern, in the caller's value order
+        (solver_hipmf_solve_adjoint).  g, x: vectors or arrays of shape (nrhs, ld); lam: the array lambda is written into (it may be g),
+        None: a new one; want_grad False: the solve alone.  Returns (lambda, grad or None)."""
+        ga, single = self._columns(g, self.n, "solve_adjoint")
+        xa = None if x is None else self._columns(x, self.n, "solve_adjoint")[0]
+        if want_grad and (xa is None or xa.shape != ga.shape):
+            raise ValueError("solve_adjoint: the gradient needs x in the shape of g")
+        out = np.zeros_like(ga) if lam is None else lam
+        gr = None if not want_grad else (np.zeros(self._value_count(mapped)) if grad is None else grad)
+        code = self.lib.solver_hipmf_solve_adjoint(self.h, out.ctypes.data, None if gr is None else gr.ctypes.data, None if xa is None else xa.ctypes.data,
+                                                   ga.ctypes.data, ga.shape[0], ga.shape[1], float(beta), int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_adjoint")
+        return (out.reshape(ga.shape)[0] if single and lam is None else out), gr
+
     def mat_vec_mul(self, u, alpha=1.0):
         v = np.zeros(self.n)
         code = self.lib.solver_hipmf_mat_vec_mul(self.h, v, alpha, np.ascontiguousarray(u, dtype=np.float64))
@@ -305,7 +364,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -446,6 +505,25 @@ class Hipmf:
             raise self._err(code, "solver_hipmf_solve_bordered_device")
         return info[:nrhs]
 
+    def values_outer_device(self, d_grad, d_u, d_w, ncols=1, alpha=1.0, beta=0.0, mapped=False, ldu=None, ldw=None):
+        """values_outer with grad, u and w (column-major ldu x ncols, ldw x ncols) resident on the device"""
+        code = self.lib.solver_hipmf_values_outer_device(self.h, d_grad, d_u, d_w, int(ncols), int(ldu or self.n), int(ldw or self.n), float(alpha), float(beta),
+                                                         int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_values_outer_device")
+
+    def solve_tangent_device(self, d_dx, d_x, d_dvalues, d_db=None, nrhs=1, mapped=False, ld=None):
+        """solve_tangent with dx, x, db (column-major ld x nrhs; db None: zero) and dvalues resident on the device"""
+        code = self.lib.solver_hipmf_solve_tangent_device(self.h, d_dx, d_x, d_dvalues, d_db, int(nrhs), int(ld or self.n), int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_tangent_device")
+
+    def solve_adjoint_device(self, d_lambda, d_grad, d_x, d_g, nrhs=1, beta=0.0, mapped=False, ld=None):
+        """solve_adjoint with lambda, x, g (column-major ld x nrhs) and grad (None: the solve alone) resident on the device"""
+        code = self.lib.solver_hipmf_solve_adjoint_device(self.h, d_lambda, d_grad, d_x, d_g, int(nrhs), int(ld or self.n), float(beta), int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_adjoint_device")
+
     def solve_updated_many_device(self, d_x, d_rhs, nrhs, d_values, mapped=False, rel_tol=0.0, max_steps=0, ld=None, transpose=False):
         """solve_updated_many with x, rhs (column-major ld x nrhs) and values resident on the device; returns (steps, relres, status)"""
         name = "solver_hipmf_solve_updated_transpose_many_device" if transpose else "solver_hipmf_solve_updated_many_device"
@@ -456,3 +534,136 @@ class Hipmf:
         if code not in (0, self.WARNING_NOT_CONVERGED):
             raise self._err(code, name)
         return steps[:nrhs], relres[:nrhs], code
+
+
+class ComplexHipmf:
+    """The complex twin's handle (complex_solver_hipmf_*): life cycle, solve and the sensitivity calls.  Complex vectors and value arrays
+    go in and out as NumPy complex128 arrays; the library sees them as interleaved (re, im) pairs."""
+
+    def __init__(self, lib_path=None):
+        self.lib = _capi.load(lib_path)
+        self.h = self.lib.complex_solver_hipmf_new()
+        if not self.h:
+            raise RuntimeError("complex_solver_hipmf_new returned NULL: no HIP device visible (there is no CPU fallback)")
+        self.n = self.nnz = self.nnz_in = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.complex_solver_hipmf_drop(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _err(self, code, where):
+        return HipmfError(code, where, (self.lib.complex_solver_hipmf_last_error(self.h) or b"").decode())
+
+    @staticmethod
+    def _z(a):
+        return np.ascontiguousarray(a, dtype=np.complex128)
+
+    def initialize(self, n, row_pointers, col_indices, ordering=0, scaling=1, pivot_epsilon=-1.0, refinement_nstep=-1, verbose=False, general_symmetric=False,
+                   values=None):
+        rp = np.ascontiguousarray(row_pointers, dtype=np.int32)
+        ci = np.ascontiguousarray(col_indices, dtype=np.int32)
+        self.n, self.nnz = int(n), int(rp[n])
+        self._init_values = None if values is None else self._z(values)
+        return self.lib.complex_solver_hipmf_initialize(self.h, ordering, scaling, pivot_epsilon, refinement_nstep, int(verbose), int(general_symmetric), n, rp, ci,
+                                                        None if values is None else self._init_values.ctypes.data)
+
+    def factorize(self, values, verbose=False):
+        """numeric factorisation from the nnz stored complex entries (drops a triplet map: the identity map is back in force)"""
+        npv = C.c_int32()
+        code = self.lib.complex_solver_hipmf_factorize(self.h, None, None, C.byref(npv), None, None, None, None, 0, int(verbose), self._z(values).view(np.float64))
+        self.num_perturbed, self.nnz_in = npv.value, 0
+        return code
+
+    def set_value_map(self, seg_ptr, seg_idx):
+        sp = np.ascontiguousarray(seg_ptr, dtype=np.int32)
+        si = np.ascontiguousarray(seg_idx, dtype=np.int32)
+        code = self.lib.complex_solver_hipmf_set_value_map(self.h, int(si.size), sp, si)
+        if code == 0:
+            self.nnz_in = int(si.size)
+        return code
+
+    def factorize_mapped(self, input_values, verbose=False):
+        return self.lib.complex_solver_hipmf_factorize_mapped(self.h, None, None, None, None, int(verbose), self._z(input_values).view(np.float64))
+
+    def solve(self, rhs, verbose=False):
+        x = np.zeros(self.n, np.complex128)
+        code = self.lib.complex_solver_hipmf_solve(self.h, x.view(np.float64), self._z(rhs).view(np.float64), int(verbose))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve")
+        return x
+
+    def solve_transpose(self, rhs, conjugate=True, verbose=False):
+        """x = A^{-H} rhs (conjugate) or A^{-T} rhs with the factor of A"""
+        x = np.zeros(self.n, np.complex128)
+        code = self.lib.complex_solver_hipmf_solve_transpose(self.h, x.view(np.float64), self._z(rhs).view(np.float64), int(bool(conjugate)), int(verbose))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve_transpose")
+        return x
+
+    def determinant(self):
+        """(real, imaginary, exponent): det A = (real + i imaginary) x 10^exponent, of the last factorisation"""
+        g = (C.c_double(), C.c_double(), C.c_double())
+        code = self.lib.complex_solver_hipmf_get_determinant(self.h, C.byref(g[0]), C.byref(g[1]), C.byref(g[2]))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_get_determinant")
+        return tuple(q.value for q in g)
+
+    def counter(self, name):
+        return int(self.lib.complex_solver_hipmf_get_counter(self.h, Hipmf.COUNTERS[name]))
+
+    def _columns(self, a, what):
+        a = self._z(a)
+        single = a.ndim == 1
+        a = a.reshape(1, -1) if single else a
+        if a.ndim != 2 or a.shape[1] < self.n:
+            raise ValueError("%s expects a vector of %d entries or an array of shape (ncols, ld >= %d), got %r" % (what, self.n, self.n, a.shape))
+        return a, single
+
+    def _value_count(self, mapped):
+        return int(self.nnz_in) if mapped else int(self.nnz)
+
+    def values_outer(self, u, w, alpha=1.0, beta=0.0, grad=None, mapped=False, conjugate_w=False):
+        """grad = beta grad + alpha sum_c u_c op(w_c)^T restricted to the pattern, op = conj with conjugate_w, in the order of the complex
+        values the handle is fed (mapped: the triplets of the value map); complex_solver_hipmf_values_outer."""
+        ua, _ = self._columns(u, "values_outer")
+        wa, _ = self._columns(w, "values_outer")
+        if ua.shape[0] != wa.shape[0]:
+            raise ValueError("values_outer: u has %d columns, w %d" % (ua.shape[0], wa.shape[0]))
+        g = np.zeros(self._value_count(mapped), np.complex128) if grad is None else grad
+        code = self.lib.complex_solver_hipmf_values_outer(self.h, g.ctypes.data, ua.ctypes.data, wa.ctypes.data, ua.shape[0], ua.shape[1], wa.shape[1], float(alpha),
+                                                          float(beta), int(bool(mapped)), int(bool(conjugate_w)))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_values_outer")
+        return g
+
+    def solve_tangent(self, x, dvalues, db=None, mapped=False, dx=None):
+        """dx = A^{-1} (db - dA x) for the complex matrix dA that dvalues describe (complex_solver_hipmf_solve_tangent)"""
+        xa, single = self._columns(x, "solve_tangent")
+        ba = None if db is None else self._columns(db, "solve_tangent")[0]
+        if ba is not None and ba.shape != xa.shape:
+            raise ValueError("solve_tangent: x has shape %r, db %r" % (xa.shape, ba.shape))
+        out = np.zeros_like(xa) if dx is None else dx
+        code = self.lib.complex_solver_hipmf_solve_tangent(self.h, out.ctypes.data, xa.ctypes.data, self._z(dvalues).ctypes.data, None if ba is None else ba.ctypes.data,
+                                                           xa.shape[0], xa.shape[1], int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve_tangent")
+        return out.reshape(xa.shape)[0] if single and dx is None else out
+
+    def solve_adjoint(self, g, x=None, beta=0.0, grad=None, mapped=False, want_grad=True, lam=None):
+        """lambda = A^{-H} g and grad_k = beta grad_k - sum_c lambda_i conj(x_j) for a real-valued J with g = dJ/dRe x + i dJ/dIm x
+        (complex_solver_hipmf_solve_adjoint): dJ = Re <grad, dA> + Re <lambda, db>.  Returns (lambda, grad or None)."""
+        ga, single = self._columns(g, "solve_adjoint")
+        xa = None if x is None else self._columns(x, "solve_adjoint")[0]
+        if want_grad and (xa is None or xa.shape != ga.shape):
+            raise ValueError("solve_adjoint: the gradient needs x in the shape of g")
+        out = np.zeros_like(ga) if lam is None else lam
+        gr = None if not want_grad else (np.zeros(self._value_count(mapped), np.complex128) if grad is None else grad)
+        code = self.lib.complex_solver_hipmf_solve_adjoint(self.h, out.ctypes.data, None if gr is None else gr.ctypes.data, None if xa is None else xa.ctypes.data,
+                                                           ga.ctypes.data, ga.shape[0], ga.shape[1], float(beta), int(bool(mapped)))
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve_adjoint")
+        return (out.reshape(ga.shape)[0] if single and lam is None else out), gr

@@ -39,6 +39,10 @@ struct InterfaceComplexHIPMF {
     int32_t effective_ordering = 0;
     bool triplet_map = false; // the installed map reads the caller's COO triplets (complex_solver_hipmf_set_value_map)
     int8_t pairs_state = 0;   // the pairing the complex error analysis relies on: 0 not checked yet, 1 holds, -1 broken
+    // the sensitivity calls (kernels_sensitivity.hpp) work on the caller's complex entries: row and column of every stored entry, the
+    // inverse of the triplet map (triplet -> stored entries, ascending; empty without one), and whether the solver holds both as they are
+    std::vector<int32_t> zrow, zcol, tri_inv_ptr, tri_inv_idx;
+    bool sens_uploaded = false;
 };
 
 // No C++ exception crosses the C boundary (the same rule as interface_hipmf.cpp): a failed host allocation comes back as ERROR_MALLOC
@@ -180,6 +184,10 @@ static int32_t c_initialize_body(struct InterfaceComplexHIPMF *h, int32_t orderi
     }
     code = h->solver.initialize(2 * ndim, rp2.data(), ci2.data(), false, so, no, values ? v2.data() : nullptr);
     if (code != SUCCESSFUL_EXIT) return code;
+    h->zrow.resize((size_t)h->nnz), h->zcol.assign(col_indices, col_indices + h->nnz);
+    for (int32_t i = 0; i < ndim; i++)
+        for (int32_t k = row_pointers[i]; k < row_pointers[i + 1]; k++) h->zrow[(size_t)k] = i;
+    h->tri_inv_ptr.clear(), h->tri_inv_idx.clear(), h->sens_uploaded = false;
     return install_map(h, h->nnz, nullptr, nullptr);
 }
 
@@ -198,6 +206,16 @@ static int32_t c_set_value_map_body(struct InterfaceComplexHIPMF *h, int32_t nnz
     for (int32_t t = 0; t < nnz_in; t++)
         if (seg_idx[t] < 0 || seg_idx[t] >= nnz_in) return ERROR_HIPMF_INVALID_VALUE;
     h->triplet_map = true;
+    { // triplet t is read by the stored entries tri_inv_idx[tri_inv_ptr[t] .. tri_inv_ptr[t + 1]), ascending
+        h->tri_inv_ptr.assign((size_t)nnz_in + 1, 0);
+        for (int32_t q = 0; q < nnz_in; q++) h->tri_inv_ptr[(size_t)seg_idx[q] + 1]++;
+        for (int32_t t = 0; t < nnz_in; t++) h->tri_inv_ptr[(size_t)t + 1] += h->tri_inv_ptr[(size_t)t];
+        h->tri_inv_idx.resize((size_t)nnz_in);
+        std::vector<int32_t> at(h->tri_inv_ptr.begin(), h->tri_inv_ptr.end() - 1);
+        for (int64_t c = 0; c < h->nnz; c++)
+            for (int32_t q = seg_ptr[c]; q < seg_ptr[c + 1]; q++) h->tri_inv_idx[(size_t)at[(size_t)seg_idx[q]]++] = (int32_t)c;
+        h->sens_uploaded = false;
+    }
     return install_map(h, nnz_in, seg_ptr, seg_idx);
 }
 
@@ -240,6 +258,7 @@ static int32_t c_factorize_body(struct InterfaceComplexHIPMF *h, int32_t *effect
         int32_t c = install_map(h, h->nnz, nullptr, nullptr);
         if (c != SUCCESSFUL_EXIT) return c;
         h->triplet_map = false;
+        h->tri_inv_ptr.clear(), h->tri_inv_idx.clear(), h->sens_uploaded = false;
     }
     h->solver.opt.verbose = verbose == 1;
     const int32_t code = finish(h, h->solver.factorize_mapped(values, false), effective_ordering, effective_scaling, num_perturbed_pivots, rcond_estimate);
@@ -577,6 +596,68 @@ int32_t complex_solver_hipmf_solve_with_error_analysis(struct InterfaceComplexHI
     });
 }
 
+// Sensitivities with respect to the complex matrix values (Solver::values_outer_complex, solve_tangent, solve_adjoint;
+// kernels_sensitivity.hpp), host pointers.  The outer product runs on the caller's complex entries and their order -- the stored entries
+// (a complex-symmetric handle: its lower triangle, an off-diagonal entry standing for both positions) or the triplets of the value map --;
+// the two solves run on the real-equivalent system, whose vectors the interleaved columns are: A dx = db - dA x there, and A^H lambda = g
+// as its transposed system.  `mapped` has to name the map in force, as for complex_solver_hipmf_solve_updated.
+static int32_t c_sens_map_check(struct InterfaceComplexHIPMF *h, int32_t mapped, const char *who) {
+    if ((mapped != 0) == h->triplet_map) return SUCCESSFUL_EXIT;
+    h->solver.last_error = mapped != 0 ? std::string(who) + ": mapped = 1 but no triplet map is installed (complex_solver_hipmf_set_value_map)"
+                                       : std::string(who) + ": mapped = 0 but the triplet map of complex_solver_hipmf_set_value_map is installed";
+    return ERROR_HIPMF_INVALID_VALUE;
+}
+
+// ... and the pattern and the inverse triplet map of the outer product on the device
+static int32_t c_sens_prepare(struct InterfaceComplexHIPMF *h, int32_t mapped, const char *who) {
+    if (const int32_t c = c_sens_map_check(h, mapped, who); c != SUCCESSFUL_EXIT) return c;
+    if (h->sens_uploaded && h->solver.complex_pattern_set()) return SUCCESSFUL_EXIT; // (a re-matching factorize drops the solver's copy)
+    int32_t code = h->solver.set_complex_pattern(h->nnz, h->zrow, h->zcol, h->sym_lower);
+    if (code == SUCCESSFUL_EXIT) code = h->solver.set_complex_value_map(h->triplet_map ? (int64_t)h->tri_inv_idx.size() : 0, h->tri_inv_ptr, h->tri_inv_idx);
+    h->sens_uploaded = code == SUCCESSFUL_EXIT;
+    return code;
+}
+
+int32_t complex_solver_hipmf_values_outer(struct InterfaceComplexHIPMF *h, double *grad, const double *u, const double *w, int32_t ncols, int32_t ldu, int32_t ldw,
+                                          double alpha, double beta, int32_t mapped, int32_t conjugate_w) {
+    return guarded(h, [&]() {
+        if (!h || !grad || !u || !w) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.initialized) return (int32_t)ERROR_NEED_INITIALIZATION;
+        if (ncols < 1 || ldu < h->n || ldw < h->n || (conjugate_w != 0 && conjugate_w != 1)) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        const int32_t code = c_sens_prepare(h, mapped, "complex_solver_hipmf_values_outer");
+        if (code != SUCCESSFUL_EXIT) return code;
+        return h->solver.values_outer_complex(grad, u, w, ncols, ldu, ldw, alpha, beta, conjugate_w == 1);
+    });
+}
+
+int32_t complex_solver_hipmf_solve_tangent(struct InterfaceComplexHIPMF *h, double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs,
+                                           int32_t ld, int32_t mapped) {
+    return guarded(h, [&]() {
+        if (!h || !dx || !x || !dvalues) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.initialized) return (int32_t)ERROR_NEED_INITIALIZATION;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (nrhs < 1 || ld < h->n) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        const int32_t code = c_sens_map_check(h, mapped, "complex_solver_hipmf_solve_tangent"); // (the tangent needs no pattern of its own)
+        if (code != SUCCESSFUL_EXIT) return code;
+        return h->solver.solve_tangent(dx, x, dvalues, db, nrhs, 2 * (int64_t)ld, true, false); // (the handle always carries a value map)
+    });
+}
+
+int32_t complex_solver_hipmf_solve_adjoint(struct InterfaceComplexHIPMF *h, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs,
+                                           int32_t ld, double beta, int32_t mapped) {
+    return guarded(h, [&]() {
+        if (!h || !lambda || !g || (grad_values && !x)) return (int32_t)ERROR_NULL_POINTER;
+        if (!h->solver.initialized) return (int32_t)ERROR_NEED_INITIALIZATION;
+        if (!h->solver.factorized) return (int32_t)ERROR_NEED_FACTORIZATION;
+        if (nrhs < 1 || ld < h->n) return (int32_t)ERROR_HIPMF_INVALID_VALUE;
+        int32_t code = grad_values ? c_sens_prepare(h, mapped, "complex_solver_hipmf_solve_adjoint") : (int32_t)SUCCESSFUL_EXIT;
+        if (code != SUCCESSFUL_EXIT) return code;
+        code = h->solver.solve_adjoint(lambda, nullptr, nullptr, g, nrhs, 2 * (int64_t)ld, 0.0, false, false); // lambda = A^{-H} g: the transposed real-equivalent system
+        if (code != SUCCESSFUL_EXIT || !grad_values) return code;
+        return h->solver.values_outer_complex(grad_values, lambda, x, nrhs, ld, ld, -1.0, beta, true); // grad_k = beta grad_k - sum_c lambda_i conj(x_j)
+    });
+}
+
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *h) { return h ? h->solver.last_error.c_str() : "null solver"; }
 
 static int32_t c_get_stats_body(struct InterfaceComplexHIPMF *h, int64_t *is, double *ds) {
@@ -640,6 +721,8 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_EXTRA_PRECISE_RESIDUAL_US: return (int64_t)(1e3 * s.extra_ms[0]);
     case HIPMF_COUNTER_EXTRA_PRECISE_PRECOND_US: return (int64_t)(1e3 * s.extra_ms[1]);
     case HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US: return (int64_t)(1e3 * s.extra_ms[2]);
+    case HIPMF_COUNTER_SENS_OUTER_COLUMNS: return s.sens_outer_columns;
+    case HIPMF_COUNTER_SENS_OUTER_US: return (int64_t)(1e3 * s.sens_outer_ms);
     default: return -1;
     }
 }

@@ -743,6 +743,63 @@ int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *h, double *d_x
     return guarded(h, [&]() { return solve_bordered_body(h, d_x, d_z, d_f, d_g, nrhs, ldx, ldz, max_steps, info, verbose, true, "solver_hipmf_solve_bordered_device"); });
 }
 
+// Sensitivities with respect to the matrix values (Solver::values_outer, solve_tangent, solve_adjoint; kernels_sensitivity.hpp).  Status
+// codes in this order: ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, (the two solves) ERROR_NEED_FACTORIZATION, then
+// ERROR_HIPMF_INVALID_VALUE (ncols / nrhs < 1, a leading dimension below ndim, mapped without a map).
+static int32_t values_outer_body(struct InterfaceHIPMF *h, double *grad, const double *u, const double *w, int32_t ncols, int32_t ldu, int32_t ldw, double alpha,
+                                 double beta, int32_t mapped, bool on_device) {
+    if (!h || !grad || !u || !w) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    return h->solver.values_outer(grad, u, w, ncols, ldu, ldw, alpha, beta, mapped != 0, on_device);
+}
+
+int32_t solver_hipmf_values_outer(struct InterfaceHIPMF *h, double *grad, const double *u, const double *w, int32_t ncols, int32_t ldu, int32_t ldw, double alpha,
+                                  double beta, int32_t mapped) {
+    return guarded(h, [&]() { return values_outer_body(h, grad, u, w, ncols, ldu, ldw, alpha, beta, mapped, false); });
+}
+
+int32_t solver_hipmf_values_outer_device(struct InterfaceHIPMF *h, double *d_grad, const double *d_u, const double *d_w, int32_t ncols, int32_t ldu, int32_t ldw,
+                                         double alpha, double beta, int32_t mapped) {
+    return guarded(h, [&]() { return values_outer_body(h, d_grad, d_u, d_w, ncols, ldu, ldw, alpha, beta, mapped, true); });
+}
+
+static int32_t solve_tangent_body(struct InterfaceHIPMF *h, double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs, int32_t ld,
+                                  int32_t mapped, bool on_device) {
+    if (!h || !dx || !x || !dvalues) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    return h->solver.solve_tangent(dx, x, dvalues, db, nrhs, ld, mapped != 0, on_device);
+}
+
+int32_t solver_hipmf_solve_tangent(struct InterfaceHIPMF *h, double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs, int32_t ld,
+                                   int32_t mapped) {
+    return guarded(h, [&]() { return solve_tangent_body(h, dx, x, dvalues, db, nrhs, ld, mapped, false); });
+}
+
+int32_t solver_hipmf_solve_tangent_device(struct InterfaceHIPMF *h, double *d_dx, const double *d_x, const double *d_dvalues, const double *d_db, int32_t nrhs,
+                                          int32_t ld, int32_t mapped) {
+    return guarded(h, [&]() { return solve_tangent_body(h, d_dx, d_x, d_dvalues, d_db, nrhs, ld, mapped, true); });
+}
+
+static int32_t solve_adjoint_body(struct InterfaceHIPMF *h, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs, int32_t ld,
+                                  double beta, int32_t mapped, bool on_device) {
+    if (!h || !lambda || !g || (grad_values && !x)) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    // (a symmetric matrix that was expanded to a general one inside the handle still has A^T = A: the ordinary solve)
+    return h->solver.solve_adjoint(lambda, grad_values, x, g, nrhs, ld, beta, mapped != 0, on_device, h->expanded);
+}
+
+int32_t solver_hipmf_solve_adjoint(struct InterfaceHIPMF *h, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs, int32_t ld,
+                                   double beta, int32_t mapped) {
+    return guarded(h, [&]() { return solve_adjoint_body(h, lambda, grad_values, x, g, nrhs, ld, beta, mapped, false); });
+}
+
+int32_t solver_hipmf_solve_adjoint_device(struct InterfaceHIPMF *h, double *d_lambda, double *d_grad_values, const double *d_x, const double *d_g, int32_t nrhs,
+                                          int32_t ld, double beta, int32_t mapped) {
+    return guarded(h, [&]() { return solve_adjoint_body(h, d_lambda, d_grad_values, d_x, d_g, nrhs, ld, beta, mapped, true); });
+}
+
 // Solve exactly as solver_hipmf_solve does, then analyse the returned x against A and b: the argument shape of solver_mumps_solve
 // (interface_mumps.c:243-247; RINFOG(4..11) copied out at interface_mumps.c:266-275, solver_mumps.rs:249-253,415-422).
 // error_analysis_option: 0 none (the array is not touched), 1 all eight values (condition numbers included), 2 entries 0 - 4.
@@ -862,6 +919,8 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_BORDER_COLUMNS: return s.bd_k;
     case HIPMF_COUNTER_BORDERED_STEPS: return s.bordered_steps;
     case HIPMF_COUNTER_BORDERED_BLOCKS: return s.bordered_blocks;
+    case HIPMF_COUNTER_SENS_OUTER_COLUMNS: return s.sens_outer_columns;
+    case HIPMF_COUNTER_SENS_OUTER_US: return (int64_t)(1e3 * s.sens_outer_ms);
     default: return -1;
     }
 }

@@ -15,3 +15,4 @@
 #include "kernels_vector.hpp"
 #include "kernels_refine_extra.hpp"
 #include "kernels_border.hpp"
+#include "kernels_sensitivity.hpp"

@@ -1899,6 +1899,7 @@ int32_t Solver::set_value_map(int64_t nin, const int32_t *seg_ptr, const int32_t
     HIPC(hipMemcpy(d_seg_ptr, seg_ptr, sizeof(int32_t) * (nnz + 1), hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
     HIPC(hipMemcpy(d_seg_idx, seg_idx, sizeof(int32_t) * nmap, hipMemcpyHostToDevice), ERROR_HIP_MEMCPY);
     nnz_in = nin;
+    sn_map_ready = false; // (the inverse map of values_outer is rebuilt from this one at its next mapped call)
     if (h_seg_ptr.data() != seg_ptr) h_seg_ptr.assign(seg_ptr, seg_ptr + nnz + 1), h_seg_idx.assign(seg_idx, seg_idx + nmap);
     return SUCCESSFUL_EXIT;
 }
@@ -4525,6 +4526,246 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
     return SUCCESSFUL_EXIT;
 }
 
+// ---- sensitivities with respect to the matrix values (kernels_sensitivity.hpp) ----
+// J = J(x), A x = b: with lambda = A^{-T} dJ/dx the derivatives are dJ/db = lambda and dJ/da_ij = -lambda_i x_j on the pattern (adjoint,
+// solve_adjoint); forward, dx = A^{-1} (db - dA x) (solve_tangent).  <dJ/dx, dx> = <grad, dvalues> + <lambda, db> ties the two together.
+// The products are formed per STORED entry of the handle (values_outer) and carried to the order of the caller's values by the inverse
+// of whatever staging a factorize applies to them (stage_values): the value map, the expansion of a mirrored lower triangle.
+namespace {
+
+// The inverse of a staging map.  Slot j of the handle's CSR reads the inputs idx[ptr[j] .. ptr[j + 1]) (ptr == nullptr: the one input
+// idx[j]); input t is read by the slots inv_idx[inv_ptr[t] .. inv_ptr[t + 1]), ascending.  false: the map subtracts an input (~t: the
+// real-equivalent form of a complex matrix, whose gradient is values_outer_complex's business).
+bool invert_staging(int64_t nin, int64_t nslot, const int32_t *ptr, const int32_t *idx, std::vector<int32_t> &inv_ptr, std::vector<int32_t> &inv_idx) {
+    const int64_t nmap = ptr ? ptr[nslot] : nslot;
+    auto input = [&](int64_t q) { return idx[q]; };
+    for (int64_t q = 0; q < nmap; q++)
+        if (idx[q] < 0) return false;
+    inv_ptr.assign((size_t)nin + 1, 0);
+    for (int64_t q = 0; q < nmap; q++) inv_ptr[(size_t)input(q) + 1]++;
+    for (int64_t t = 0; t < nin; t++) inv_ptr[(size_t)t + 1] += inv_ptr[(size_t)t];
+    inv_idx.resize((size_t)nmap);
+    std::vector<int32_t> at(inv_ptr.begin(), inv_ptr.end() - 1);
+    for (int64_t j = 0; j < nslot; j++)
+        for (int64_t q = ptr ? ptr[j] : j; q < (ptr ? ptr[j + 1] : j + 1); q++) inv_idx[(size_t)at[(size_t)input(q)]++] = (int32_t)j;
+    return true;
+}
+
+// What a transposed solve leaves behind, put back when the guard goes (NestedSolveGuard keeps the ordinary solves' side)
+struct TransposedStatsGuard {
+    Solver &s;
+    auto fields() const { return std::tie(s.transposed_solves, s.transposed_blocks, s.krylov_iterations_t, s.last_omega_t, s.refinement_steps_done_t); }
+    const std::tuple<int64_t, int64_t, int64_t, double, int32_t> kept;
+    explicit TransposedStatsGuard(Solver &s_) : s(s_), kept(fields()) {}
+    ~TransposedStatsGuard() { fields() = kept; }
+};
+
+dim3 sens_grid(int64_t count) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(SENS_MAX_WG, (count + 255) / 256))); }
+
+} // namespace
+
+int32_t Solver::values_outer(double *grad, const double *u, const double *w, int32_t ncols, int64_t ldu, int64_t ldw, double alpha, double beta, bool mapped,
+                             bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!grad || !u || !w) return ERROR_NULL_POINTER;
+    const int32_t n = S.n;
+    const int64_t nnz = S.nnz_a;
+    if (ncols < 1 || ldu < n || ldw < n || (mapped && nnz_in < 1)) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    // the way back to the caller's order: nothing (the CSR order), or an inverse map, built at its first use
+    const int32_t *inv_ptr = nullptr, *inv_idx = nullptr;
+    int64_t nout = nnz;
+    if (mapped) {
+        if (!sn_map_ready) {
+            std::vector<int32_t> ip, ii;
+            if (!invert_staging(nnz_in, nnz, h_seg_ptr.data(), h_seg_idx.data(), ip, ii)) return ERROR_HIPMF_INVALID_VALUE;
+            HIPC(d_sn_map_ptr.upload(ip), ERROR_HIP_MALLOC);
+            HIPC(d_sn_map_idx.upload(ii), ERROR_HIP_MALLOC);
+            sn_map_ready = true;
+        }
+        inv_ptr = d_sn_map_ptr, inv_idx = d_sn_map_idx, nout = nnz_in;
+    } else if (d_emap) {
+        if (!sn_exp_ready) {
+            std::vector<int32_t> ip, ii;
+            (void)invert_staging(nnz_low, nnz, nullptr, h_emap.data(), ip, ii);
+            HIPC(d_sn_exp_ptr.upload(ip), ERROR_HIP_MALLOC);
+            HIPC(d_sn_exp_idx.upload(ii), ERROR_HIP_MALLOC);
+            sn_exp_ready = true;
+        }
+        inv_ptr = d_sn_exp_ptr, inv_idx = d_sn_exp_idx, nout = nnz_low;
+    }
+    if (!sn_ev0) HIPC(hipEventCreate(sn_ev0.put()), ERROR_HIPMF_NO_DEVICE);
+    if (!sn_ev1) HIPC(hipEventCreate(sn_ev1.put()), ERROR_HIPMF_NO_DEVICE);
+    const double *du = u, *dw = w;
+    double *dout = grad;
+    if (!on_device) { // the operand columns packed (leading dimension n), the gradient in the caller's order
+        const size_t nb = sizeof(double) * (size_t)n, blk = (size_t)n * ncols;
+        HIPC(d_sn_ops.need(2 * blk), ERROR_HIP_MALLOC);
+        HIPC(d_sn_out.need((size_t)std::max<int64_t>(nout, 1)), ERROR_HIP_MALLOC);
+        for (int32_t c = 0; c < ncols; c++) {
+            HIPC(hipMemcpyAsync(d_sn_ops.a + (size_t)c * n, u + (int64_t)c * ldu, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            HIPC(hipMemcpyAsync(d_sn_ops.a + blk + (size_t)c * n, w + (int64_t)c * ldw, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        }
+        if (beta != 0.0) HIPC(hipMemcpyAsync(d_sn_out.a, grad, sizeof(double) * (size_t)nout, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        du = d_sn_ops.a, dw = d_sn_ops.a + blk, ldu = ldw = n, dout = d_sn_out.a;
+    }
+    double *dslot = dout;
+    if (inv_ptr) {
+        HIPC(d_sn_slot.need((size_t)std::max<int64_t>(nnz, 1)), ERROR_HIP_MALLOC);
+        dslot = d_sn_slot.a;
+    }
+    const double beta_outer = inv_ptr ? 0.0 : beta; // (through a map the caller's gradient enters in the scatter)
+    HIPC(hipEventRecord((hipEvent_t)sn_ev0, STREAM), ERROR_HIP_SYNCHRONIZE);
+    if (d_tptr) hipLaunchKernelGGL(k_sens_outer<true>, sens_grid(nnz), dim3(256), 0, STREAM, nnz, d_arow, d_ci, du, ldu, dw, ldw, ncols, alpha, beta_outer, dslot);
+    else hipLaunchKernelGGL(k_sens_outer<false>, sens_grid(nnz), dim3(256), 0, STREAM, nnz, d_arow, d_ci, du, ldu, dw, ldw, ncols, alpha, beta_outer, dslot);
+    if (inv_ptr) hipLaunchKernelGGL(k_sens_scatter, sens_grid(nout), dim3(256), 0, STREAM, nout, inv_ptr, inv_idx, (const double *)dslot, beta, dout);
+    HIPC(hipEventRecord((hipEvent_t)sn_ev1, STREAM), ERROR_HIP_SYNCHRONIZE);
+    if (!on_device) HIPC(hipMemcpyAsync(grad, dout, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, (hipEvent_t)sn_ev0, (hipEvent_t)sn_ev1);
+    sens_outer_ms = ms;
+    sens_outer_columns += ncols;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::solve_tangent(double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs, int64_t ld, bool mapped, bool on_device) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!dx || !x || !dvalues) return ERROR_NULL_POINTER;
+    const int32_t n = S.n;
+    if (nrhs < 1 || ld < n || (mapped && nnz_in < 1)) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    const size_t nb = sizeof(double) * (size_t)n, blk = (size_t)n * nrhs;
+    // R = db - dA x and Y = A^{-1} R packed (leading dimension n), a zero vector for db == nullptr; x and db of a host-pointer call
+    HIPC(d_sn_rhs.need((on_device ? 2 : 4) * blk + (size_t)n), ERROR_HIP_MALLOC);
+    const int64_t pcol = 2 * (int64_t)std::max(spmv_blocks, 1);
+    HIPC(d_sn_part.need((size_t)pcol * KRYB_COLS), ERROR_HIP_MALLOC);
+    if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(S.nnz_a, 1)), ERROR_HIP_MALLOC);
+    double *const R = d_sn_rhs.a, *const Y = R + blk, *const zero = Y + blk, *const XS = zero + n, *const BS = XS + blk;
+    int32_t code = stage_values(d_up_vals, dvalues, mapped, on_device);
+    if (code != SUCCESSFUL_EXIT) return code;
+    const double *X = x, *B = db;
+    int64_t xstr = ld, bstr = ld;
+    if (!on_device) {
+        for (int32_t c = 0; c < nrhs; c++) {
+            HIPC(hipMemcpyAsync(XS + (size_t)c * n, x + (int64_t)c * ld, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+            if (db) HIPC(hipMemcpyAsync(BS + (size_t)c * n, db + (int64_t)c * ld, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        }
+        X = XS, B = BS, xstr = bstr = n;
+    }
+    if (!db) {
+        HIPC(hipMemsetAsync(zero, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+        B = zero, bstr = 0; // (every column reads the same zeros)
+    }
+    for (int32_t j0 = 0; j0 < nrhs; j0 += KRYB_COLS) { // the right-hand sides: the blocked residual of the solve_updated forms on the staged dvalues
+        const int32_t nk = std::min<int32_t>(KRYB_COLS, nrhs - j0);
+        OpPlain::residual_blk(*this, STREAM, n, X + (int64_t)j0 * xstr, xstr, B + (int64_t)j0 * bstr, bstr, R + (size_t)j0 * n, nk, (1u << nk) - 1u, d_sn_part.a, pcol);
+    }
+    {
+        const NestedSolveGuard guard(*this); // (refined as the handle is set up; the statistics of the ordinary solves stay the caller's)
+        code = solve(Y, R, nrhs, n, true);
+    }
+    if (code != SUCCESSFUL_EXIT) return code;
+    for (int32_t c = 0; c < nrhs; c++)
+        HIPC(hipMemcpyAsync(dx + (int64_t)c * ld, Y + (size_t)c * n, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::solve_adjoint(double *lambda, double *grad, const double *x, const double *g, int32_t nrhs, int64_t ld, double beta, bool mapped, bool on_device,
+                              bool symmetric_matrix) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!lambda || !g || (grad && !x)) return ERROR_NULL_POINTER;
+    const int32_t n = S.n;
+    if (nrhs < 1 || ld < n || (grad && mapped && nnz_in < 1)) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    int32_t code;
+    {
+        const NestedSolveGuard guard(*this);
+        const TransposedStatsGuard guard_t(*this);
+        const bool plain = symmetric_matrix || S.sym_mode || d_tptr; // A^T = A: the ordinary solve, which reads its right-hand sides again while it refines
+        const double *rhs = g;
+        if (plain && on_device && lambda == g) {
+            const size_t span = (size_t)(nrhs - 1) * (size_t)ld + (size_t)n;
+            HIPC(d_sn_rhs.need(span), ERROR_HIP_MALLOC);
+            HIPC(hipMemcpyAsync(d_sn_rhs.a, g, sizeof(double) * span, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+            rhs = d_sn_rhs.a;
+        }
+        code = plain ? solve(lambda, rhs, nrhs, ld, on_device) : solve_transpose_many(lambda, rhs, nrhs, ld, on_device);
+    }
+    if (code != SUCCESSFUL_EXIT || !grad) return code;
+    return values_outer(grad, lambda, x, nrhs, ld, ld, -1.0, beta, mapped, on_device);
+}
+
+int32_t Solver::set_complex_pattern(int64_t nnzc, const std::vector<int32_t> &zrow, const std::vector<int32_t> &zcol, bool sym) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (nnzc < 1 || (int64_t)zrow.size() != nnzc || (int64_t)zcol.size() != nnzc) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    sn_znnz = 0;
+    HIPC(d_sn_zrow.upload(zrow), ERROR_HIP_MALLOC);
+    HIPC(d_sn_zcol.upload(zcol), ERROR_HIP_MALLOC);
+    sn_znnz = nnzc, sn_zsym = sym, sn_znin = 0;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::set_complex_value_map(int64_t nin, const std::vector<int32_t> &inv_ptr, const std::vector<int32_t> &inv_idx) {
+    if (sn_znnz < 1) return ERROR_NEED_INITIALIZATION;
+    sn_znin = 0;
+    if (nin < 1) return SUCCESSFUL_EXIT;
+    if ((int64_t)inv_ptr.size() != nin + 1) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    HIPC(d_sn_zinv_ptr.upload(inv_ptr), ERROR_HIP_MALLOC);
+    HIPC(d_sn_zinv_idx.upload(inv_idx), ERROR_HIP_MALLOC);
+    sn_znin = nin;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::values_outer_complex(double *grad, const double *u, const double *w, int32_t ncols, int64_t ldu, int64_t ldw, double alpha, double beta,
+                                     bool conjugate_w) {
+    if (!initialized || sn_znnz < 1) return ERROR_NEED_INITIALIZATION;
+    if (!grad || !u || !w) return ERROR_NULL_POINTER;
+    const int64_t nc = S.n / 2, nnzc = sn_znnz, nout = sn_znin > 0 ? sn_znin : nnzc;
+    if (ncols < 1 || ldu < nc || ldw < nc) return ERROR_HIPMF_INVALID_VALUE;
+    DeviceScope dev_scope(device);
+    if (!sn_ev0) HIPC(hipEventCreate(sn_ev0.put()), ERROR_HIPMF_NO_DEVICE);
+    if (!sn_ev1) HIPC(hipEventCreate(sn_ev1.put()), ERROR_HIPMF_NO_DEVICE);
+    const size_t nb = sizeof(double) * 2 * (size_t)nc, blk = 2 * (size_t)nc * ncols;
+    HIPC(d_sn_ops.need(2 * blk), ERROR_HIP_MALLOC);
+    HIPC(d_sn_out.need(2 * (size_t)nout), ERROR_HIP_MALLOC);
+    for (int32_t c = 0; c < ncols; c++) {
+        HIPC(hipMemcpyAsync(d_sn_ops.a + 2 * (size_t)c * nc, u + 2 * (int64_t)c * ldu, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipMemcpyAsync(d_sn_ops.a + blk + 2 * (size_t)c * nc, w + 2 * (int64_t)c * ldw, nb, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    }
+    if (beta != 0.0) HIPC(hipMemcpyAsync(d_sn_out.a, grad, sizeof(double) * 2 * (size_t)nout, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    const double *du = d_sn_ops.a, *dw = d_sn_ops.a + blk;
+    double *dout = d_sn_out.a, *dslot = dout;
+    const bool via = sn_znin > 0;
+    if (via) {
+        HIPC(d_sn_slot.need(2 * (size_t)nnzc), ERROR_HIP_MALLOC);
+        dslot = d_sn_slot.a;
+    }
+    const double beta_outer = via ? 0.0 : beta;
+    const dim3 gz = sens_grid(nnzc), b256(256);
+    HIPC(hipEventRecord((hipEvent_t)sn_ev0, STREAM), ERROR_HIP_SYNCHRONIZE);
+    auto outer = [&](auto kernel) { hipLaunchKernelGGL(kernel, gz, b256, 0, STREAM, nnzc, (const int32_t *)d_sn_zrow, (const int32_t *)d_sn_zcol, du, nc, dw, nc, ncols, alpha, beta_outer, dslot); };
+    if (sn_zsym) conjugate_w ? outer(k_zsens_outer<true, true>) : outer(k_zsens_outer<true, false>);
+    else conjugate_w ? outer(k_zsens_outer<false, true>) : outer(k_zsens_outer<false, false>);
+    if (via) hipLaunchKernelGGL(k_zsens_scatter, sens_grid(nout), b256, 0, STREAM, nout, (const int32_t *)d_sn_zinv_ptr, (const int32_t *)d_sn_zinv_idx, (const double *)dslot, beta, dout);
+    HIPC(hipEventRecord((hipEvent_t)sn_ev1, STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipMemcpyAsync(grad, dout, sizeof(double) * 2 * (size_t)nout, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, (hipEvent_t)sn_ev0, (hipEvent_t)sn_ev1);
+    sens_outer_ms = ms;
+    sens_outer_columns += ncols;
+    return SUCCESSFUL_EXIT;
+}
+
 int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (nnz_lower < 1 || (int64_t)emap.size() != S.nnz_a) return ERROR_HIPMF_INVALID_VALUE;
@@ -4532,6 +4773,7 @@ int32_t Solver::set_expansion(int64_t nnz_lower, const std::vector<int32_t> &ema
     HIPC(d_emap.upload(emap), ERROR_HIP_MALLOC);
     HIPC(d_vlow.alloc((size_t)nnz_lower), ERROR_HIP_MALLOC);
     nnz_low = nnz_lower;
+    sn_exp_ready = false;
     if (&emap != &h_emap) h_emap = emap;
     return SUCCESSFUL_EXIT;
 }

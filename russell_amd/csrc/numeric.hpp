@@ -232,10 +232,26 @@ struct SolverBorder {
     int32_t bd_cols = 0, bd_small_kp = 0; // columns and border width the blocks of solve_bordered are allocated for (0: not allocated)
 };
 
+// solver_hipmf_values_outer / _solve_tangent / _solve_adjoint (kernels_sensitivity.hpp).  The inverse maps input -> CSR slots (pointer and
+// slot list) that carry a slot gradient to the caller's value order: one for the value map (built at the first mapped call from
+// h_seg_ptr / h_seg_idx; set_value_map marks it stale), one for the expansion of a symmetric-lower matrix (from h_emap).  The complex
+// twin's pattern (row and column of every stored complex entry) and the inverse of its triplet map come from its interface.  Staging
+// that only grows: the slot gradients, the caller-ordered gradient and the operand columns of a host-pointer call, the right-hand
+// sides and solutions of a tangent solve, the partial sums its residual kernel writes.
+struct SolverSensitivity {
+    bool sn_map_ready = false, sn_exp_ready = false;
+    DeviceArray<int32_t> d_sn_map_ptr, d_sn_map_idx, d_sn_exp_ptr, d_sn_exp_idx;
+    DeviceArray<int32_t> d_sn_zrow, d_sn_zcol, d_sn_zinv_ptr, d_sn_zinv_idx;
+    int64_t sn_znnz = 0, sn_znin = 0; // stored complex entries; triplets of the complex value map (0: none installed)
+    bool sn_zsym = false;
+    SolverPruned::Growing<double> d_sn_slot, d_sn_out, d_sn_ops, d_sn_rhs, d_sn_part;
+    EventOwner sn_ev0, sn_ev1; // around the outer and scatter kernels of a call
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise, SolverBorder {
+struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise, SolverBorder, SolverSensitivity {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -452,6 +468,34 @@ class Solver : public SolverDevice, public Tunables {
                            bool on_device);
     void drop_border(); // frees the border's device memory
     int64_t bordered_steps = 0, bordered_blocks = 0; // of the last solve_bordered: block steps summed over the blocks, 16-column blocks
+    // Sensitivities with respect to the matrix values (kernels_sensitivity.hpp).  The pattern-restricted outer product
+    //   grad = beta grad + alpha sum_c u_c w_c^T |pattern
+    // in the order of the values the caller hands to factorize (mapped = false: its CSR order, a symmetric-lower handle its lower
+    // triangle, also when the handle expanded it) or to factorize_mapped (mapped = true: the inputs of the value map).  u, w:
+    // column-major ldu x ncols, ldw x ncols.  Needs initialize only.  One fixed chain of fma per entry: the same bits from host and
+    // device pointers, from call to call and on every device.
+    int32_t values_outer(double *grad, const double *u, const double *w, int32_t ncols, int64_t ldu, int64_t ldw, double alpha, double beta, bool mapped,
+                         bool on_device);
+    // dx = A^{-1} (db - dA x) for the matrix dA that dvalues describe (values / mapped as above; db nullptr: zero): dvalues are staged
+    // in the operator's value buffer of the solve_updated forms, the right-hand sides come from their blocked residual kernel, the
+    // solve is solve() with the handle's refinement.  d_vals, the factor and the statistics of the ordinary solves stay as they were.
+    int32_t solve_tangent(double *dx, const double *x, const double *dvalues, const double *db, int32_t nrhs, int64_t ld, bool mapped, bool on_device);
+    // lambda = A^{-T} g by solve_transpose_many (A^T = A: solve), then grad = beta grad - sum_c lambda_c x_c^T |pattern by ONE
+    // values_outer over all nrhs columns (grad nullptr: only the solve).  lambda may be g.  symmetric_matrix: a symmetric matrix that
+    // the interface expanded to general storage (A^T = A).  The statistics of the ordinary and of the transposed solves stay as they were.
+    int32_t solve_adjoint(double *lambda, double *grad, const double *x, const double *g, int32_t nrhs, int64_t ld, double beta, bool mapped, bool on_device,
+                          bool symmetric_matrix = false);
+    // The complex twin (this handle holds the real-equivalent system of order 2 nc; host pointers, interleaved (re, im)):
+    // set_complex_pattern: row and column of every stored complex entry (sym: the lower triangle of a complex-symmetric matrix);
+    // set_complex_value_map: the inverse of the triplet map, triplet -> stored entries (nin = 0: none, the values are the stored entries)
+    int32_t set_complex_pattern(int64_t nnzc, const std::vector<int32_t> &zrow, const std::vector<int32_t> &zcol, bool sym);
+    int32_t set_complex_value_map(int64_t nin, const std::vector<int32_t> &inv_ptr, const std::vector<int32_t> &inv_idx);
+    bool complex_pattern_set() const { return sn_znnz > 0; }
+    // grad = beta grad + alpha sum_c u_c op(w_c)^T |pattern on complex entries, op = conj with conjugate_w; ldu, ldw in complex elements
+    int32_t values_outer_complex(double *grad, const double *u, const double *w, int32_t ncols, int64_t ldu, int64_t ldw, double alpha, double beta,
+                                 bool conjugate_w);
+    int64_t sens_outer_columns = 0; // columns summed by the outer products of this handle, over all calls
+    double sens_outer_ms = 0.0;     // HIP-event time of the outer and scatter kernels of the last such call
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
     int64_t transposed_solves = 0;   // solve_transpose calls that solved (columns)
     int64_t analysis_solves = 0;     // pass pairs of the last error analysis (condition estimates)
