@@ -388,6 +388,34 @@ int32_t solver_hipmf_solve_bordered(struct InterfaceHIPMF *solver, double *x, do
 int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *solver, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs, int32_t ldx,
                                            int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
 
+/* THE TRANSPOSED BORDERED SYSTEM with the border that solver_hipmf_set_border put in force:
+ *     [ A^T  C   ] [y]   [p]
+ *     [ B^T  D^T ] [w] = [q]      M^T of the system above
+ * -- the left vector of fold and branch-point continuation with bordering (M v = e and M^T w = e in every step; the derivatives of the
+ * test function are then ONE solver_hipmf_values_outer call, -w^T A_alpha v), and the discrete adjoint of anything computed with
+ * solver_hipmf_solve_bordered: M^T [lambda; mu] = [dJ/dx; dJ/dz] (solver_hipmf_solve_adjoint covers A alone).
+ * The arguments, info (4 doubles per column: steps, omega, omega before the first step, state), max_steps <= 0 -> 4, w == NULL /
+ * q == NULL and the status codes are exactly those of solver_hipmf_solve_bordered.  Per block of up to 16 columns
+ *   y0 <- one unrefined blocked TRANSPOSED pass pair of p, t <- q - B^T y0, w <- S^{-T} t, y <- y0 - V w,   V = A^{-T} C,
+ * with the SAME S = D - C^T A^{-1} B (S^T = D^T - B^T V): its kept LU is solved transposed.  Then the same refinement on all ndim + k
+ * rows of M^T, the residual accumulated beyond twice the working precision and rounded once, the same stopping rule column by column.
+ * V and a packed D^T are built at the FIRST transposed call after a set_border (k refined transposed solves, 16 per block) and kept
+ * until the border is dropped; a handle that never makes the call allocates and launches nothing for it.  A symmetric-lower handle
+ * keeps its L D L^T factor here too (there A^T = A, but M^T != M unless B = C and D = D^T).
+ * NO SIDE EFFECTS on any counter, statistic or timer of the other solves (HIPMF_COUNTER_BORDERED_STEPS / _BLOCKS included) or the bits
+ * of a later solve; bit-reproducible; the host and _device forms give the same bits.
+ * HIPMF_COUNTER_BORDERED_TRANSPOSED_STEPS / _BLOCKS report the last call, HIPMF_COUNTER_BORDER_TRANSPOSED_BYTES the device memory held
+ * for V and D^T (0 until the first call).
+ * WHAT IT COSTS (tools/bordered_transpose.py, one MI355X, 1M unknowns, profiles/r22_bordered_transpose.txt; one step after the start):
+ * one column 3.30 / 3.72 / 6.05 ms for k = 1 / 16 / 64 (the first call after a set_border 6.4 / 11.9 / 40.2 ms); 16 columns 9.3 / 10.1 /
+ * 18.7 ms against 7.3 / 12.4 / 37.2 ms for solver_hipmf_solve_bordered_device -- the residual of the transposed form takes the block's
+ * columns four at a time.  k = 1 on host vectors: 3.89 ms against 6.76 ms for two solve_transpose calls, two inner products and the
+ * combination by hand.  A symmetric-lower handle costs what the plain form costs. */
+int32_t solver_hipmf_solve_bordered_transpose(struct InterfaceHIPMF *solver, double *y, double *w, const double *p, const double *q, int32_t nrhs, int32_t ldx,
+                                              int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
+int32_t solver_hipmf_solve_bordered_transpose_device(struct InterfaceHIPMF *solver, double *d_y, double *d_w, const double *d_p, const double *d_q, int32_t nrhs,
+                                                     int32_t ldx, int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
+
 /* SENSITIVITIES of the solve with respect to the matrix VALUES: tangent (forward) and adjoint (reverse) mode.
  * For J = J(x) with A x = b:  forward,  dx = A^{-1} (db - dA x);  reverse, with g = dJ/dx:  lambda = A^{-T} g = dJ/db  and
  *   dJ/da_ij = -lambda_i x_j  on the sparsity pattern, summed over the right-hand sides,
@@ -562,6 +590,9 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_BORDERED_BLOCKS 46            /* 16-column blocks of that call */
 #define HIPMF_COUNTER_SENS_OUTER_COLUMNS 47         /* columns summed by the pattern-restricted outer products of this handle (solver_hipmf_values_outer / _device, the gradients of solver_hipmf_solve_adjoint / _device; the complex twin's calls), over all calls */
 #define HIPMF_COUNTER_SENS_OUTER_US 48              /* microseconds between HIP events around the outer and scatter kernels of the last such call */
+#define HIPMF_COUNTER_BORDERED_TRANSPOSED_STEPS 49  /* refinement steps of the last solver_hipmf_solve_bordered_transpose / _device, summed over its blocks */
+#define HIPMF_COUNTER_BORDERED_TRANSPOSED_BLOCKS 50 /* 16-column blocks of that call */
+#define HIPMF_COUNTER_BORDER_TRANSPOSED_BYTES 51    /* device bytes held for the transposed side of the border (V = A^{-T} C, D^T): 0 until the first transposed call */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

@@ -70,6 +70,10 @@ SYMBOLS = {
                                                 C.c_int32]),
     "solver_hipmf_solve_bordered_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                        C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_bordered_transpose": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                          C.c_void_p, C.c_int32]),
+    "solver_hipmf_solve_bordered_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                                 C.c_int32, C.c_void_p, C.c_int32]),
     "solver_hipmf_values_outer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32]),
     "solver_hipmf_values_outer_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                                      C.c_int32]),

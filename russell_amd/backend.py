@@ -263,6 +263,14 @@ class Hipmf:
         """[A B; C^T D] [x; z] = [f; g] with the border of set_border, refined on the whole system (solver_hipmf_solve_bordered).
         f: (n,) or (nrhs, ldx) as solve_many takes it; g: (k,) or (nrhs, ldz), None: g = 0; want_z False: z is not returned.
         x / z: arrays of those shapes to write into (their padding is left alone).  Returns (x, z or None, info of shape (nrhs, 4))."""
+        return self._solve_bordered("solver_hipmf_solve_bordered", f, g, want_z, max_steps, ldx, ldz, verbose, x, z)
+
+    def solve_bordered_transpose(self, p, q=None, want_w=True, max_steps=0, ldx=None, ldz=None, verbose=False, y=None, w=None):
+        """[A^T C; B^T D^T] [y; w] = [p; q], the transpose of solve_bordered's system with the same border
+        (solver_hipmf_solve_bordered_transpose).  Arguments and results as solve_bordered: returns (y, w or None, info)."""
+        return self._solve_bordered("solver_hipmf_solve_bordered_transpose", p, q, want_w, max_steps, ldx, ldz, verbose, y, w)
+
+    def _solve_bordered(self, entry, f, g, want_z, max_steps, ldx, ldz, verbose, x, z):
         k = self.counter("border_columns")
         fa = np.ascontiguousarray(f, dtype=np.float64)
         single = fa.ndim == 1
@@ -274,10 +282,10 @@ class Hipmf:
         x = np.zeros((nrhs, ldx)) if x is None else x
         z = (np.zeros((nrhs, max(ldz, 1))) if z is None else z) if want_z else None
         info = np.zeros((nrhs, 4))
-        code = self.lib.solver_hipmf_solve_bordered(self.h, x.ctypes.data, None if z is None else z.ctypes.data, fa.ctypes.data, None if ga is None else ga.ctypes.data,
-                                                    nrhs, ldx, ldz, int(max_steps), info.ctypes.data, int(verbose))
+        code = getattr(self.lib, entry)(self.h, x.ctypes.data, None if z is None else z.ctypes.data, fa.ctypes.data, None if ga is None else ga.ctypes.data, nrhs, ldx,
+                                        ldz, int(max_steps), info.ctypes.data, int(verbose))
         if code != 0:
-            raise self._err(code, "solver_hipmf_solve_bordered")
+            raise self._err(code, entry)
         if single:
             return x[0], (None if z is None else z[0]), info[0]
         return x, z, info
@@ -364,7 +372,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48, "bordered_transposed_steps": 49, "bordered_transposed_blocks": 50, "border_transposed_bytes": 51}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -503,6 +511,16 @@ class Hipmf:
                                                            int(max_steps), info.ctypes.data, 0)
         if code != 0:
             raise self._err(code, "solver_hipmf_solve_bordered_device")
+        return info[:nrhs]
+
+    def solve_bordered_transpose_device(self, d_y, d_w, d_p, d_q, nrhs=1, max_steps=0, ldx=None, ldz=None):
+        """solve_bordered_transpose with y, p (column-major ldx x nrhs) and w, q (ldz x nrhs; None allowed) resident on the device; returns info"""
+        nrhs = int(nrhs)
+        info = np.zeros((max(nrhs, 1), 4))
+        code = self.lib.solver_hipmf_solve_bordered_transpose_device(self.h, d_y, d_w, d_p, d_q, nrhs, int(ldx or self.n),
+                                                                     int(ldz or max(self.counter("border_columns"), 1)), int(max_steps), info.ctypes.data, 0)
+        if code != 0:
+            raise self._err(code, "solver_hipmf_solve_bordered_transpose_device")
         return info[:nrhs]
 
     def values_outer_device(self, d_grad, d_u, d_w, ncols=1, alpha=1.0, beta=0.0, mapped=False, ldu=None, ldw=None):

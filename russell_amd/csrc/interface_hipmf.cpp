@@ -721,15 +721,17 @@ int32_t solver_hipmf_set_border_device(struct InterfaceHIPMF *h, int32_t k, cons
 }
 
 static int32_t solve_bordered_body(struct InterfaceHIPMF *h, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx, int32_t ldz,
-                                   int32_t max_steps, double *info, C_BOOL verbose, bool on_device, const char *who) {
+                                   int32_t max_steps, double *info, C_BOOL verbose, bool on_device, const char *who, bool transposed = false) {
     if (!h || !x || !f) return ERROR_NULL_POINTER;
     if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
     if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
-    h->solver.opt.verbose = verbose == 1;
-    const int32_t code = h->solver.solve_bordered(x, z, f, g, nrhs, ldx, ldz, max_steps, info, on_device);
+    Solver &s = h->solver;
+    s.opt.verbose = verbose == 1;
+    const int32_t code = transposed ? s.solve_bordered_transpose(x, z, f, g, nrhs, ldx, ldz, max_steps, info, on_device)
+                                    : s.solve_bordered(x, z, f, g, nrhs, ldx, ldz, max_steps, info, on_device);
     if (verbose == 1 && code == SUCCESSFUL_EXIT)
-        printf("%s: %d column(s), border of %d: %lld block step(s) in %lld block(s)\n", who, nrhs, h->solver.bd_k, (long long)h->solver.bordered_steps,
-               (long long)h->solver.bordered_blocks);
+        printf("%s: %d column(s), border of %d: %lld block step(s) in %lld block(s)\n", who, nrhs, s.bd_k, (long long)(transposed ? s.bordered_t_steps : s.bordered_steps),
+               (long long)(transposed ? s.bordered_t_blocks : s.bordered_blocks));
     return code;
 }
 
@@ -741,6 +743,19 @@ int32_t solver_hipmf_solve_bordered(struct InterfaceHIPMF *h, double *x, double 
 int32_t solver_hipmf_solve_bordered_device(struct InterfaceHIPMF *h, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs, int32_t ldx,
                                            int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose) {
     return guarded(h, [&]() { return solve_bordered_body(h, d_x, d_z, d_f, d_g, nrhs, ldx, ldz, max_steps, info, verbose, true, "solver_hipmf_solve_bordered_device"); });
+}
+
+// the transposed system [A^T C; B^T D^T] [y; w] = [p; q] with the same border: the argument rules and status codes above
+int32_t solver_hipmf_solve_bordered_transpose(struct InterfaceHIPMF *h, double *y, double *w, const double *p, const double *q, int32_t nrhs, int32_t ldx, int32_t ldz,
+                                              int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() { return solve_bordered_body(h, y, w, p, q, nrhs, ldx, ldz, max_steps, info, verbose, false, "solver_hipmf_solve_bordered_transpose", true); });
+}
+
+int32_t solver_hipmf_solve_bordered_transpose_device(struct InterfaceHIPMF *h, double *d_y, double *d_w, const double *d_p, const double *d_q, int32_t nrhs, int32_t ldx,
+                                                     int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return solve_bordered_body(h, d_y, d_w, d_p, d_q, nrhs, ldx, ldz, max_steps, info, verbose, true, "solver_hipmf_solve_bordered_transpose_device", true);
+    });
 }
 
 // Sensitivities with respect to the matrix values (Solver::values_outer, solve_tangent, solve_adjoint; kernels_sensitivity.hpp).  Status
@@ -921,6 +936,9 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_BORDERED_BLOCKS: return s.bordered_blocks;
     case HIPMF_COUNTER_SENS_OUTER_COLUMNS: return s.sens_outer_columns;
     case HIPMF_COUNTER_SENS_OUTER_US: return (int64_t)(1e3 * s.sens_outer_ms);
+    case HIPMF_COUNTER_BORDERED_TRANSPOSED_STEPS: return s.bordered_t_steps;
+    case HIPMF_COUNTER_BORDERED_TRANSPOSED_BLOCKS: return s.bordered_t_blocks;
+    case HIPMF_COUNTER_BORDER_TRANSPOSED_BYTES: return s.bt_bytes;
     default: return -1;
     }
 }

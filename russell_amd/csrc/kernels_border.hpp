@@ -24,6 +24,13 @@
 //                  SAVE = OUT, OUT = OUT + (Y - P Z).
 // k_border_residual_n, k_border_rows_part, k_border_rows  the residual of all n + k rows, accumulated beyond twice the working
 //                  precision and rounded once, with the denominators and the omegas of solve()'s stopping rule (see there).
+// The transposed form (solver_hipmf_solve_bordered_transpose; Solver::solve_bordered_transpose): [A^T C; B^T D^T] [y; w] = [p; q] with
+// V = A^{-T} C and the SAME S (S^T = D^T - B^T V), so the LU above serves.  The Gram, apply and border-row kernels are reused with the
+// operands swapped (B for C, V for W, the packed D^T for D); what is new:
+// k_border_unpack  column-major columns back out of a packed array (the right-hand sides of V = A^{-T} C)
+// k_border_small_solve_t  t = q - G, dw = S^{-T} t from the same LU: U^T forward, L^T backward, the row exchanges undone in reverse
+// k_border_residual_nt  the n rows of M^T through the rows of A^T (tptr / trow / tmap of the transposed solves), the block's columns
+//                  BORDER_RT at a time: a thread reads its row of A^T and of C once per tile of columns instead of once per column
 // Columns whose bit in `mask` is clear are finished: a residual column is zeros (it rides along through the next pass pair), a correction
 // leaves x and z of such a column alone.
 // Traffic per launch, in bytes: gram 8 n (kp + m); apply 8 n (kp + 2 m), with SAVE 8 n (kp + 4 m); the residual of the n rows one pass
@@ -377,6 +384,146 @@ __global__ void __launch_bounds__(64) k_border_rows(int32_t k, int32_t kp, int32
         double mx = 0.0;
         for (int i = 0; i < k; i++) mx = qs[i] > mx ? qs[i] : mx;
         omega[c] = mx;
+    }
+}
+
+// ---- the transposed form ----
+
+// dst[i + j ld] = src[i kp + j0 + j], j < ncols: k_border_pack backwards
+__global__ void __launch_bounds__(256) k_border_unpack(int32_t n, int32_t ncols, int32_t kp, int32_t j0, const double *__restrict__ src, double *__restrict__ dst,
+                                                       int64_t ld) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = e / ncols;
+    const int j = (int)(e - i * ncols);
+    if (i < n) dst[i + (int64_t)j * ld] = src[i * kp + j0 + j];
+}
+
+// One wavefront per column c (grid m): dw = S^{-T} (q - G) from the LU of k_border_lu (P S = L U, so S^T = U^T L^T P): U^T forward, L^T
+// backward with its unit diagonal, then the row exchanges undone in reverse order.  zs, mask and the zero padding: k_border_small_solve.
+__global__ void __launch_bounds__(64) k_border_small_solve_t(int32_t k, int32_t kp, const double *__restrict__ LU, const int32_t *__restrict__ piv,
+                                                             const double *__restrict__ g, const double *__restrict__ G, double *__restrict__ dz,
+                                                             double *__restrict__ z, double *__restrict__ zs, uint32_t mask) {
+    __shared__ double t[BORDER_MAX];
+    const int c = blockIdx.x, j = threadIdx.x;
+    if (!((mask >> c) & 1u)) return;
+    const int64_t col = (int64_t)c * kp;
+    if (j < k) t[j] = g[col + j] - G[col + j];
+    __syncthreads();
+    for (int q = 0; q < k; q++) { // U^T a = t: row q of U is column q of U^T
+        if (j == q) t[q] = t[q] / LU[q + (int64_t)q * kp];
+        __syncthreads();
+        const double tq = t[q];
+        if (j > q && j < k) t[j] = fma(-LU[q + (int64_t)j * kp], tq, t[j]);
+        __syncthreads();
+    }
+    for (int q = k - 1; q > 0; q--) { // L^T b = a, unit diagonal
+        const double tq = t[q];
+        __syncthreads();
+        if (j < q) t[j] = fma(-LU[q + (int64_t)j * kp], tq, t[j]);
+        __syncthreads();
+    }
+    if (j == 0)
+        for (int q = k - 1; q >= 0; q--) {
+            const int r = piv[q];
+            if (r != q) {
+                const double v = t[q];
+                t[q] = t[r], t[r] = v;
+            }
+        }
+    __syncthreads();
+    if (j < kp) {
+        const double v = j < k ? t[j] : 0.0;
+        dz[col + j] = v;
+        if (zs) {
+            const double old = z[col + j];
+            zs[col + j] = old, z[col + j] = old + v;
+        } else {
+            z[col + j] = v;
+        }
+    }
+}
+
+// rows of A^T: one thread per row i, the columns of the block BORDER_RT at a time.  r = p - A^T y - C w, den = |A^T||y| + |C||w| + |p|,
+// omega as k_border_residual_n.  Row i of A^T is column i of A: entries vals[tmap[e]] in the rows trow[e], e in [tptr[i], tptr[i + 1]).
+// A tile of columns shares every load of the row -- value, map and row index of a stored entry, the k entries of the border row -- and
+// keeps one (sum, denominator) pair per column; within a column the additions come in the order p_i, the stored entries, j = 0 .. k - 1,
+// whatever the tile holds: the tiling changes no bit.  A column whose bit in `mask` is clear: r = 0, no omega.
+constexpr int BORDER_RT = 4;
+__global__ void __launch_bounds__(256) k_border_residual_nt(int32_t n, const int32_t *__restrict__ tptr, const int32_t *__restrict__ trow, const int32_t *__restrict__ tmap,
+                                                            const double *__restrict__ vals, int32_t k, int32_t kp, const double *__restrict__ Cp,
+                                                            const double *__restrict__ W, const double *__restrict__ y, int64_t ystr, const double *__restrict__ p,
+                                                            int64_t pstr, double *__restrict__ r, int64_t rstr, unsigned long long *nrm, int32_t ncols, uint32_t mask) {
+#pragma clang fp contract(off)
+    __shared__ double red[BORDER_RT][4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n;
+    const int e0 = in ? tptr[i] : 0, e1 = in ? tptr[i + 1] : 0;
+    const double *ci = Cp + (int64_t)(in ? i : 0) * kp;
+    for (int c0 = 0; c0 < ncols; c0 += BORDER_RT) { // (workgroup-uniform, as everything that depends on the mask alone)
+        const int nt = ncols - c0 < BORDER_RT ? ncols - c0 : BORDER_RT;
+        const uint32_t tm = (mask >> c0) & ((1u << nt) - 1u);
+        if (in)
+            for (int t = 0; t < nt; t++)
+                if (!((tm >> t) & 1u)) r[i + (int64_t)(c0 + t) * rstr] = 0.0;
+        if (!tm) continue;
+        double qi[BORDER_RT] = {0.0, 0.0, 0.0, 0.0};
+        if (in) {
+            XrSum acc[BORDER_RT];
+            double den[BORDER_RT];
+#pragma unroll
+            for (int t = 0; t < BORDER_RT; t++) {
+                const double pi = ((tm >> t) & 1u) ? p[i + (int64_t)(c0 + t) * pstr] : 0.0;
+                acc[t].s = pi, acc[t].c = 0.0, acc[t].cc = 0.0, den[t] = fabs(pi);
+            }
+            for (int e = e0; e < e1; e++) {
+                const double a = vals[tmap[e]];
+                const double *yj = y + trow[e];
+#pragma unroll
+                for (int t = 0; t < BORDER_RT; t++)
+                    if ((tm >> t) & 1u) {
+                        const double yv = yj[(int64_t)(c0 + t) * ystr];
+                        xr_dot_sub(acc[t], a, yv);
+                        den[t] += fabs(a * yv);
+                    }
+            }
+            for (int j = 0; j < k; j++) {
+                const double a = ci[j];
+                const double *wj = W + (int64_t)c0 * kp + j;
+#pragma unroll
+                for (int t = 0; t < BORDER_RT; t++)
+                    if ((tm >> t) & 1u) {
+                        const double wv = wj[(int64_t)t * kp];
+                        xr_dot_sub(acc[t], a, wv);
+                        den[t] += fabs(a * wv);
+                    }
+            }
+#pragma unroll
+            for (int t = 0; t < BORDER_RT; t++)
+                if ((tm >> t) & 1u) {
+                    const double ri = xr_round(acc[t]), ai = fabs(ri);
+                    r[i + (int64_t)(c0 + t) * rstr] = ri;
+                    const double q = den[t] > 0.0 ? ai / den[t] : (ai > 0.0 ? 1.0 : 0.0);
+                    qi[t] = q > 0.0 ? q : 0.0; // (a NaN never wins the maximum, as in spmv_block)
+                }
+        }
+#pragma unroll
+        for (int t = 0; t < BORDER_RT; t++)
+            for (int off = 32; off > 0; off >>= 1) {
+                const double other = __shfl_xor(qi[t], off);
+                qi[t] = other > qi[t] ? other : qi[t];
+            }
+        __syncthreads(); // (the maxima of the tile before have been read)
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int t = 0; t < BORDER_RT; t++) red[t][threadIdx.x >> 6] = qi[t];
+        }
+        __syncthreads();
+        if (threadIdx.x < BORDER_RT && ((tm >> threadIdx.x) & 1u)) {
+            const int t = threadIdx.x;
+            double mx = red[t][0];
+            for (int w = 1; w < 4; w++) mx = red[t][w] > mx ? red[t][w] : mx;
+            atomicMax(nrm + (size_t)(c0 + t) * RES_NORM_WORDS + (size_t)(blockIdx.x & (RES_SLOTS - 1)) * RES_SLOT_WORDS + 1, (unsigned long long)__double_as_longlong(mx));
+        }
     }
 }
 

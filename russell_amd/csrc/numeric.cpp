@@ -2056,7 +2056,7 @@ int32_t Solver::run_factor() {
     const int32_t n = S.n;
     const int64_t nnz = S.nnz_a;
     int64_t launches = 0;
-    bd_k = 0; // (a border belongs to the factorisation it was set for: Solver::set_border)
+    forget_border(); // (a border belongs to the factorisation it was set for: Solver::set_border)
     HIPC(hipEventRecord((hipEvent_t)ev[0], STREAM), ERROR_HIP_SYNCHRONIZE);
     // (with a matching in force the scalings dr, dc of initialize stay: the structure was chosen for them)
     if (!matched)
@@ -4399,8 +4399,14 @@ int32_t Solver::set_border(int32_t k, const double *B, int64_t ldb, const double
     return SUCCESSFUL_EXIT;
 }
 
-int32_t Solver::solve_bordered(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
-                               bool on_device) {
+// The transposed form, [A^T C; B^T D^T] [y; w] = [p; q] (T of bordered_core), is the same loop with the operands swapped: V = A^{-T} C for W
+// and the transposed pass pair for the plain one (bt_pass), B for C in the Gram product and the border rows, S^T = D^T - B^T V through the
+// LU of S (k_border_small_solve_t), the packed D^T for D, and the n rows of the residual through the rows of A^T, the block's columns four
+// at a time (k_border_residual_nt; on a handle where A^T = A, k_border_residual_n with C for B).  V and D^T are built at the first
+// transposed call after a set_border (bt_prepare).  With T false nothing is allocated or launched that the plain form did not before.
+template <bool T>
+int32_t Solver::bordered_core(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                              bool on_device) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !f) return ERROR_NULL_POINTER;
@@ -4409,9 +4415,19 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
     DeviceScope dev_scope(device);
     const double EPS = 2.220446049250313e-16;
     const int32_t limit = max_steps > 0 ? max_steps : 4;
-    bordered_steps = bordered_blocks = 0;
+    int64_t &steps_done = T ? bordered_t_steps : bordered_steps, &blocks_done = T ? bordered_t_blocks : bordered_blocks;
+    steps_done = blocks_done = 0;
     if (info)
         for (int64_t q = 0; q < 4 * (int64_t)nrhs; q++) info[q] = 0.0;
+    if (T) {
+        const int32_t code = bt_prepare();
+        if (code != SUCCESSFUL_EXIT) return code;
+    }
+    const bool a_is_at = S.sym_mode || d_tptr; // A^T = A: the plain pass pair and the plain rows serve the transposed form
+    // what the elimination multiplies with (the Gram product and the border rows; the correction), and the small diagonal block
+    const double *const d_gram = T ? (const double *)d_bd_B : (const double *)d_bd_C, *const d_corr = T ? (const double *)d_bt_V : (const double *)d_bd_W;
+    const double *const d_diag = T ? (const double *)d_bt_Dt : (const double *)d_bd_D;
+    const double *const d_side = T ? (const double *)d_bd_C : (const double *)d_bd_B; // the border columns in the first n rows
     const int32_t C = std::min(nrhs, BORDER_COLS);
     const size_t tile = (size_t)kp * BORDER_COLS;
     if (bd_cols < C || bd_small_kp != kp) {
@@ -4434,7 +4450,7 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
     guard.unrefined_quiet();
     for (int32_t j0 = 0; j0 < nrhs; j0 += BORDER_COLS) {
         const int32_t nk = std::min(BORDER_COLS, nrhs - j0);
-        bordered_blocks++;
+        blocks_done++;
         double *const xb = on_device ? x + (int64_t)j0 * ldx : d_bd_vec + 3 * blk;
         const double *const fb = on_device ? f + (int64_t)j0 * ldx : d_bd_vec + 4 * blk;
         HIPC(hipMemsetAsync(d_bd_small, 0, sizeof(double) * 6 * tile, STREAM), ERROR_HIP_MEMCPY); // (the rows k .. kp - 1 stay zero: g = 0 without a g)
@@ -4450,25 +4466,34 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
 
         // (dx, dz) of the residual (rf, rg), dx = y - W dz with y left in ydst by the pass pair; fresh: (x, z) <- (dx, dz), else (x, z) += (dx, dz)
         auto eliminate = [&](double *ydst, int64_t ystr, const double *rf, const double *rg, bool fresh) -> int32_t {
-            const int32_t code = solve_core(ydst, rf, nk, ystr, true);
+            const int32_t code = T ? bt_pass(ydst, ystr, rf, ystr, nk) : solve_core(ydst, rf, nk, ystr, true);
             if (code != SUCCESSFUL_EXIT) return code;
-            hipLaunchKernelGGL(k_border_gram, gg, b64, 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)ydst, ystr, nk, (double *)d_bd_part);
+            hipLaunchKernelGGL(k_border_gram, gg, b64, 0, STREAM, n, kp, d_gram, (const double *)ydst, ystr, nk, (double *)d_bd_part);
             hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, nch, kp, (const double *)d_bd_part, d_G);
-            hipLaunchKernelGGL(k_border_small_solve, dim3((unsigned)nk), b64, 0, STREAM, k, kp, (const double *)d_bd_LU, (const int32_t *)d_bd_piv, rg, (const double *)d_G,
-                               d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
-            hipLaunchKernelGGL(k_border_apply, gt, b256, 0, STREAM, n, k, kp, (const double *)d_bd_W, (const double *)d_DZ, nk, mask, (const double *)ydst, ystr, xb, stride,
+            if (T) {
+                hipLaunchKernelGGL(k_border_small_solve_t, dim3((unsigned)nk), b64, 0, STREAM, k, kp, (const double *)d_bd_LU, (const int32_t *)d_bd_piv, rg,
+                                   (const double *)d_G, d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
+            } else {
+                hipLaunchKernelGGL(k_border_small_solve, dim3((unsigned)nk), b64, 0, STREAM, k, kp, (const double *)d_bd_LU, (const int32_t *)d_bd_piv, rg,
+                                   (const double *)d_G, d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
+            }
+            hipLaunchKernelGGL(k_border_apply, gt, b256, 0, STREAM, n, k, kp, d_corr, (const double *)d_DZ, nk, mask, (const double *)ydst, ystr, xb, stride,
                                fresh ? (double *)nullptr : d_XS, (int64_t)n);
             return SUCCESSFUL_EXIT;
         };
         // the residual of (x, z) over all n + k rows into (d_R, d_RG), the omegas of the columns of the mask to the host
         auto measure = [&]() -> int32_t {
             HIPC(hipMemsetAsync(d_nrm, 0, nrm_words * sizeof(unsigned long long), STREAM), ERROR_HIP_MEMCPY);
-            hipLaunchKernelGGL(k_border_residual_n, dim3((unsigned)((n + 255) / 256)), b256, 0, STREAM, n, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, k, kp,
-                               (const double *)d_bd_B, (const double *)d_Z, (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
-            hipLaunchKernelGGL(k_border_rows_part, dim3((unsigned)nch, (unsigned)nk), b256, 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)xb, stride, mask,
-                               (double *)d_bd_part);
-            hipLaunchKernelGGL(k_border_rows, dim3((unsigned)nk), b64, 0, STREAM, k, kp, nch, (const double *)d_bd_D, (const double *)d_GG, (const double *)d_bd_part,
-                               (const double *)d_Z, d_RG, d_omega_g, mask);
+            if (T && !a_is_at) {
+                hipLaunchKernelGGL(k_border_residual_nt, dim3((unsigned)((n + 255) / 256)), b256, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, k, kp, d_side,
+                                   (const double *)d_Z, (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
+            } else {
+                hipLaunchKernelGGL(k_border_residual_n, dim3((unsigned)((n + 255) / 256)), b256, 0, STREAM, n, d_rp, d_ci, d_vals, d_tptr, d_tidx, d_arow, k, kp, d_side,
+                                   (const double *)d_Z, (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
+            }
+            hipLaunchKernelGGL(k_border_rows_part, dim3((unsigned)nch, (unsigned)nk), b256, 0, STREAM, n, kp, d_gram, (const double *)xb, stride, mask, (double *)d_bd_part);
+            hipLaunchKernelGGL(k_border_rows, dim3((unsigned)nk), b64, 0, STREAM, k, kp, nch, d_diag, (const double *)d_GG, (const double *)d_bd_part, (const double *)d_Z,
+                               d_RG, d_omega_g, mask);
             HIPC(hipMemcpyAsync(h_bd_nrm, d_nrm, nrm_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
             HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
             return SUCCESSFUL_EXIT;
@@ -4489,7 +4514,7 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
                 if (!q.active) continue;
                 double omega = h_omega_g[c];
                 for (int32_t sl = 0; sl < RES_SLOTS; sl++) omega = std::max(omega, h_bd_nrm[(size_t)RES_NORM_WORDS * c + (size_t)sl * RES_SLOT_WORDS + 1]);
-                if (guard.verbose && j0 + c == 0) fprintf(stderr, "hipmf: solve_bordered: after %d step(s): omega = %.3e\n", it, omega);
+                if (guard.verbose && j0 + c == 0) fprintf(stderr, "hipmf: %s: after %d step(s): omega = %.3e\n", T ? "solve_bordered_transpose" : "solve_bordered", it, omega);
                 if (it == 0) q.omega0 = omega;
                 if (it > 0 && !(omega < q.prev)) { // the step did not lower omega: taken back
                     HIPC(hipMemcpyAsync(xb + (int64_t)c * stride, d_XS + (size_t)c * n, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
@@ -4509,7 +4534,7 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
             if (!mask) break;
             code = eliminate(d_Y, (int64_t)n, d_R, d_RG, false);
             if (code != SUCCESSFUL_EXIT) return code;
-            bordered_steps++;
+            steps_done++;
         }
         for (int32_t c = 0; c < nk; c++) {
             const Column &q = col[c];
@@ -4524,6 +4549,11 @@ int32_t Solver::solve_bordered(double *x, double *z, const double *f, const doub
     }
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::solve_bordered(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                               bool on_device) {
+    return bordered_core<false>(x, z, f, g, nrhs, ldx, ldz, max_steps, info, on_device);
 }
 
 // ---- sensitivities with respect to the matrix values (kernels_sensitivity.hpp) ----
@@ -4701,6 +4731,74 @@ int32_t Solver::solve_adjoint(double *lambda, double *grad, const double *x, con
     return values_outer(grad, lambda, x, nrhs, ld, ld, -1.0, beta, mapped, on_device);
 }
 
+// ---- the transposed bordered system (the loop: bordered_core above) ----
+
+int32_t Solver::solve_bordered_transpose(double *y, double *w, const double *p, const double *q, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                                         bool on_device) {
+    return bordered_core<true>(y, w, p, q, nrhs, ldx, ldz, max_steps, info, on_device);
+}
+
+// V = A^{-T} C by the handle's refined transposed solves, 16 columns per block, as W = A^{-1} B came from solve() -- nothing of the
+// caller's statistics moves, plain or transposed --, packed as W is; D^T packed as D is (k_border_pack reads a column-major k x k array
+// into a row-major one: the transpose).  Also the rows of A^T and the buffers of the transposed pass pair (tr_prepare,
+// tr_prepare_blocked), which a handle where A^T = A does not need.
+int32_t Solver::bt_prepare() {
+    if (bt_ready) return SUCCESSFUL_EXIT;
+    const int32_t n = S.n, k = bd_k, kp = bd_kp;
+    const size_t npk = (size_t)n * kp, kk2 = (size_t)kp * kp;
+    const dim3 b256(256);
+    if (!(S.sym_mode || d_tptr)) {
+        const int32_t code = tr_prepare();
+        if (code != SUCCESSFUL_EXIT) return code;
+        if (Tunables::now(&Tunables::transpose_blocked)) (void)tr_prepare_blocked(); // (without the block buffers: tr_pass per column, see bt_pass)
+    }
+    DeviceArray<double> d_cols, d_vcol; // a block of C's columns as they came, and of V
+    HIPC(d_bt_V.alloc(npk), ERROR_HIP_MALLOC);
+    HIPC(d_bt_Dt.alloc(kk2), ERROR_HIP_MALLOC);
+    HIPC(d_cols.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
+    HIPC(d_vcol.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
+    HIPC(hipMemsetAsync(d_bt_V, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemsetAsync(d_bt_Dt, 0, sizeof(double) * kk2, STREAM), ERROR_HIP_MEMCPY);
+    hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)k * k + 255) / 256)), b256, 0, STREAM, k, k, kp, 0, (const double *)d_bd_D, (int64_t)kp, (double *)d_bt_Dt);
+    {
+        const NestedSolveGuard guard(*this);
+        const TransposedStatsGuard guard_t(*this);
+        for (int32_t j0 = 0; j0 < k; j0 += BORDER_COLS) {
+            const int32_t nk = std::min(BORDER_COLS, k - j0);
+            const dim3 gp((unsigned)(((int64_t)n * nk + 255) / 256));
+            hipLaunchKernelGGL(k_border_unpack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_bd_C, (double *)d_cols, (int64_t)n);
+            const int32_t code = solve_transpose_many(d_vcol, d_cols, nk, n, true);
+            if (code != SUCCESSFUL_EXIT) return code;
+            hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_vcol, (int64_t)n, (double *)d_bt_V);
+        }
+    }
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the two blocks go with this scope)
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    bt_bytes = (int64_t)(sizeof(double) * (npk + kk2));
+    bt_ready = true;
+    return SUCCESSFUL_EXIT;
+}
+
+int32_t Solver::bt_pass(double *Z, int64_t zs, const double *V, int64_t vs, int32_t C) {
+    if (S.sym_mode || d_tptr) return solve_core(Z, V, C, zs, true);
+    const int32_t n = S.n;
+    if (C > 1 && tr_blk_ready && Tunables::now(&Tunables::transpose_blocked)) { // (one column: the single kernels, as solve_transpose_many sends it)
+        const dim3 gp((n + 255) / 256, TR_KB / PERM_CW), b(256);
+        const uint64_t all = (1ull << C) - 1ull;
+        double *XP = d_tblk + 2 * (size_t)n * TR_KB;
+        hipLaunchKernelGGL(k_tr_perm_in_cols, gp, b, 0, STREAM, n, d_perm, d_cs, V, vs, XP, (int64_t)n, all, C);
+        const int32_t code = run_transposed<TrBlocked>(XP);
+        if (code != SUCCESSFUL_EXIT) return code;
+        hipLaunchKernelGGL(k_perm_out_cols, gp, b, 0, STREAM, n, d_rperm, d_rs, (const double *)XP, (int64_t)n, Z, zs, 0, all, C);
+        return SUCCESSFUL_EXIT;
+    }
+    for (int32_t c = 0; c < C; c++) {
+        const int32_t code = tr_pass(Z + (int64_t)c * zs, V + (int64_t)c * vs);
+        if (code != SUCCESSFUL_EXIT) return code;
+    }
+    return SUCCESSFUL_EXIT;
+}
+
 int32_t Solver::set_complex_pattern(int64_t nnzc, const std::vector<int32_t> &zrow, const std::vector<int32_t> &zcol, bool sym) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (nnzc < 1 || (int64_t)zrow.size() != nnzc || (int64_t)zcol.size() != nnzc) return ERROR_HIPMF_INVALID_VALUE;
@@ -4786,7 +4884,7 @@ int32_t Solver::adopt_factor(const double *d_values) {
     if (lc != SUCCESSFUL_EXIT) return lc;
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
     n_perturbed = n_zero_pivot = 0;
-    factorized = true, bd_k = 0;
+    factorized = true, forget_border();
     return SUCCESSFUL_EXIT;
 }
 

@@ -218,7 +218,7 @@ struct SolverExtraPrecise {
 // solver_hipmf_set_border / solver_hipmf_solve_bordered (kernels_border.hpp).  The border in force: B, C and W = A^{-1} B packed row-major
 // n x kp (kp = k rounded up to a multiple of 16), D, the LU of S = D - C^T W (column-major, leading dimension kp) and its pivots, the
 // scratch of the Gram products' partial tiles.  Allocated by set_border, freed by set_border(0) or with the handle; a factorisation
-// only clears bd_k.  The blocks of solve_bordered are allocated at its first call and regrown for a wider block: five n x C blocks -- the
+// only clears bd_k and bt_ready (forget_border).  The blocks of solve_bordered are allocated at its first call and regrown for a wider block: five n x C blocks -- the
 // residual, the pass pair's result, the x a step can be taken back from, and the staging of x and f of a host-pointer call --, the vectors of order kp of a block, the omegas of a block step and their pinned mirror.
 struct SolverBorder {
     int32_t bd_k = 0, bd_kp = 0;   // border columns in force (0: none), and what the arrays are padded to
@@ -230,6 +230,11 @@ struct SolverBorder {
     DeviceArray<unsigned long long> d_bd_nrm;
     PinnedArray<double> h_bd_nrm;
     int32_t bd_cols = 0, bd_small_kp = 0; // columns and border width the blocks of solve_bordered are allocated for (0: not allocated)
+    // The transposed side (solve_bordered_transpose), built at the first transposed call after a set_border and kept until the border
+    // is dropped: V = A^{-T} C packed as W is, and D^T packed as D is.  A factorisation clears bt_ready with bd_k.
+    DeviceArray<double> d_bt_V, d_bt_Dt;
+    bool bt_ready = false;
+    int64_t bt_bytes = 0; // device memory held for the transposed side
 };
 
 // solver_hipmf_values_outer / _solve_tangent / _solve_adjoint (kernels_sensitivity.hpp).  The inverse maps input -> CSR slots (pointer and
@@ -456,7 +461,7 @@ class Solver : public SolverDevice, public Tunables {
     // set_border copies the border to the device, computes W = A^{-1} B with solve() in blocks of 16 columns, S = D - C^T W and its LU
     // with partial pivoting in one workgroup; info (nullptr allowed): min / max |u_ii| of S, det S as mantissa and base-10 exponent,
     // bytes held.  k == 0 frees the border.  WARNING_SINGULAR_MATRIX for an exactly zero pivot of S: no border is left set.
-    // Every factorisation drops the border (bd_k = 0).
+    // Every factorisation drops the border (forget_border).
     int32_t set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device);
     // Block elimination refined on the whole system, per block of 16 columns: y = one unrefined pass pair of f, t = g - C^T y,
     // z = S^{-1} t, x = y - W z; then steps on the residual (f - A x - B z, g - C^T x - D z) by the stopping rule of solve() on the
@@ -466,8 +471,16 @@ class Solver : public SolverDevice, public Tunables {
     // left as they were.  See numeric.cpp.
     int32_t solve_bordered(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
                            bool on_device);
+    // The transposed system [A^T C; B^T D^T] [y; w] = [p; q] with the border in force: the same loop with V = A^{-T} C for W, the
+    // transposed pass pair for the plain one, S^T = D^T - B^T V through the LU of S (U^T, L^T, the exchanges backwards), and the
+    // residual over the rows of M^T.  Arguments, info and status codes as solve_bordered.  V and the packed D^T are built at the first
+    // call after a set_border (bt_prepare); counters 44 - 46 and the statistics of every other solve are left as they were.
+    int32_t solve_bordered_transpose(double *y, double *w, const double *p, const double *q, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
+                                     bool on_device);
     void drop_border(); // frees the border's device memory
+    void forget_border() { bd_k = 0, bt_ready = false; } // a new factor: the border and what was built from it are no longer valid
     int64_t bordered_steps = 0, bordered_blocks = 0; // of the last solve_bordered: block steps summed over the blocks, 16-column blocks
+    int64_t bordered_t_steps = 0, bordered_t_blocks = 0; // the same of the last solve_bordered_transpose
     // Sensitivities with respect to the matrix values (kernels_sensitivity.hpp).  The pattern-restricted outer product
     //   grad = beta grad + alpha sum_c u_c w_c^T |pattern
     // in the order of the values the caller hands to factorize (mapped = false: its CSR order, a symmetric-lower handle its lower
@@ -521,7 +534,7 @@ class Solver : public SolverDevice, public Tunables {
     int32_t set_expansion(int64_t nnz_lower, const std::vector<int32_t> &emap);
     int64_t expansion_inputs() const { return nnz_low; }
     const std::vector<int32_t> &expansion_map() const { return h_emap; }
-    void mark_factor_adopted(int32_t root_perturbed = 0) { n_perturbed = root_perturbed, n_zero_pivot = 0, factorized = true, bd_k = 0; } // ... including the matrix values; the root's count of replaced pivots decides about the Krylov rescue here too
+    void mark_factor_adopted(int32_t root_perturbed = 0) { n_perturbed = root_perturbed, n_zero_pivot = 0, factorized = true, forget_border(); } // ... including the matrix values; the root's count of replaced pivots decides about the Krylov rescue here too
     void *d_diag_ptr() const { return d_diag; }
     // FNV-1a over what two handles must share to exchange a factor: the fill-reducing permutation, the matching's row permutation, the
     // layout of the pool (computed at initialize / after a re-matching factorize)
@@ -628,6 +641,13 @@ class Solver : public SolverDevice, public Tunables {
     int32_t solve_extra_precise_core(double *x, double *tail, const double *rhs, int32_t nrhs, int64_t ld, double dx_tol, int32_t max_steps, double *info, bool on_device);
     // the blocked transposed pass pair on C <= 16 contiguous columns (stride n): Z = A^{-T} V, unrefined (buffers of tr_prepare_blocked())
     int32_t tr_pass_blk(double *Z, const double *V, int32_t C);
+    // the loop of solve_bordered (T false) and solve_bordered_transpose (T true): the operands and the four launches that differ
+    template <bool T>
+    int32_t bordered_core(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info, bool on_device);
+    int32_t bt_prepare(); // V = A^{-T} C and the packed D^T of the border in force, once per set_border
+    // Z = A^{-T} V for C <= 16 columns at the strides zs, vs, unrefined: the blocked pass pair, tr_pass per column without its buffers
+    // or with HIPMF_TRANSPOSE_BLOCKED=0, solve_core on a handle where A^T = A (vs == zs there)
+    int32_t bt_pass(double *Z, int64_t zs, const double *V, int64_t vs, int32_t C);
     // the error analysis of both forms; P: what differs (EaReal, EaComplex in numeric.cpp)
     template <class P>
     int32_t error_analysis_core(const double *xbar, const double *rhs, double *out, int32_t option);
