@@ -136,11 +136,11 @@ def chain(p1, m1, p2, m2, seed, weak=False, symmetric=False):
     return Case(A, symmetric)
 
 
-def complex_two_leaves_and_root(p, m, seed, weak=False, symmetric=False):
+def complex_two_leaves_and_root(p, m, seed, weak=False, symmetric=False, leaves=2):
     """The complex twin: complex order p, m (real-equivalent fronts of 2p, 2m, paired pivot searches).  Returns the complex dense matrix,
     the CSR pattern and the interleaved (re, im) values; `symmetric`: complex SYMMETRIC (A = A^T, not Hermitian), lower triangle."""
-    re = two_leaves_and_root(p, m, seed, weak=weak, symmetric=symmetric, group=16)  # (16 complex pivots = one 32-row tile)
-    im = two_leaves_and_root(p, m, seed + 7919, weak=False, symmetric=symmetric)
+    re = two_leaves_and_root(p, m, seed, weak=weak, symmetric=symmetric, leaves=leaves, group=16)  # (16 complex pivots = one 32-row tile)
+    im = two_leaves_and_root(p, m, seed + 7919, weak=False, symmetric=symmetric, leaves=leaves)
     Z = re.A + 1j * (im.A - np.diag(np.diag(im.A)) * 0.5)  # (diagonal 3 + 1.5 i plus noise)
     M = sp.csr_matrix(np.tril(Z) if symmetric else Z)
     M.sort_indices()
