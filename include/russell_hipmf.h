@@ -593,6 +593,12 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_BORDERED_TRANSPOSED_STEPS 49  /* refinement steps of the last solver_hipmf_solve_bordered_transpose / _device, summed over its blocks */
 #define HIPMF_COUNTER_BORDERED_TRANSPOSED_BLOCKS 50 /* 16-column blocks of that call */
 #define HIPMF_COUNTER_BORDER_TRANSPOSED_BYTES 51    /* device bytes held for the transposed side of the border (V = A^{-T} C, D^T): 0 until the first transposed call */
+#define HIPMF_COUNTER_COMPLEX_BORDER_COLUMNS 52             /* complex twin: k of the border in force (complex_solver_hipmf_set_border), 0 when none */
+#define HIPMF_COUNTER_COMPLEX_BORDERED_STEPS 53             /* complex twin: refinement steps of the last complex_solver_hipmf_solve_bordered / _device, summed over its blocks */
+#define HIPMF_COUNTER_COMPLEX_BORDERED_BLOCKS 54            /* 16-column blocks of that call */
+#define HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_STEPS 55  /* complex twin: refinement steps of the last complex_solver_hipmf_solve_bordered_transpose / _device */
+#define HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_BLOCKS 56 /* 16-column blocks of that call */
+#define HIPMF_COUNTER_COMPLEX_BORDER_TRANSPOSED_BYTES 57    /* complex twin: device bytes held for V = A^{-H} conj(C) and D^H: 0 until the first transposed call */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only
@@ -859,6 +865,62 @@ int32_t complex_solver_hipmf_solve_tangent(struct InterfaceComplexHIPMF *solver,
                                            int32_t ld, int32_t mapped);
 int32_t complex_solver_hipmf_solve_adjoint(struct InterfaceComplexHIPMF *solver, double *lambda, double *grad_values, const double *x, const double *g, int32_t nrhs,
                                            int32_t ld, double beta, int32_t mapped);
+/* BORDERED SYSTEMS for the complex handle: solver_hipmf_set_border, _solve_bordered and _solve_bordered_transpose in complex arithmetic,
+ *     [ A   B ] [x]   [f]      A: the factorised complex n x n matrix
+ *     [ C^T D ] [z] = [g]      B, C: n x k complex dense, D: k x k complex dense, 1 <= k <= HIPMF_COMPLEX_BORDER_MAX
+ * -- Hopf-point location and continuation ([J - i omega M, B; C^T, D] with k = 1 or 2, and the same system transposed or adjoint in every
+ * Newton step), constrained complex-shifted systems (K + i omega C - omega^2 M with constraints or Lagrange multipliers), and rank-k
+ * changes outside the pattern: (A + U V^T) x = b is the bordered system with B = U, C = V, D = -I, g = 0 (Woodbury; Radau5's complex
+ * system with a Broyden-type correction of J).
+ * C^T is the PLAIN transpose, not the Hermitian one: border row i of the system is column i of C, as for the real handle.  All arrays
+ * are interleaved (re, im) doubles, column-major; leading dimensions count COMPLEX entries: ldb, ldc, ldx >= n; ldd, ldz >= k.
+ * HIPMF_COMPLEX_BORDER_MAX = 32: the real-equivalent border then has at most HIPMF_BORDER_MAX = 64 columns, what the products of the
+ * real form are built for.
+ * complex_solver_hipmf_set_border computes W = A^{-1} B with k refined solves (16 per block), S = D - C^T W and its LU as a COMPLEX
+ * k x k matrix, partial pivoting by modulus.  border_info (NULL allowed): [0] min |u_ii| / max |u_ii| of that LU  [1], [2] real and
+ * imaginary mantissa and [3] base-10 exponent of det S, in the form of complex_solver_hipmf_get_determinant: det M = det A det S
+ * [4] bytes of device memory held for the border.  An exactly zero pivot of S returns HIPMF_WARNING_SINGULAR_MATRIX and leaves NO border
+ * set.  k = 0 drops the border (the pointers may be NULL); every factorize*, initialize and adopted factor drops it.
+ * complex_solver_hipmf_solve_bordered: block elimination, then iterative refinement on the whole system exactly as the real form does
+ * it.  The residual of all n + k complex rows is accumulated beyond twice the working precision and rounded once; omega is the
+ * componentwise backward error per COMPLEX row on complex moduli, |r_i| / (sum_j |a_ij||x_j| + sum_j |b_ij||z_j| + |f_i|), not that of
+ * the 2 n real rows taken separately.  z / g may be NULL (z not returned; g = 0).  max_steps <= 0 selects 4.  info (NULL allowed):
+ * 4 doubles per column -- steps, last omega, omega before the first step, state 0 converged / 1 no progress / 2 step limit; the call
+ * returns 0 whatever the state.  No Krylov rescue inside.
+ * complex_solver_hipmf_solve_bordered_transpose: M^H [y; w] = [p; q] (conjugate = 1), M^H = [A^H conj(C); B^H D^H], or M^T [y; w] =
+ * [p; q] (conjugate = 0), M^T = [A^T C; B^T D^T]; `conjugate` as in complex_solver_hipmf_solve_transpose.  V = A^{-H} conj(C) and D^H
+ * and the LU of its own Schur complement D^H - B^H V are built at the FIRST transposed call after a set_border (k refined transposed
+ * solves; an exactly zero pivot there returns HIPMF_WARNING_SINGULAR_MATRIX from that call) and serve both: conjugate = 0 runs the loop
+ * of M^H on conjugated data (p and q conjugated in a staging copy on entry, y and w on exit).  A handle that never makes the call
+ * allocates and launches nothing for it.
+ * NO SIDE EFFECTS on the factor, the values, any counter, statistic or timer of another solve (the plain and the transposed form do not
+ * move each other's counters) or the bits of a later solve; bit-reproducible; the host and _device forms give the same bits.
+ * HIPMF_COUNTER_COMPLEX_BORDER_COLUMNS .. _COMPLEX_BORDER_TRANSPOSED_BYTES (52 - 57) report the border in force and the last calls.
+ * WHAT IT COSTS (tools/bordered_complex.py, one MI355X, the 500 x 500 complex shifted grid of tools/solve_updated.py --complex,
+ * profiles/r24_bordered_complex.txt; one step after the start in every case): set_border_device 2.0 / 4.8 / 8.5 ms for k = 1 / 16 / 32;
+ * solve_bordered_device, one column: 1.51 / 1.93 / 2.65 ms against 0.77 ms for complex_solver_hipmf_solve_device; 16 columns: 7.4 /
+ * 11.0 / 16.2 ms against 3.2 ms -- two to five times the plain solve, dearest on a wide border with many columns (the compensated
+ * complex residual).  Transposed, conjugate = 1: 3.12 / 3.54 / 4.22 ms for one column (the first call after a set_border 6.1 / 8.3 /
+ * 16.9 ms), 8.2 / 9.6 / 11.9 ms for 16 -- dearer than the plain form for one column, cheaper for 16 columns from k = 16 on; conjugate =
+ * 0 costs 0.03 - 0.2 ms more.  k = 1 on host vectors: 1.78 ms against 3.36 ms for two complex_solver_hipmf_solve calls, two inner
+ * products and the combination by hand.  The border holds three packed 2n x kp arrays (kp = 2k rounded up to 16), the transposed
+ * side a fourth: 784 MB + 256 MB at k = 32 on 250 000 unknowns.
+ * ERROR_NULL_POINTER, ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION in this order, then ERROR_HIPMF_INVALID_VALUE (k outside
+ * 0 .. HIPMF_COMPLEX_BORDER_MAX, a leading dimension that is too small, nrhs < 1, a conjugate other than 0 or 1, no border in force). */
+#define HIPMF_COMPLEX_BORDER_MAX 32
+int32_t complex_solver_hipmf_set_border(struct InterfaceComplexHIPMF *solver, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D,
+                                        int32_t ldd, double *border_info_len_5, C_BOOL verbose);
+int32_t complex_solver_hipmf_set_border_device(struct InterfaceComplexHIPMF *solver, int32_t k, const double *d_B, int32_t ldb, const double *d_C, int32_t ldc,
+                                               const double *d_D, int32_t ldd, double *border_info_len_5, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_bordered(struct InterfaceComplexHIPMF *solver, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx,
+                                            int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_bordered_device(struct InterfaceComplexHIPMF *solver, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs,
+                                                   int32_t ldx, int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_bordered_transpose(struct InterfaceComplexHIPMF *solver, double *y, double *w, const double *p, const double *q, int32_t nrhs,
+                                                      int32_t ldx, int32_t ldz, int32_t conjugate, int32_t max_steps, double *info, C_BOOL verbose);
+int32_t complex_solver_hipmf_solve_bordered_transpose_device(struct InterfaceComplexHIPMF *solver, double *d_y, double *d_w, const double *d_p, const double *d_q,
+                                                             int32_t nrhs, int32_t ldx, int32_t ldz, int32_t conjugate, int32_t max_steps, double *info,
+                                                             C_BOOL verbose);
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *solver);
 
 /* plain device-memory helpers so that callers need no HIP binding of their own */

@@ -74,6 +74,17 @@ SYMBOLS = {
                                                           C.c_void_p, C.c_int32]),
     "solver_hipmf_solve_bordered_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                                  C.c_int32, C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_set_border": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_set_border_device": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                           C.c_int32]),
+    "complex_solver_hipmf_solve_bordered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                        C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_solve_bordered_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                               C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_solve_bordered_transpose": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                  C.c_int32, C.c_void_p, C.c_int32]),
+    "complex_solver_hipmf_solve_bordered_transpose_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "solver_hipmf_values_outer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32]),
     "solver_hipmf_values_outer_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                                      C.c_int32]),

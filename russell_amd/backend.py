@@ -372,7 +372,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48, "bordered_transposed_steps": 49, "bordered_transposed_blocks": 50, "border_transposed_bytes": 51}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48, "bordered_transposed_steps": 49, "bordered_transposed_blocks": 50, "border_transposed_bytes": 51, "complex_border_columns": 52, "complex_bordered_steps": 53, "complex_bordered_blocks": 54, "complex_bordered_transposed_steps": 55, "complex_bordered_transposed_blocks": 56, "complex_border_transposed_bytes": 57}
 
     WARNING_NOT_CONVERGED = 2
 
@@ -685,3 +685,106 @@ class ComplexHipmf:
         if code != 0:
             raise self._err(code, "complex_solver_hipmf_solve_adjoint")
         return (out.reshape(ga.shape)[0] if single and lam is None else out), gr
+
+    # ---- bordered systems on the kept factor (complex_solver_hipmf_set_border / _solve_bordered / _solve_bordered_transpose) ----
+    WARNING_SINGULAR_MATRIX = 1
+
+    def set_border(self, B, C_, D, verbose=False):
+        """The border of [A B; C^T D] on the kept factor, C^T the plain transpose: B, C_ complex of shape (n, k), D of shape (k, k); k = 0
+        (or B None) drops it.  Returns (border_info, status): min / max |u_ii| of the complex LU of S = D - C^T A^{-1} B, real and
+        imaginary mantissa and base-10 exponent of det S, device bytes held; status 0 or WARNING_SINGULAR_MATRIX; others raise."""
+        info = np.zeros(5)
+        if B is None or np.asarray(B).size == 0:
+            code = self.lib.complex_solver_hipmf_set_border(self.h, 0, None, 0, None, 0, None, 0, info.ctypes.data, int(verbose))
+        else:
+            Bf, Cf, Df = (np.asfortranarray(np.asarray(a, dtype=np.complex128).reshape(np.shape(a)[0], -1)) for a in (B, C_, D))
+            k = Bf.shape[1]
+            if Bf.shape != (self.n, k) or Cf.shape != (self.n, k) or Df.shape != (k, k):
+                raise ValueError("set_border expects B, C of shape (%d, k) and D of shape (k, k), got %r, %r, %r" % (self.n, Bf.shape, Cf.shape, Df.shape))
+            code = self.lib.complex_solver_hipmf_set_border(self.h, k, Bf.ctypes.data, self.n, Cf.ctypes.data, self.n, Df.ctypes.data, k, info.ctypes.data, int(verbose))
+        if code not in (0, self.WARNING_SINGULAR_MATRIX):
+            raise self._err(code, "complex_solver_hipmf_set_border")
+        return info, code
+
+    def solve_bordered(self, f, g=None, want_z=True, max_steps=0, ldx=None, ldz=None, verbose=False, x=None, z=None):
+        """[A B; C^T D] [x; z] = [f; g] with the border of set_border, refined on the whole system.  f: complex (n,) or (nrhs, ldx); g:
+        (k,) or (nrhs, ldz), None: g = 0; want_z False: z is not returned.  x / z: complex arrays of those shapes to write into (their
+        padding is left alone).  Returns (x, z or None, info of shape (nrhs, 4))."""
+        return self._solve_bordered("complex_solver_hipmf_solve_bordered", None, f, g, want_z, max_steps, ldx, ldz, verbose, x, z)
+
+    def solve_bordered_transpose(self, p, q=None, conjugate=True, want_w=True, max_steps=0, ldx=None, ldz=None, verbose=False, y=None, w=None):
+        """M^H [y; w] = [p; q] (conjugate) or M^T [y; w] = [p; q] with M = [A B; C^T D] of set_border.  Arguments and results as
+        solve_bordered: returns (y, w or None, info)."""
+        return self._solve_bordered("complex_solver_hipmf_solve_bordered_transpose", int(bool(conjugate)), p, q, want_w, max_steps, ldx, ldz, verbose, y, w)
+
+    def _solve_bordered(self, entry, conjugate, f, g, want_z, max_steps, ldx, ldz, verbose, x, z):
+        k = self.counter("complex_border_columns")
+        fa = self._z(f)
+        single = fa.ndim == 1
+        fa = fa.reshape(1, -1) if single else fa
+        nrhs = fa.shape[0]
+        ldx = fa.shape[1] if ldx is None else int(ldx)
+        ga = None if g is None else self._z(g).reshape(nrhs, -1)
+        ldz = (k if ga is None else ga.shape[1]) if ldz is None else int(ldz)
+        x = np.zeros((nrhs, ldx), np.complex128) if x is None else x
+        z = (np.zeros((nrhs, max(ldz, 1)), np.complex128) if z is None else z) if want_z else None
+        info = np.zeros((nrhs, 4))
+        head = (self.h, x.ctypes.data, None if z is None else z.ctypes.data, fa.ctypes.data, None if ga is None else ga.ctypes.data, nrhs, ldx, ldz)
+        tail = (int(max_steps), info.ctypes.data, int(verbose))
+        code = getattr(self.lib, entry)(*(head + (() if conjugate is None else (conjugate,)) + tail))
+        if code != 0:
+            raise self._err(code, entry)
+        if single:
+            return x[0], (None if z is None else z[0]), info[0]
+        return x, z, info
+
+    # device-resident operands: interleaved complex arrays, 16 bytes per entry
+    def dev_alloc(self, nbytes):
+        p = self.lib.hipmf_device_malloc(nbytes)
+        if not p:
+            raise MemoryError("hipmf_device_malloc(%d)" % nbytes)
+        return p
+
+    def dev_free(self, p):
+        self.lib.hipmf_device_free(p)
+
+    def h2d(self, dptr, arr):
+        a = np.ascontiguousarray(arr)
+        code = self.lib.hipmf_memcpy_h2d(dptr, a.ctypes.data_as(C.c_void_p), a.nbytes)
+        if code != 0:
+            raise self._err(code, "hipmf_memcpy_h2d")
+
+    def d2h(self, arr, dptr):
+        assert arr.flags["C_CONTIGUOUS"]
+        code = self.lib.hipmf_memcpy_d2h(arr.ctypes.data_as(C.c_void_p), dptr, arr.nbytes)
+        if code != 0:
+            raise self._err(code, "hipmf_memcpy_d2h")
+
+    def set_border_device(self, k, d_B, d_C, d_D, ldb=None, ldc=None, ldd=None):
+        """set_border with B, C (column-major ld x k complex) and D (ldd x k) resident on the device; returns (border_info, status)"""
+        info = np.zeros(5)
+        code = self.lib.complex_solver_hipmf_set_border_device(self.h, int(k), d_B, int(ldb or self.n), d_C, int(ldc or self.n), d_D, int(ldd or k), info.ctypes.data, 0)
+        if code not in (0, self.WARNING_SINGULAR_MATRIX):
+            raise self._err(code, "complex_solver_hipmf_set_border_device")
+        return info, code
+
+    def solve_bordered_device(self, d_x, d_z, d_f, d_g, nrhs=1, max_steps=0, ldx=None, ldz=None):
+        """solve_bordered with x, f (column-major ldx x nrhs complex) and z, g (ldz x nrhs; None allowed) resident on the device; returns info"""
+        nrhs = int(nrhs)
+        info = np.zeros((max(nrhs, 1), 4))
+        code = self.lib.complex_solver_hipmf_solve_bordered_device(self.h, d_x, d_z, d_f, d_g, nrhs, int(ldx or self.n),
+                                                                   int(ldz or max(self.counter("complex_border_columns"), 1)), int(max_steps), info.ctypes.data, 0)
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve_bordered_device")
+        return info[:nrhs]
+
+    def solve_bordered_transpose_device(self, d_y, d_w, d_p, d_q, nrhs=1, conjugate=True, max_steps=0, ldx=None, ldz=None):
+        """solve_bordered_transpose with y, p (column-major ldx x nrhs complex) and w, q (ldz x nrhs; None allowed) resident on the device; returns info"""
+        nrhs = int(nrhs)
+        info = np.zeros((max(nrhs, 1), 4))
+        code = self.lib.complex_solver_hipmf_solve_bordered_transpose_device(self.h, d_y, d_w, d_p, d_q, nrhs, int(ldx or self.n),
+                                                                             int(ldz or max(self.counter("complex_border_columns"), 1)), int(bool(conjugate)),
+                                                                             int(max_steps), info.ctypes.data, 0)
+        if code != 0:
+            raise self._err(code, "complex_solver_hipmf_solve_bordered_transpose_device")
+        return info[:nrhs]

@@ -658,6 +658,79 @@ int32_t complex_solver_hipmf_solve_adjoint(struct InterfaceComplexHIPMF *h, doub
     });
 }
 
+// Bordered systems on the kept factor for the complex handle (Solver::set_border, Solver::solve_bordered, Solver::solve_bordered_transpose
+// in their pairs mode; kernels_border_complex.hpp): the interleaved complex arrays are handed on as they are, leading dimensions doubled.
+// Status codes in the order of the real entry points: ERROR_NULL_POINTER (the handle; B, C, D with k > 0; x, f),
+// ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION, then ERROR_HIPMF_INVALID_VALUE.  The residual kernels read the moduli |a_ij| from
+// the adjacent pairs of the rows 2i: check_pairs, once per handle.
+static int32_t c_set_border_body(struct InterfaceComplexHIPMF *h, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D,
+                                 int32_t ldd, double *border_info, C_BOOL verbose, bool on_device) {
+    if (!h) return ERROR_NULL_POINTER;
+    if (k > 0 && k <= HIPMF_COMPLEX_BORDER_MAX && (!B || !C || !D)) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (k > 0 && k <= HIPMF_COMPLEX_BORDER_MAX && (ldb < h->n || ldc < h->n || ldd < k)) return ERROR_HIPMF_INVALID_VALUE;
+    if (k > 0 && k <= HIPMF_COMPLEX_BORDER_MAX)
+        if (const int32_t code = check_pairs(h); code != SUCCESSFUL_EXIT) return code;
+    h->solver.opt.verbose = verbose == 1;
+    return h->solver.set_border(k, B, 2 * (int64_t)ldb, C, 2 * (int64_t)ldc, D, 2 * (int64_t)ldd, border_info, on_device, true);
+}
+
+int32_t complex_solver_hipmf_set_border(struct InterfaceComplexHIPMF *h, int32_t k, const double *B, int32_t ldb, const double *C, int32_t ldc, const double *D,
+                                        int32_t ldd, double *border_info_len_5, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_set_border_body(h, k, B, ldb, C, ldc, D, ldd, border_info_len_5, verbose, false); });
+}
+
+int32_t complex_solver_hipmf_set_border_device(struct InterfaceComplexHIPMF *h, int32_t k, const double *d_B, int32_t ldb, const double *d_C, int32_t ldc,
+                                               const double *d_D, int32_t ldd, double *border_info_len_5, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_set_border_body(h, k, d_B, ldb, d_C, ldc, d_D, ldd, border_info_len_5, verbose, true); });
+}
+
+// trans: 0 the system itself, 1 M^T (the loop of M^H on conjugated data), 2 M^H (the transposed real-equivalent system)
+static int32_t c_solve_bordered_body(struct InterfaceComplexHIPMF *h, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx, int32_t ldz,
+                                     int32_t max_steps, double *info, C_BOOL verbose, bool on_device, const char *who, int32_t trans) {
+    if (!h || !x || !f) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    Solver &s = h->solver;
+    if (trans < 0 || !s.bd_pairs) return ERROR_HIPMF_INVALID_VALUE; // (a conjugate other than 0 or 1; no border of this handle's kind in force)
+    s.opt.verbose = verbose == 1;
+    const int32_t code = trans != 0 ? s.solve_bordered_transpose(x, z, f, g, nrhs, 2 * (int64_t)ldx, 2 * (int64_t)ldz, max_steps, info, on_device, trans == 1)
+                                    : s.solve_bordered(x, z, f, g, nrhs, 2 * (int64_t)ldx, 2 * (int64_t)ldz, max_steps, info, on_device);
+    if (verbose == 1 && code == SUCCESSFUL_EXIT)
+        printf("%s: %d column(s), border of %d: %lld block step(s) in %lld block(s)\n", who, nrhs, s.bd_k / 2, (long long)(trans != 0 ? s.bordered_t_steps : s.bordered_steps),
+               (long long)(trans != 0 ? s.bordered_t_blocks : s.bordered_blocks));
+    return code;
+}
+
+int32_t complex_solver_hipmf_solve_bordered(struct InterfaceComplexHIPMF *h, double *x, double *z, const double *f, const double *g, int32_t nrhs, int32_t ldx,
+                                            int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() { return c_solve_bordered_body(h, x, z, f, g, nrhs, ldx, ldz, max_steps, info, verbose, false, "complex_solver_hipmf_solve_bordered", 0); });
+}
+
+int32_t complex_solver_hipmf_solve_bordered_device(struct InterfaceComplexHIPMF *h, double *d_x, double *d_z, const double *d_f, const double *d_g, int32_t nrhs,
+                                                   int32_t ldx, int32_t ldz, int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_bordered_body(h, d_x, d_z, d_f, d_g, nrhs, ldx, ldz, max_steps, info, verbose, true, "complex_solver_hipmf_solve_bordered_device", 0);
+    });
+}
+
+int32_t complex_solver_hipmf_solve_bordered_transpose(struct InterfaceComplexHIPMF *h, double *y, double *w, const double *p, const double *q, int32_t nrhs,
+                                                      int32_t ldx, int32_t ldz, int32_t conjugate, int32_t max_steps, double *info, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_bordered_body(h, y, w, p, q, nrhs, ldx, ldz, max_steps, info, verbose, false, "complex_solver_hipmf_solve_bordered_transpose", trans_of(conjugate));
+    });
+}
+
+int32_t complex_solver_hipmf_solve_bordered_transpose_device(struct InterfaceComplexHIPMF *h, double *d_y, double *d_w, const double *d_p, const double *d_q,
+                                                             int32_t nrhs, int32_t ldx, int32_t ldz, int32_t conjugate, int32_t max_steps, double *info,
+                                                             C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return c_solve_bordered_body(h, d_y, d_w, d_p, d_q, nrhs, ldx, ldz, max_steps, info, verbose, true, "complex_solver_hipmf_solve_bordered_transpose_device",
+                                     trans_of(conjugate));
+    });
+}
+
 const char *complex_solver_hipmf_last_error(struct InterfaceComplexHIPMF *h) { return h ? h->solver.last_error.c_str() : "null solver"; }
 
 static int32_t c_get_stats_body(struct InterfaceComplexHIPMF *h, int64_t *is, double *ds) {
@@ -723,6 +796,12 @@ int64_t complex_solver_hipmf_get_counter(struct InterfaceComplexHIPMF *h, int32_
     case HIPMF_COUNTER_EXTRA_PRECISE_UPDATE_US: return (int64_t)(1e3 * s.extra_ms[2]);
     case HIPMF_COUNTER_SENS_OUTER_COLUMNS: return s.sens_outer_columns;
     case HIPMF_COUNTER_SENS_OUTER_US: return (int64_t)(1e3 * s.sens_outer_ms);
+    case HIPMF_COUNTER_COMPLEX_BORDER_COLUMNS: return s.bd_pairs ? s.bd_k / 2 : 0;
+    case HIPMF_COUNTER_COMPLEX_BORDERED_STEPS: return s.bordered_steps;
+    case HIPMF_COUNTER_COMPLEX_BORDERED_BLOCKS: return s.bordered_blocks;
+    case HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_STEPS: return s.bordered_t_steps;
+    case HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_BLOCKS: return s.bordered_t_blocks;
+    case HIPMF_COUNTER_COMPLEX_BORDER_TRANSPOSED_BYTES: return s.bt_bytes;
     default: return -1;
     }
 }

@@ -15,4 +15,5 @@
 #include "kernels_vector.hpp"
 #include "kernels_refine_extra.hpp"
 #include "kernels_border.hpp"
+#include "kernels_border_complex.hpp"
 #include "kernels_sensitivity.hpp"

@@ -4327,11 +4327,16 @@ void Solver::drop_border() {
     static_cast<SolverBorder &>(*this) = SolverBorder();
 }
 
-int32_t Solver::set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device) {
+// pairs: the border of the complex twin (kernels_border_complex.hpp).  kc complex columns are k = 2 kc packed real-equivalent ones -- the
+// interleaved column and its partner, every pair rotated --; C is packed conjugated, so that the Gram product with it is C^T; W = A^{-1} B
+// takes kc solves of interleaved columns, not 2 kc; S = D - C^T W stays a complex kc x kc matrix and is factorised as one.
+int32_t Solver::set_border(int32_t kc, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device,
+                           bool pairs) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
-    if (k < 0 || k > BORDER_MAX) return ERROR_HIPMF_INVALID_VALUE;
-    if (info) info[0] = info[1] = info[2] = info[3] = 0.0;
+    if (kc < 0 || kc > (pairs ? ZBORDER_MAX : BORDER_MAX) || (pairs && (S.n & 1))) return ERROR_HIPMF_INVALID_VALUE;
+    const int32_t k = pairs ? 2 * kc : kc; // real(-equivalent) border columns
+    if (info) info[0] = info[1] = info[2] = info[3] = 0.0, info[pairs ? 4 : 3] = 0.0;
     if (k == 0) {
         drop_border();
         return SUCCESSFUL_EXIT;
@@ -4353,46 +4358,62 @@ int32_t Solver::set_border(int32_t k, const double *B, int64_t ldb, const double
     HIPC(d_bd_piv.alloc((size_t)kp), ERROR_HIP_MALLOC);
     HIPC(d_bd_rec.alloc(BORDER_REC), ERROR_HIP_MALLOC);
     HIPC(d_bd_part.alloc(BORDER_PART * (size_t)nch * tile), ERROR_HIP_MALLOC); // (the widest user: k_border_rows_part)
-    HIPC(d_cols.alloc((size_t)n * k), ERROR_HIP_MALLOC);
+    HIPC(d_cols.alloc((size_t)n * kc), ERROR_HIP_MALLOC);
     HIPC(d_wcol.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
     HIPC(d_gs.alloc(kk2), ERROR_HIP_MALLOC);
     const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const dim3 b256(256), gp((unsigned)(((int64_t)n * k + 255) / 256));
+    const dim3 b256(256);
     HIPC(hipMemsetAsync(d_bd_B, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(d_bd_C, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(d_bd_W, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(d_bd_D, 0, sizeof(double) * kk2, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(d_bd_piv, 0, sizeof(int32_t) * (size_t)kp, STREAM), ERROR_HIP_MEMCPY);
-    for (int32_t j = 0; j < k; j++) {
+    // columns [j0, j0 + nk) of `to` from the columns of `from` as they came: nk (complex) columns, n doubles apart
+    auto pack = [&](const double *from, int32_t j0, int32_t nk, int32_t conj, double *to) {
+        if (pairs)
+            hipLaunchKernelGGL(k_zborder_pack, dim3((unsigned)(((int64_t)(n / 2) * nk + 255) / 256)), b256, 0, STREAM, n / 2, nk, kp, j0, from, (int64_t)n, conj, to);
+        else
+            hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)n * nk + 255) / 256)), b256, 0, STREAM, n, nk, kp, j0, from, (int64_t)n, to);
+    };
+    for (int32_t j = 0; j < kc; j++) {
         HIPC(hipMemcpyAsync(d_cols + (size_t)j * n, C + (int64_t)j * ldc, nb, in, STREAM), ERROR_HIP_MEMCPY);
         HIPC(hipMemcpyAsync(d_bd_D + (size_t)j * kp, D + (int64_t)j * ldd, sizeof(double) * (size_t)k, in, STREAM), ERROR_HIP_MEMCPY);
     }
-    hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, k, kp, 0, (const double *)d_cols, (int64_t)n, (double *)d_bd_C);
-    for (int32_t j = 0; j < k; j++) HIPC(hipMemcpyAsync(d_cols + (size_t)j * n, B + (int64_t)j * ldb, nb, in, STREAM), ERROR_HIP_MEMCPY);
-    hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, k, kp, 0, (const double *)d_cols, (int64_t)n, (double *)d_bd_B);
+    pack(d_cols, 0, kc, 1, d_bd_C); // (pairs: conj(C), whose real-equivalent form transposed is that of C^T)
+    for (int32_t j = 0; j < kc; j++) HIPC(hipMemcpyAsync(d_cols + (size_t)j * n, B + (int64_t)j * ldb, nb, in, STREAM), ERROR_HIP_MEMCPY);
+    pack(d_cols, 0, kc, 0, d_bd_B);
     {
         const NestedSolveGuard guard(*this); // (W comes from ordinary refined solves: their statistics are not the caller's)
-        for (int32_t j0 = 0; j0 < k; j0 += BORDER_COLS) {
-            const int32_t nk = std::min(BORDER_COLS, k - j0);
+        for (int32_t j0 = 0; j0 < kc; j0 += BORDER_COLS) {
+            const int32_t nk = std::min(BORDER_COLS, kc - j0);
             const int32_t code = solve(d_wcol, d_cols + (size_t)j0 * n, nk, n, true);
             if (code != SUCCESSFUL_EXIT) return code;
-            hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)n * nk + 255) / 256)), b256, 0, STREAM, n, nk, kp, j0, (const double *)d_wcol, (int64_t)n,
-                               (double *)d_bd_W);
+            pack(d_wcol, j0, nk, 0, d_bd_W);
+            // (pairs: C^T W of nk interleaved columns comes out interleaved, kp doubles per complex column of S)
             hipLaunchKernelGGL(k_border_gram, dim3((unsigned)nch, (unsigned)(kp / 16)), dim3(64), 0, STREAM, n, kp, (const double *)d_bd_C, (const double *)d_wcol,
                                (int64_t)n, nk, (double *)d_bd_part);
             hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, nch, kp, (const double *)d_bd_part, d_gs + (size_t)j0 * kp);
         }
     }
-    hipLaunchKernelGGL(k_border_lu, dim3(1), b256, 0, STREAM, k, kp, (const double *)d_bd_D, (const double *)d_gs, (double *)d_bd_LU, (int32_t *)d_bd_piv, (double *)d_bd_rec);
+    if (pairs)
+        hipLaunchKernelGGL(k_zborder_lu, dim3(1), b256, 0, STREAM, kc, kp, (const double *)d_bd_D, (const double *)d_gs, (double *)d_bd_LU, (int32_t *)d_bd_piv,
+                           (double *)d_bd_rec);
+    else
+        hipLaunchKernelGGL(k_border_lu, dim3(1), b256, 0, STREAM, k, kp, (const double *)d_bd_D, (const double *)d_gs, (double *)d_bd_LU, (int32_t *)d_bd_piv,
+                           (double *)d_bd_rec);
     double rec[BORDER_REC];
     HIPC(hipMemcpyAsync(rec, d_bd_rec, sizeof rec, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     if (rec[4] != 0.0) return WARNING_SINGULAR_MATRIX; // (an exactly zero pivot of S: no border is left set)
-    bd_k = k, bd_kp = kp, bd_chunks = nch;
+    bd_k = k, bd_kp = kp, bd_chunks = nch, bd_pairs = pairs;
     bd_bytes = (int64_t)(sizeof(double) * (3 * npk + 2 * kk2 + BORDER_PART * (size_t)nch * tile + BORDER_REC) + sizeof(int32_t) * (size_t)kp);
-    if (info) info[0] = rec[1] > 0.0 ? rec[0] / rec[1] : 0.0, info[1] = rec[2], info[2] = rec[3], info[3] = (double)bd_bytes;
-    if (opt.verbose)
+    if (info && pairs) info[0] = rec[1] > 0.0 ? rec[0] / rec[1] : 0.0, info[1] = rec[2], info[2] = rec[5], info[3] = rec[3], info[4] = (double)bd_bytes;
+    if (info && !pairs) info[0] = rec[1] > 0.0 ? rec[0] / rec[1] : 0.0, info[1] = rec[2], info[2] = rec[3], info[3] = (double)bd_bytes;
+    if (opt.verbose && pairs)
+        fprintf(stderr, "hipmf: set_border (complex): k = %d, min / max |u_ii| of S = %.3e, det S = (%.6f %+.6f i) x 10^%.0f, %.1f MB on the device\n", kc,
+                rec[1] > 0.0 ? rec[0] / rec[1] : 0.0, rec[2], rec[5], rec[3], 1e-6 * (double)bd_bytes);
+    if (opt.verbose && !pairs)
         fprintf(stderr, "hipmf: set_border: k = %d, min / max |u_ii| of S = %.3e, det S = %.6f x 10^%.0f, %.1f MB on the device\n", k, rec[1] > 0.0 ? rec[0] / rec[1] : 0.0,
                 rec[2], rec[3], 1e-6 * (double)bd_bytes);
     undo.keep = true;
@@ -4406,7 +4427,7 @@ int32_t Solver::set_border(int32_t k, const double *B, int64_t ldb, const double
 // transposed call after a set_border (bt_prepare).  With T false nothing is allocated or launched that the plain form did not before.
 template <bool T>
 int32_t Solver::bordered_core(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
-                              bool on_device) {
+                              bool on_device, bool conj_pairs) {
     if (!initialized) return ERROR_NEED_INITIALIZATION;
     if (!factorized) return ERROR_NEED_FACTORIZATION;
     if (!x || !f) return ERROR_NULL_POINTER;
@@ -4428,6 +4449,13 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
     const double *const d_gram = T ? (const double *)d_bd_B : (const double *)d_bd_C, *const d_corr = T ? (const double *)d_bt_V : (const double *)d_bd_W;
     const double *const d_diag = T ? (const double *)d_bt_Dt : (const double *)d_bd_D;
     const double *const d_side = T ? (const double *)d_bd_C : (const double *)d_bd_B; // the border columns in the first n rows
+    // The border of the complex twin (bd_pairs; kernels_border_complex.hpp): the pass pairs, the Gram products and the corrections above
+    // are those of the real-equivalent system with k = 2 kc packed columns; the small solve is complex (T: with the Schur complement of
+    // M^H, the transposed real-equivalent system), the residual and its omegas run per complex row on moduli.  conj_pairs (T alone): M^T -- the
+    // loop of M^H on conjugated data; right-hand sides and results of a device call are then staged as a host call's are.
+    const bool Z = bd_pairs;
+    if (conj_pairs && !(T && Z)) return ERROR_HIPMF_INVALID_VALUE;
+    const bool staged = !on_device || conj_pairs;
     const int32_t C = std::min(nrhs, BORDER_COLS);
     const size_t tile = (size_t)kp * BORDER_COLS;
     if (bd_cols < C || bd_small_kp != kp) {
@@ -4443,7 +4471,7 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
     double *const d_GG = d_bd_small, *const d_Z = d_bd_small + tile, *const d_ZS = d_bd_small + 2 * tile, *const d_DZ = d_bd_small + 3 * tile;
     double *const d_RG = d_bd_small + 4 * tile, *const d_G = d_bd_small + 5 * tile;
     const dim3 b256(256), b64(64), gt((unsigned)((n + 63) / 64)), gg((unsigned)nch, (unsigned)(kp / 16));
-    const int64_t stride = on_device ? ldx : (int64_t)n;
+    const int64_t stride = staged ? (int64_t)n : ldx;
     const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 
     const NestedSolveGuard guard(*this);
@@ -4451,13 +4479,19 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
     for (int32_t j0 = 0; j0 < nrhs; j0 += BORDER_COLS) {
         const int32_t nk = std::min(BORDER_COLS, nrhs - j0);
         blocks_done++;
-        double *const xb = on_device ? x + (int64_t)j0 * ldx : d_bd_vec + 3 * blk;
-        const double *const fb = on_device ? f + (int64_t)j0 * ldx : d_bd_vec + 4 * blk;
+        double *const xb = staged ? d_bd_vec + 3 * blk : x + (int64_t)j0 * ldx;
+        const double *const fb = staged ? d_bd_vec + 4 * blk : f + (int64_t)j0 * ldx;
         HIPC(hipMemsetAsync(d_bd_small, 0, sizeof(double) * 6 * tile, STREAM), ERROR_HIP_MEMCPY); // (the rows k .. kp - 1 stay zero: g = 0 without a g)
         for (int32_t c = 0; c < nk; c++) {
-            if (!on_device) HIPC(hipMemcpyAsync(d_bd_vec + 4 * blk + (size_t)c * n, f + (int64_t)(j0 + c) * ldx, nb, in, STREAM), ERROR_HIP_MEMCPY);
+            if (staged) HIPC(hipMemcpyAsync(d_bd_vec + 4 * blk + (size_t)c * n, f + (int64_t)(j0 + c) * ldx, nb, in, STREAM), ERROR_HIP_MEMCPY);
             if (g) HIPC(hipMemcpyAsync(d_GG + (size_t)c * kp, g + (int64_t)(j0 + c) * ldz, kb, in, STREAM), ERROR_HIP_MEMCPY);
         }
+        // conj_pairs: the imaginary parts of the block's n-vectors and of its vectors of order k negated (on the way in: p and q)
+        auto conj_block = [&](double *vn, double *vk) {
+            hipLaunchKernelGGL(k_tr_conj_cols, dim3((unsigned)((n / 2 + 255) / 256), (unsigned)nk), b256, 0, STREAM, n, vn, (int64_t)n, ~0u, nk);
+            hipLaunchKernelGGL(k_tr_conj_cols, dim3(1, (unsigned)nk), b256, 0, STREAM, kp, vk, (int64_t)kp, ~0u, nk);
+        };
+        if (conj_pairs) conj_block(d_bd_vec + 4 * blk, d_GG);
         const size_t nrm_words = (size_t)RES_NORM_WORDS * nk + BORDER_COLS;
         unsigned long long *const d_nrm = d_bd_nrm;
         double *const d_omega_g = reinterpret_cast<double *>(d_nrm + (size_t)RES_NORM_WORDS * nk);
@@ -4470,7 +4504,10 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
             if (code != SUCCESSFUL_EXIT) return code;
             hipLaunchKernelGGL(k_border_gram, gg, b64, 0, STREAM, n, kp, d_gram, (const double *)ydst, ystr, nk, (double *)d_bd_part);
             hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, nch, kp, (const double *)d_bd_part, d_G);
-            if (T) {
+            if (Z) { // (T: the LU of S_T = D^H - B^H V, see bt_prepare)
+                hipLaunchKernelGGL(k_zborder_small_solve, dim3((unsigned)nk), b64, 0, STREAM, k / 2, kp, T ? (const double *)d_bt_LU : (const double *)d_bd_LU,
+                                   T ? (const int32_t *)d_bt_piv : (const int32_t *)d_bd_piv, rg, (const double *)d_G, d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
+            } else if (T) {
                 hipLaunchKernelGGL(k_border_small_solve_t, dim3((unsigned)nk), b64, 0, STREAM, k, kp, (const double *)d_bd_LU, (const int32_t *)d_bd_piv, rg,
                                    (const double *)d_G, d_DZ, d_Z, fresh ? (double *)nullptr : d_ZS, mask);
             } else {
@@ -4484,6 +4521,22 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
         // the residual of (x, z) over all n + k rows into (d_R, d_RG), the omegas of the columns of the mask to the host
         auto measure = [&]() -> int32_t {
             HIPC(hipMemsetAsync(d_nrm, 0, nrm_words * sizeof(unsigned long long), STREAM), ERROR_HIP_MEMCPY);
+            if (Z) {
+                const dim3 gz((unsigned)((n / 2 + 255) / 256));
+                if (T)
+                    hipLaunchKernelGGL(k_zborder_residual_nt, gz, b256, 0, STREAM, n / 2, d_ttptr, d_ttrow, d_ttmap, d_vals, k / 2, kp, d_side, (const double *)d_Z,
+                                       (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
+                else
+                    hipLaunchKernelGGL(k_zborder_residual_n, gz, b256, 0, STREAM, n / 2, d_rp, d_ci, d_vals, k / 2, kp, d_side, (const double *)d_Z, (const double *)xb,
+                                       stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
+                hipLaunchKernelGGL(k_zborder_rows_part, dim3((unsigned)nch, (unsigned)nk), b256, 0, STREAM, n, kp, d_gram, (const double *)xb, stride, mask,
+                                   (double *)d_bd_part);
+                hipLaunchKernelGGL(k_zborder_rows, dim3((unsigned)nk), b64, 0, STREAM, k / 2, kp, nch, d_diag, (const double *)d_GG, (const double *)d_bd_part,
+                                   (const double *)d_Z, d_RG, d_omega_g, mask);
+                HIPC(hipMemcpyAsync(h_bd_nrm, d_nrm, nrm_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+                HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+                return SUCCESSFUL_EXIT;
+            }
             if (T && !a_is_at) {
                 hipLaunchKernelGGL(k_border_residual_nt, dim3((unsigned)((n + 255) / 256)), b256, 0, STREAM, n, d_ttptr, d_ttrow, d_ttmap, d_vals, k, kp, d_side,
                                    (const double *)d_Z, (const double *)xb, stride, fb, stride, d_R, (int64_t)n, d_nrm, nk, mask);
@@ -4536,13 +4589,14 @@ int32_t Solver::bordered_core(double *x, double *z, const double *f, const doubl
             if (code != SUCCESSFUL_EXIT) return code;
             steps_done++;
         }
+        if (conj_pairs) conj_block(xb, d_Z); // (on the way out: y and w)
         for (int32_t c = 0; c < nk; c++) {
             const Column &q = col[c];
             if (info) {
                 double *const o = info + 4 * (size_t)(j0 + c);
                 o[0] = q.steps, o[1] = q.omega, o[2] = q.omega0, o[3] = q.state;
             }
-            if (!on_device) HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ldx, xb + (size_t)c * n, nb, out, STREAM), ERROR_HIP_MEMCPY);
+            if (staged) HIPC(hipMemcpyAsync(x + (int64_t)(j0 + c) * ldx, xb + (size_t)c * n, nb, out, STREAM), ERROR_HIP_MEMCPY);
             if (z) HIPC(hipMemcpyAsync(z + (int64_t)(j0 + c) * ldz, d_Z + (size_t)c * kp, kb, out, STREAM), ERROR_HIP_MEMCPY);
         }
         HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the staging blocks are the next block's)
@@ -4734,8 +4788,8 @@ int32_t Solver::solve_adjoint(double *lambda, double *grad, const double *x, con
 // ---- the transposed bordered system (the loop: bordered_core above) ----
 
 int32_t Solver::solve_bordered_transpose(double *y, double *w, const double *p, const double *q, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
-                                         bool on_device) {
-    return bordered_core<true>(y, w, p, q, nrhs, ldx, ldz, max_steps, info, on_device);
+                                         bool on_device, bool conj_pairs) {
+    return bordered_core<true>(y, w, p, q, nrhs, ldx, ldz, max_steps, info, on_device, conj_pairs);
 }
 
 // V = A^{-T} C by the handle's refined transposed solves, 16 columns per block, as W = A^{-1} B came from solve() -- nothing of the
@@ -4752,29 +4806,68 @@ int32_t Solver::bt_prepare() {
         if (code != SUCCESSFUL_EXIT) return code;
         if (Tunables::now(&Tunables::transpose_blocked)) (void)tr_prepare_blocked(); // (without the block buffers: tr_pass per column, see bt_pass)
     }
-    DeviceArray<double> d_cols, d_vcol; // a block of C's columns as they came, and of V
+    DeviceArray<double> d_cols, d_vcol, d_gs, d_rec; // a block of C's columns as they came, and of V; pairs: B^H V and the record of its LU
     HIPC(d_bt_V.alloc(npk), ERROR_HIP_MALLOC);
     HIPC(d_bt_Dt.alloc(kk2), ERROR_HIP_MALLOC);
+    if (bd_pairs) {
+        HIPC(d_bt_LU.alloc(kk2), ERROR_HIP_MALLOC);
+        HIPC(d_bt_piv.alloc((size_t)kp), ERROR_HIP_MALLOC);
+        HIPC(d_gs.alloc(kk2), ERROR_HIP_MALLOC);
+        HIPC(d_rec.alloc(BORDER_REC), ERROR_HIP_MALLOC);
+        HIPC(hipMemsetAsync(d_bt_piv, 0, sizeof(int32_t) * (size_t)kp, STREAM), ERROR_HIP_MEMCPY);
+    }
     HIPC(d_cols.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
     HIPC(d_vcol.alloc((size_t)n * BORDER_COLS), ERROR_HIP_MALLOC);
     HIPC(hipMemsetAsync(d_bt_V, 0, sizeof(double) * npk, STREAM), ERROR_HIP_MEMCPY);
     HIPC(hipMemsetAsync(d_bt_Dt, 0, sizeof(double) * kk2, STREAM), ERROR_HIP_MEMCPY);
-    hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)k * k + 255) / 256)), b256, 0, STREAM, k, k, kp, 0, (const double *)d_bd_D, (int64_t)kp, (double *)d_bt_Dt);
+    if (bd_pairs) // (D^H: the small block of the transposed real-equivalent system, M^H)
+        hipLaunchKernelGGL(k_zborder_adjoint, dim3((unsigned)((k / 2 * (k / 2) + 255) / 256)), b256, 0, STREAM, k / 2, kp, (const double *)d_bd_D, (double *)d_bt_Dt);
+    else
+        hipLaunchKernelGGL(k_border_pack, dim3((unsigned)(((int64_t)k * k + 255) / 256)), b256, 0, STREAM, k, k, kp, 0, (const double *)d_bd_D, (int64_t)kp, (double *)d_bt_Dt);
     {
         const NestedSolveGuard guard(*this);
         const TransposedStatsGuard guard_t(*this);
-        for (int32_t j0 = 0; j0 < k; j0 += BORDER_COLS) {
-            const int32_t nk = std::min(BORDER_COLS, k - j0);
-            const dim3 gp((unsigned)(((int64_t)n * nk + 255) / 256));
-            hipLaunchKernelGGL(k_border_unpack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_bd_C, (double *)d_cols, (int64_t)n);
+        // (pairs: V = A^{-H} conj(C) from the k / 2 interleaved columns of conj(C), the even columns of the packed array; M^T is
+        // served from the same V on conjugated data, see bordered_core)
+        const int32_t kcols = bd_pairs ? k / 2 : k;
+        for (int32_t j0 = 0; j0 < kcols; j0 += BORDER_COLS) {
+            const int32_t nk = std::min(BORDER_COLS, kcols - j0);
+            const dim3 gp((unsigned)(((int64_t)n * nk + 255) / 256)), gz((unsigned)(((int64_t)(n / 2) * nk + 255) / 256));
+            if (bd_pairs)
+                hipLaunchKernelGGL(k_zborder_unpack, gz, b256, 0, STREAM, n / 2, nk, kp, j0, (const double *)d_bd_C, (double *)d_cols, (int64_t)n);
+            else
+                hipLaunchKernelGGL(k_border_unpack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_bd_C, (double *)d_cols, (int64_t)n);
             const int32_t code = solve_transpose_many(d_vcol, d_cols, nk, n, true);
             if (code != SUCCESSFUL_EXIT) return code;
-            hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_vcol, (int64_t)n, (double *)d_bt_V);
+            if (bd_pairs) {
+                hipLaunchKernelGGL(k_zborder_pack, gz, b256, 0, STREAM, n / 2, nk, kp, j0, (const double *)d_vcol, (int64_t)n, 0, (double *)d_bt_V);
+                hipLaunchKernelGGL(k_border_gram, dim3((unsigned)bd_chunks, (unsigned)(kp / 16)), dim3(64), 0, STREAM, n, kp, (const double *)d_bd_B, (const double *)d_vcol,
+                                   (int64_t)n, nk, (double *)d_bd_part);
+                hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)kp), b256, 0, STREAM, bd_chunks, kp, (const double *)d_bd_part, d_gs + (size_t)j0 * kp);
+            } else {
+                hipLaunchKernelGGL(k_border_pack, gp, b256, 0, STREAM, n, nk, kp, j0, (const double *)d_vcol, (int64_t)n, (double *)d_bt_V);
+            }
         }
     }
-    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the two blocks go with this scope)
+    if (bd_pairs) {
+        // The complex twin factorises the Schur complement of M^H on its own, S_T = D^H - B^H V, instead of reaching for S^H through the LU
+        // of S.  The real form may do that because W and V come from the SAME perturbed factor, (A + E)^{-1} B and (A + E)^{-T} C: then
+        // D^T - B^T V is the transpose of S to rounding.  Here W and V are each built from k solves of the even real-equivalent columns,
+        // the partners by rotation, and E does not have the structure of a complex matrix: rows and columns of the 2k x 2k real Schur
+        // complement then give complex numbers that differ by cond(A)^2 eps -- 7e-7 relative at cond 7e10 (zhopf1e-10 of
+        // tests/bordered_complex.py), which the border rows see in full as an omega of 1e-2 before the first step.  With S_T the
+        // elimination of M^H is as consistent as that of M.  An exactly zero pivot of S_T: WARNING_SINGULAR_MATRIX, nothing is kept.
+        hipLaunchKernelGGL(k_zborder_lu, dim3(1), b256, 0, STREAM, k / 2, kp, (const double *)d_bt_Dt, (const double *)d_gs, (double *)d_bt_LU, (int32_t *)d_bt_piv,
+                           (double *)d_rec);
+        double rec[BORDER_REC];
+        HIPC(hipMemcpyAsync(rec, d_rec, sizeof rec, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        if (rec[4] != 0.0) return WARNING_SINGULAR_MATRIX;
+    }
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (the blocks go with this scope)
     HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
     bt_bytes = (int64_t)(sizeof(double) * (npk + kk2));
+    if (bd_pairs) bt_bytes += (int64_t)(sizeof(double) * kk2 + sizeof(int32_t) * (size_t)kp);
     bt_ready = true;
     return SUCCESSFUL_EXIT;
 }

@@ -222,6 +222,8 @@ struct SolverExtraPrecise {
 // residual, the pass pair's result, the x a step can be taken back from, and the staging of x and f of a host-pointer call --, the vectors of order kp of a block, the omegas of a block step and their pinned mirror.
 struct SolverBorder {
     int32_t bd_k = 0, bd_kp = 0;   // border columns in force (0: none), and what the arrays are padded to
+    bool bd_pairs = false;         // the border of the complex twin (kernels_border_complex.hpp): bd_k = 2 k real-equivalent columns, S, D and the
+                                   // vectors of order k interleaved complex numbers, the residual and its omegas on complex moduli
     int32_t bd_chunks = 0;         // partial sums per entry of a Gram product: ceil(n / BORDER_CHUNK)
     int64_t bd_bytes = 0;          // device memory held for the border
     DeviceArray<double> d_bd_B, d_bd_C, d_bd_W, d_bd_D, d_bd_LU, d_bd_part, d_bd_rec;
@@ -233,6 +235,8 @@ struct SolverBorder {
     // The transposed side (solve_bordered_transpose), built at the first transposed call after a set_border and kept until the border
     // is dropped: V = A^{-T} C packed as W is, and D^T packed as D is.  A factorisation clears bt_ready with bd_k.
     DeviceArray<double> d_bt_V, d_bt_Dt;
+    DeviceArray<double> d_bt_LU;    // pairs: the LU of S_T = D^H - B^H V, the Schur complement of M^H factorised on its own (bt_prepare) ...
+    DeviceArray<int32_t> d_bt_piv;  // ... and its pivots
     bool bt_ready = false;
     int64_t bt_bytes = 0; // device memory held for the transposed side
 };
@@ -462,7 +466,11 @@ class Solver : public SolverDevice, public Tunables {
     // with partial pivoting in one workgroup; info (nullptr allowed): min / max |u_ii| of S, det S as mantissa and base-10 exponent,
     // bytes held.  k == 0 frees the border.  WARNING_SINGULAR_MATRIX for an exactly zero pivot of S: no border is left set.
     // Every factorisation drops the border (forget_border).
-    int32_t set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device);
+    // pairs (the complex twin, kernels_border_complex.hpp): this handle holds the real-equivalent system of a complex matrix; k counts
+    // COMPLEX columns (<= ZBORDER_MAX), B, C, D are interleaved complex arrays with ldb, ldc, ldd in doubles, C^T is the plain transpose,
+    // and info takes five doubles: min / max |u_ii| of the complex LU of S, real and imaginary mantissa and exponent of det S, bytes.
+    int32_t set_border(int32_t k, const double *B, int64_t ldb, const double *C, int64_t ldc, const double *D, int64_t ldd, double *info, bool on_device,
+                       bool pairs = false);
     // Block elimination refined on the whole system, per block of 16 columns: y = one unrefined pass pair of f, t = g - C^T y,
     // z = S^{-1} t, x = y - W z; then steps on the residual (f - A x - B z, g - C^T x - D z) by the stopping rule of solve() on the
     // componentwise backward error omega over all n + k rows, at most max_steps (<= 0: 4).  x, f: column-major ldx x nrhs; z, g:
@@ -475,8 +483,10 @@ class Solver : public SolverDevice, public Tunables {
     // transposed pass pair for the plain one, S^T = D^T - B^T V through the LU of S (U^T, L^T, the exchanges backwards), and the
     // residual over the rows of M^T.  Arguments, info and status codes as solve_bordered.  V and the packed D^T are built at the first
     // call after a set_border (bt_prepare); counters 44 - 46 and the statistics of every other solve are left as they were.
+    // With a border set in pairs mode the system is M^H [y; w] = [p; q], M^H = [A^H conj(C); B^H D^H] (the transposed real-equivalent
+    // system); conj_pairs: M^T instead -- the same loop on conjugated data, staged on the device, conjugated back on the way out.
     int32_t solve_bordered_transpose(double *y, double *w, const double *p, const double *q, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info,
-                                     bool on_device);
+                                     bool on_device, bool conj_pairs = false);
     void drop_border(); // frees the border's device memory
     void forget_border() { bd_k = 0, bt_ready = false; } // a new factor: the border and what was built from it are no longer valid
     int64_t bordered_steps = 0, bordered_blocks = 0; // of the last solve_bordered: block steps summed over the blocks, 16-column blocks
@@ -643,7 +653,8 @@ class Solver : public SolverDevice, public Tunables {
     int32_t tr_pass_blk(double *Z, const double *V, int32_t C);
     // the loop of solve_bordered (T false) and solve_bordered_transpose (T true): the operands and the four launches that differ
     template <bool T>
-    int32_t bordered_core(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info, bool on_device);
+    int32_t bordered_core(double *x, double *z, const double *f, const double *g, int32_t nrhs, int64_t ldx, int64_t ldz, int32_t max_steps, double *info, bool on_device,
+                          bool conj_pairs = false);
     int32_t bt_prepare(); // V = A^{-T} C and the packed D^T of the border in force, once per set_border
     // Z = A^{-T} V for C <= 16 columns at the strides zs, vs, unrefined: the blocked pass pair, tr_pass per column without its buffers
     // or with HIPMF_TRANSPOSE_BLOCKED=0, solve_core on a handle where A^T = A (vs == zs there)
