@@ -469,6 +469,74 @@ int32_t solver_hipmf_solve_adjoint(struct InterfaceHIPMF *solver, double *lambda
 int32_t solver_hipmf_solve_adjoint_device(struct InterfaceHIPMF *solver, double *d_lambda, double *d_grad_values, const double *d_x, const double *d_g, int32_t nrhs,
                                           int32_t ld, double beta, int32_t mapped);
 
+/* THE INERTIA of the factorised matrix: how many of its eigenvalues are positive, negative and zero, from the signs of the pivots D of
+ * L D L^T (Sylvester's law of inertia).  For a handle that factorised K - sigma M with M positive definite, n_negative is the number of
+ * eigenvalues of K x = lambda M x below sigma -- the direct solver's own count, and the certificate that a Lanczos run missed none.
+ * The symmetric scaling S A S and the symmetric fill-reducing permutation are congruences: they leave the inertia alone.  The signs are
+ * counted on the device (integer counts in per-workgroup slots, added in slot order; kernels_eigs.hpp); any of the three outputs may
+ * be NULL.  Status codes in this order: ERROR_NULL_POINTER (solver), ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION,
+ * ERROR_NOT_AVAILABLE -- for a general handle, for a symmetric-lower handle that was expanded to general storage
+ * (HIPMF_COUNTER_SYM_EXPANDED: an LU with a matching) and for HIPMF_COUNTER_SYMMETRIC_LDLT == 0.  The tiled fronts of a symmetric
+ * handle take pivot c from row c: their pivots are D.  The fronts of at most 64 rows that one wavefront factorises in LDS search their
+ * pivot block on every handle; on diagonally dominant and on most definite matrices the search keeps the diagonal (ties go to it) and
+ * their pivots are D as well.  Where it moved a row (indefinite matrices), the signs of that front's pivots say nothing -- but the
+ * inertia of the matrix is the sum over the fronts of the inertia of their pivot blocks whatever the order inside them, so such a
+ * front's block is multiplied out from its factors and counted by a Bunch-Kaufman elimination in LDS, one wavefront per front
+ * (k_eig_inertia_small).  Replaced pivots (num_perturbed_pivots > 0) and zero pivots are reported in
+ * n_zero, the other two counts cover the rest, and the call returns HIPMF_WARNING_SINGULAR_MATRIX: the counts are then those of a nearby
+ * matrix.  ONE EXCEPTION: a replaced pivot inside a front that was multiplied out again cannot be told from the others any more; it is
+ * counted by the sign the perturbed block gives it, not in n_zero, and only the warning status tells.  No side effects on the factor, the statistics or the counters. */
+int32_t solver_hipmf_get_inertia(struct InterfaceHIPMF *solver, int64_t *n_positive, int64_t *n_negative, int64_t *n_zero);
+
+/* EIGENPAIRS NEAREST A SHIFT on the kept factor: shift-invert Lanczos (what ARPACK's mode 3 does with any direct solver), with the whole
+ * iteration on the device.  The handle holds the factor of A = K - sigma M, which the caller assembled and factorised; the call returns
+ * the nev eigenvalues lambda_i of K x = lambda M x with the smallest |lambda_i - sigma|, ordered by that distance, and their eigenvectors.
+ * M is given as VALUES ON THE HANDLE'S PATTERN, as solver_hipmf_solve_updated takes `values`: mapped = 0 the CSR order of initialize (a
+ * symmetric-lower handle: its lower triangle), mapped = 1 the nnz_in inputs of the value map; m_values NULL: M = I.  They pass through
+ * the staging of a factorize into the operator's buffer of the solve_updated forms, not the one refinement and mat_vec_mul read.  M must
+ * be symmetric positive definite (a diagonal M is in the pattern); v^T M v <= 0 or not finite at any normalisation returns
+ * ERROR_HIPMF_INVALID_VALUE.  The handle must have been initialised from a symmetric lower triangle -- kept as L D L^T or expanded to
+ * general storage, Lanczos needs a symmetric operator, not a particular factor --; any other handle returns ERROR_NOT_AVAILABLE.
+ * X: column-major ldx x nev, ldx >= ndim, M-orthonormal, the entry of largest modulus of every column (the first on ties) positive.
+ * backward_error[i] (NULL allowed) = |A x_i - mu_i M x_i|_inf / ((|A|_inf + |mu_i| |M|_inf) |x_i|_inf) with mu_i = lambda_i - sigma, the
+ * TRUE residual recomputed on the device at the end, never the Lanczos estimate.  lambda, backward_error (nev doubles), nconv, steps
+ * (NULL allowed): on the host in both forms.
+ * Method (Solver::eigs_near_shift, kernels_eigs.hpp): thick-restart Lanczos (Wu & Simon) on A^{-1} M in the M-inner product with full
+ * reorthogonalisation.  One step: p = M v_j (the stream SpMV; skipped for M = I), w = A^{-1} p by the path of solver_hipmf_solve_device
+ * WITH its refinement, classical Gram-Schmidt twice in the M-inner product against the whole basis with the fixed-order reductions of
+ * the solve_updated forms, M w recomputed by SpMV (no second basis), v_{j+1} = w / sqrt(w^T M w).  The host reads 2 (j + 1) + 1 doubles
+ * per step and keeps the projected matrix, diagonalised by a cyclic Jacobi method (on the HOST, at every step up to 32 basis vectors
+ * and every fourth beyond: near ncv = 128 one such look is of the order of 1e8 flops and is expected to cost more than the step's
+ * solve -- there the host, not the device, is the limit; not measured above ncv = 40).  Pair i has converged when
+ * |beta s_i| <= tol |theta_i| (ARPACK's rule on the operator, theta_i = 1 / mu_i).  A full basis restarts with
+ * k = nev + (ncv - nev) / 2 Ritz vectors (at most ncv - 1), formed in place on the FP64 MFMA (k_eig_rotate).  A breakdown (beta at the
+ * rounding level) continues with the next vector of the start sequence, M-orthogonalised; a basis that spans the whole space ends the
+ * call with what was found.  v0: the caller's start vector (normalised inside) or NULL: entry i of the vector of sequence number s is
+ * (h + 0.5) / 2^31 - 1 with the 32-bit hash h = i 0x9e3779b1 + s 0x85ebca77 + 0x165667b1; h ^= h >> 16; h *= 0x7feb352d;
+ * h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16 (wrap-around arithmetic), s = 0 first, the breakdown path takes the following ones
+ * (with v0 given it starts at s = 0).  No rand, no clock.
+ * Limits and defaults: 1 <= nev <= 64, nev < ndim, nev < ncv <= min(ndim, 128); ncv <= 0 selects min(ndim, max(2 nev + 8, 24)); tol <= 0
+ * selects 1e-10; max_steps <= 0 selects 20 ncv.  A basis that does not fit in device memory is halved down to nev + 2 vectors, then
+ * ERROR_HIP_MALLOC.  Returns 0 when nev pairs have converged, HIPMF_WARNING_NOT_CONVERGED when max_steps operator applications are
+ * used up: the arrays hold the nev Ritz pairs NEAREST the shift (largest |theta|) and no others, the converged ones of them first, and
+ * *nconv counts the converged among them -- a pair further away that has converged never takes a place or counts.  *steps counts operator applications.
+ * Status codes in this order: ERROR_NULL_POINTER (solver, lambda, X), ERROR_NEED_INITIALIZATION, ERROR_NEED_FACTORIZATION,
+ * ERROR_NOT_AVAILABLE, ERROR_HIPMF_INVALID_VALUE (nev, ncv, ldx < ndim, a non-finite tol or sigma, mapped = 1 without a map).
+ * NO SIDE EFFECTS on the factor, the border in force, the values refinement reads, the timers, statistics and existing counters, or the
+ * bits of later solves.  BIT-REPRODUCIBLE from call to call and between the two forms: no floating-point atomics.
+ * HIPMF_COUNTER_EIGS_STEPS / _RESTARTS / _CONVERGED / _BASIS_BYTES describe the last call; _SOLVE_US / _SPMV_US / _ORTH_US / _ROTATE_US
+ * are the HIP-event times of its phases.  The complex handle has no such call.
+ * WHAT IT COSTS (tools/eigs.py, one MI355X, one run, 1M unknowns as a lower triangle, profiles/r25_eigs.txt):
+ * sigma = 0, M = I, nev = 1 / 6 / 16: 14.9 / 34.8 / 95.5 ms on device vectors (12 / 28 / 72 steps), 15.4 / 40.8 / 112.6 ms on host vectors,
+ * against 286 / 620 / 1258 ms for scipy's eigsh driving solver_hipmf_solve on the same handle; a step = the refined solve (1.03 ms;
+ * 1.5 ms at an indefinite shift) + 0.08 - 0.18 ms of Gram-Schmidt + 0.13 ms for the three SpMVs with M. */
+int32_t solver_hipmf_eigs_near_shift(struct InterfaceHIPMF *solver, int32_t nev, int32_t ncv, double sigma, const double *m_values, int32_t mapped, const double *v0,
+                                     double tol, int32_t max_steps, double *lambda, double *X, int32_t ldx, double *backward_error, int32_t *nconv, int32_t *steps,
+                                     C_BOOL verbose);
+int32_t solver_hipmf_eigs_near_shift_device(struct InterfaceHIPMF *solver, int32_t nev, int32_t ncv, double sigma, const double *d_m_values, int32_t mapped,
+                                            const double *d_v0, double tol, int32_t max_steps, double *lambda, double *d_X, int32_t ldx, double *backward_error,
+                                            int32_t *nconv, int32_t *steps);
+
 /* Solves exactly as solver_hipmf_solve (the same x, bit for bit), then analyses x against A and b as MUMPS does with
  * ICNTL(11) (the argument shape of solver_mumps_solve, interface_mumps.c:243-247; its RINFOG(4..11) are copied out at
  * interface_mumps.c:266-275 and read by solver_mumps.rs:249-253,415-422).  error_analysis_option: 0 none (array untouched),
@@ -599,6 +667,14 @@ int32_t solver_hipmf_reset_timers(struct InterfaceHIPMF *solver);
 #define HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_STEPS 55  /* complex twin: refinement steps of the last complex_solver_hipmf_solve_bordered_transpose / _device */
 #define HIPMF_COUNTER_COMPLEX_BORDERED_TRANSPOSED_BLOCKS 56 /* 16-column blocks of that call */
 #define HIPMF_COUNTER_COMPLEX_BORDER_TRANSPOSED_BYTES 57    /* complex twin: device bytes held for V = A^{-H} conj(C) and D^H: 0 until the first transposed call */
+#define HIPMF_COUNTER_EIGS_STEPS 58       /* operator applications (refined solves) of the last solver_hipmf_eigs_near_shift / _device */
+#define HIPMF_COUNTER_EIGS_RESTARTS 59    /* ... its thick restarts */
+#define HIPMF_COUNTER_EIGS_CONVERGED 60   /* ... and the pairs that had converged when it returned (*nconv) */
+#define HIPMF_COUNTER_EIGS_BASIS_BYTES 61 /* device bytes held for the Lanczos basis of those calls (0 before the first) */
+#define HIPMF_COUNTER_EIGS_SOLVE_US 62    /* microseconds between HIP events around the solves of the last such call ... */
+#define HIPMF_COUNTER_EIGS_SPMV_US 63     /* ... its SpMVs with M ... */
+#define HIPMF_COUNTER_EIGS_ORTH_US 64     /* ... its Gram-Schmidt, norm and scaling kernels ... */
+#define HIPMF_COUNTER_EIGS_ROTATE_US 65   /* ... and its basis rotations (tools/eigs.py) */
 int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *solver, int32_t which);
 
 /* Options of LinSolParams that the initialize signature (kept in the shape of interface_cudss.cu:190-203 minus the cuDSS-only

@@ -290,6 +290,52 @@ class Hipmf:
             return x[0], (None if z is None else z[0]), info[0]
         return x, z, info
 
+    ERROR_NOT_AVAILABLE = 400000
+
+    def inertia(self):
+        """(n_positive, n_negative, n_zero, status) of the factorised matrix from the signs of the pivots of L D L^T
+        (solver_hipmf_get_inertia): status 0, or WARNING_SINGULAR_MATRIX when pivots were replaced or zero (they are counted in n_zero).
+        Raises HipmfError with code ERROR_NOT_AVAILABLE where the factor is no L D L^T (a general or an expanded handle)."""
+        pos, neg, zero = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        code = self.lib.solver_hipmf_get_inertia(self.h, C.addressof(pos), C.addressof(neg), C.addressof(zero))
+        if code not in (0, self.WARNING_SINGULAR_MATRIX):
+            raise self._err(code, "solver_hipmf_get_inertia")
+        return int(pos.value), int(neg.value), int(zero.value), code
+
+    def eigs_near_shift(self, nev, sigma, m_values=None, mapped=False, ncv=0, v0=None, tol=0.0, max_steps=0, ldx=None, verbose=False):
+        """The nev eigenpairs of K x = lambda M x nearest sigma on a handle that holds the factor of K - sigma M
+        (solver_hipmf_eigs_near_shift): m_values are M's values on the handle's pattern as solve_updated takes values (None: M = I),
+        v0 a start vector or None.  Returns (lambda, X, backward_error, nconv, steps, status): lambda and backward_error of nev
+        entries, X of shape (nev, ldx) whose rows hold the eigenvectors in their first n entries (= column-major ldx x nev);
+        status 0 = nev pairs converged, 2 = HIPMF_WARNING_NOT_CONVERGED (the best nev Ritz pairs, converged first); others raise."""
+        nev = int(nev)
+        ldx = self.n if ldx is None else int(ldx)
+        lam, be = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        X = np.zeros((max(nev, 1), max(ldx, 1)))
+        mv = None if m_values is None else np.ascontiguousarray(m_values, dtype=np.float64)
+        if mv is not None:
+            assert mv.size >= self._value_count(mapped)
+        v = None if v0 is None else np.ascontiguousarray(v0, dtype=np.float64)
+        nconv, steps = C.c_int32(0), C.c_int32(0)
+        code = self.lib.solver_hipmf_eigs_near_shift(self.h, nev, int(ncv), float(sigma), None if mv is None else mv.ctypes.data, int(bool(mapped)),
+                                                     None if v is None else v.ctypes.data, float(tol), int(max_steps), lam.ctypes.data, X.ctypes.data, ldx,
+                                                     be.ctypes.data, C.addressof(nconv), C.addressof(steps), int(verbose))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_eigs_near_shift")
+        return lam[:nev], X[:nev], be[:nev], int(nconv.value), int(steps.value), code
+
+    def eigs_near_shift_device(self, nev, sigma, d_X, d_m_values=None, mapped=False, ncv=0, d_v0=None, tol=0.0, max_steps=0, ldx=None):
+        """eigs_near_shift with M's values, the start vector and X (column-major ldx x nev) resident on the device; returns
+        (lambda, backward_error, nconv, steps, status)"""
+        nev = int(nev)
+        lam, be = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        nconv, steps = C.c_int32(0), C.c_int32(0)
+        code = self.lib.solver_hipmf_eigs_near_shift_device(self.h, nev, int(ncv), float(sigma), d_m_values, int(bool(mapped)), d_v0, float(tol), int(max_steps),
+                                                            lam.ctypes.data, d_X, int(ldx or self.n), be.ctypes.data, C.addressof(nconv), C.addressof(steps))
+        if code not in (0, self.WARNING_NOT_CONVERGED):
+            raise self._err(code, "solver_hipmf_eigs_near_shift_device")
+        return lam[:nev], be[:nev], int(nconv.value), int(steps.value), code
+
     def _value_count(self, mapped):
         """entries of a value array of this handle: the inputs of the value map (mapped) or what factorize takes"""
         return int(self.nnz_in) if mapped else int(self.nnz)
@@ -372,7 +418,7 @@ class Hipmf:
         out.update({k: float(v) for k, v in zip(DSTAT_NAMES, d)})
         return out
 
-    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48, "bordered_transposed_steps": 49, "bordered_transposed_blocks": 50, "border_transposed_bytes": 51, "complex_border_columns": 52, "complex_bordered_steps": 53, "complex_bordered_blocks": 54, "complex_bordered_transposed_steps": 55, "complex_bordered_transposed_blocks": 56, "complex_border_transposed_bytes": 57}
+    COUNTERS = {"rematch": 0, "weak_diagonal_rows": 1, "fused_fallbacks": 2, "persistent_bytes": 3, "arena_bytes": 4, "symmetric_ldlt": 5, "sym_expanded": 6, "chain_fallbacks": 7, "mid_fronts": 8, "plan_digest": 9, "tagged_solve": 10, "gate_waits": 11, "wave_fronts": 12, "leaf_fronts": 13, "split_slabs": 14, "event_fence_free": 15, "block_groups": 16, "sym_weak_diagonal": 17, "bcast_sliced_bytes": 18, "krylov_iterations": 19, "transposed_solves": 20, "analysis_solves": 21, "transposed_krylov_iterations": 22, "transposed_blocks": 23, "pruned_fwd_fronts": 24, "pruned_bwd_fronts": 25, "pruned_blocks": 26, "pruned_bytes": 27, "updated_steps": 28, "updated_cycles": 29, "updated_basis_bytes": 30, "updated_precond_us": 31, "updated_spmv_us": 32, "updated_arnoldi_us": 33, "updated_blocks": 34, "updated_column_steps": 35, "updated_block_basis_bytes": 36, "pruned_transposed_blocks": 38, "extra_precise_steps": 39, "extra_precise_blocks": 40, "extra_precise_residual_us": 41, "extra_precise_precond_us": 42, "extra_precise_update_us": 43, "border_columns": 44, "bordered_steps": 45, "bordered_blocks": 46, "sens_outer_columns": 47, "sens_outer_us": 48, "bordered_transposed_steps": 49, "bordered_transposed_blocks": 50, "border_transposed_bytes": 51, "complex_border_columns": 52, "complex_bordered_steps": 53, "complex_bordered_blocks": 54, "complex_bordered_transposed_steps": 55, "complex_bordered_transposed_blocks": 56, "complex_border_transposed_bytes": 57, "eigs_steps": 58, "eigs_restarts": 59, "eigs_converged": 60, "eigs_basis_bytes": 61, "eigs_solve_us": 62, "eigs_spmv_us": 63, "eigs_orth_us": 64, "eigs_rotate_us": 65}
 
     WARNING_NOT_CONVERGED = 2
 

@@ -599,6 +599,48 @@ int32_t solver_hipmf_solve_updated_device(struct InterfaceHIPMF *h, double *d_x,
     return guarded(h, [&]() { return solve_updated_body(h, d_x, d_rhs, d_values, mapped, rel_tol, max_steps, steps, relres, 0, true, "solver_hipmf_solve_updated_device"); });
 }
 
+// The inertia of the factor (Solver::inertia): the signs of the pivots, counted on the device.  A symmetric-lower handle that was
+// expanded to general storage holds an LU with a matching: its pivots say nothing about the inertia.
+int32_t solver_hipmf_get_inertia(struct InterfaceHIPMF *h, int64_t *n_positive, int64_t *n_negative, int64_t *n_zero) {
+    if (!h) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    if (h->expanded) return ERROR_NOT_AVAILABLE;
+    return guarded(h, [&]() { return h->solver.inertia(n_positive, n_negative, n_zero); });
+}
+
+// Eigenpairs nearest the shift on the kept factor (Solver::eigs_near_shift): thick-restart Lanczos on A^{-1} M, on the device.
+// Status codes in the project's order: NULL pointers, initialize, factorize, then the kind of handle, then the values.
+static int32_t eigs_body(struct InterfaceHIPMF *h, int32_t nev, int32_t ncv, double sigma, const double *m_values, int32_t mapped, const double *v0, double tol,
+                         int32_t max_steps, double *lambda, double *X, int32_t ldx, double *backward_error, int32_t *nconv, int32_t *steps, C_BOOL verbose, bool on_device,
+                         const char *who) {
+    if (!h || !lambda || !X) return ERROR_NULL_POINTER;
+    if (!h->solver.initialized) return ERROR_NEED_INITIALIZATION;
+    if (!h->solver.factorized) return ERROR_NEED_FACTORIZATION;
+    h->solver.opt.verbose = verbose == 1;
+    int32_t nc = 0, st = 0;
+    const int32_t code = h->solver.eigs_near_shift(nev, ncv, sigma, m_values, mapped != 0, v0, tol, max_steps, lambda, X, ldx, backward_error, &nc, &st, on_device, h->expanded);
+    if (nconv) *nconv = nc;
+    if (steps) *steps = st;
+    if (verbose == 1 && (code == SUCCESSFUL_EXIT || code == HIPMF_WARNING_NOT_CONVERGED))
+        printf("%s: %d of %d pair(s) converged after %d operator application(s), %lld restart(s)\n", who, nc, nev, st, (long long)h->solver.eigs_restarts);
+    return code;
+}
+
+int32_t solver_hipmf_eigs_near_shift(struct InterfaceHIPMF *h, int32_t nev, int32_t ncv, double sigma, const double *m_values, int32_t mapped, const double *v0, double tol,
+                                     int32_t max_steps, double *lambda, double *X, int32_t ldx, double *backward_error, int32_t *nconv, int32_t *steps, C_BOOL verbose) {
+    return guarded(h, [&]() {
+        return eigs_body(h, nev, ncv, sigma, m_values, mapped, v0, tol, max_steps, lambda, X, ldx, backward_error, nconv, steps, verbose, false, "solver_hipmf_eigs_near_shift");
+    });
+}
+
+int32_t solver_hipmf_eigs_near_shift_device(struct InterfaceHIPMF *h, int32_t nev, int32_t ncv, double sigma, const double *d_m_values, int32_t mapped, const double *d_v0,
+                                            double tol, int32_t max_steps, double *lambda, double *d_X, int32_t ldx, double *backward_error, int32_t *nconv, int32_t *steps) {
+    return guarded(h, [&]() {
+        return eigs_body(h, nev, ncv, sigma, d_m_values, mapped, d_v0, tol, max_steps, lambda, d_X, ldx, backward_error, nconv, steps, 0, true, "solver_hipmf_eigs_near_shift_device");
+    });
+}
+
 // The same for nrhs columns (Solver::solve_updated_many): blocks of 16 columns, every column its own flexible GMRES, in lockstep.
 static int32_t solve_updated_many_body(struct InterfaceHIPMF *h, double *x, const double *rhs, int32_t nrhs, int32_t ld, const double *values, int32_t mapped,
                                        double rel_tol, int32_t max_steps, int32_t *steps, double *relres, C_BOOL verbose, bool on_device, const char *who,
@@ -939,6 +981,14 @@ int64_t solver_hipmf_get_counter(struct InterfaceHIPMF *h, int32_t which) {
     case HIPMF_COUNTER_BORDERED_TRANSPOSED_STEPS: return s.bordered_t_steps;
     case HIPMF_COUNTER_BORDERED_TRANSPOSED_BLOCKS: return s.bordered_t_blocks;
     case HIPMF_COUNTER_BORDER_TRANSPOSED_BYTES: return s.bt_bytes;
+    case HIPMF_COUNTER_EIGS_STEPS: return s.eigs_steps;
+    case HIPMF_COUNTER_EIGS_RESTARTS: return s.eigs_restarts;
+    case HIPMF_COUNTER_EIGS_CONVERGED: return s.eigs_converged;
+    case HIPMF_COUNTER_EIGS_BASIS_BYTES: return s.eigs_basis_bytes();
+    case HIPMF_COUNTER_EIGS_SOLVE_US: return (int64_t)(1e3 * s.eigs_ms[0]);
+    case HIPMF_COUNTER_EIGS_SPMV_US: return (int64_t)(1e3 * s.eigs_ms[1]);
+    case HIPMF_COUNTER_EIGS_ORTH_US: return (int64_t)(1e3 * s.eigs_ms[2]);
+    case HIPMF_COUNTER_EIGS_ROTATE_US: return (int64_t)(1e3 * s.eigs_ms[3]);
     default: return -1;
     }
 }

@@ -64,4 +64,50 @@ struct GivensLsq {
     }
 };
 
+// Eigenvalues w and orthonormal eigenvectors Z (row-major n x n, Z[r n + c] = component r of eigenvector c) of the symmetric matrix A
+// (row-major, leading dimension lda; only read) by the cyclic Jacobi method -- the projected matrix of the thick-restart Lanczos
+// (Solver::eigs_near_shift), n <= 128.  The textbook scheme: sweeps over the upper triangle by rows, the rotation that annihilates
+// a_pq from t = sign(tau) / (|tau| + sqrt(1 + tau^2)), tau = (a_qq - a_pp) / (2 a_pq); after three sweeps an entry that no longer
+// changes either diagonal neighbour in working precision is set to zero.  Small eigenvector components come out with small absolute
+// errors relative to their own size, which the Lanczos stop test (the LAST row of Z) relies on.  Deterministic: no data-dependent order.
+inline void jacobi_eigh(int32_t n, const double *A, int32_t lda, std::vector<double> &w, std::vector<double> &Z) {
+    std::vector<double> a((size_t)n * n);
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t j = 0; j < n; j++) a[(size_t)i * n + j] = i <= j ? A[(size_t)i * lda + j] : A[(size_t)j * lda + i];
+    Z.assign((size_t)n * n, 0.0);
+    for (int32_t i = 0; i < n; i++) Z[(size_t)i * n + i] = 1.0;
+    for (int sweep = 0; sweep < 100; sweep++) {
+        double off = 0.0;
+        for (int32_t p = 0; p < n; p++)
+            for (int32_t q = p + 1; q < n; q++) off += std::fabs(a[(size_t)p * n + q]);
+        if (off == 0.0) break;
+        for (int32_t p = 0; p < n - 1; p++)
+            for (int32_t q = p + 1; q < n; q++) {
+                const double apq = a[(size_t)p * n + q];
+                if (apq == 0.0) continue;
+                const double app = a[(size_t)p * n + p], aqq = a[(size_t)q * n + q], g = 100.0 * std::fabs(apq);
+                if (sweep > 2 && std::fabs(app) + g == std::fabs(app) && std::fabs(aqq) + g == std::fabs(aqq)) {
+                    a[(size_t)p * n + q] = a[(size_t)q * n + p] = 0.0;
+                    continue;
+                }
+                const double tau = (aqq - app) / (2.0 * apq);
+                const double t = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), s = t * c;
+                a[(size_t)p * n + p] = app - t * apq, a[(size_t)q * n + q] = aqq + t * apq;
+                a[(size_t)p * n + q] = a[(size_t)q * n + p] = 0.0;
+                for (int32_t r = 0; r < n; r++) {
+                    if (r != p && r != q) {
+                        const double arp = a[(size_t)r * n + p], arq = a[(size_t)r * n + q];
+                        a[(size_t)r * n + p] = a[(size_t)p * n + r] = c * arp - s * arq;
+                        a[(size_t)r * n + q] = a[(size_t)q * n + r] = s * arp + c * arq;
+                    }
+                    const double zrp = Z[(size_t)r * n + p], zrq = Z[(size_t)r * n + q];
+                    Z[(size_t)r * n + p] = c * zrp - s * zrq, Z[(size_t)r * n + q] = s * zrp + c * zrq;
+                }
+            }
+    }
+    w.resize((size_t)n);
+    for (int32_t i = 0; i < n; i++) w[(size_t)i] = a[(size_t)i * n + i];
+}
+
 } // namespace hipmf

@@ -28,6 +28,7 @@
 #include "kernels_krylov_complex_blocked.hpp"
 #include "kernels_krylov_transpose.hpp"
 #include "kernels_error_analysis_complex.hpp"
+#include "kernels_eigs.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <pthread.h>
@@ -4783,6 +4784,394 @@ int32_t Solver::solve_adjoint(double *lambda, double *grad, const double *x, con
     }
     if (code != SUCCESSFUL_EXIT || !grad) return code;
     return values_outer(grad, lambda, x, nrhs, ld, ld, -1.0, beta, mapped, on_device);
+}
+
+// ---- the inertia of the factor, and eigenpairs nearest the shift on the kept factor (kernels_eigs.hpp) ----
+
+// Sylvester's law: A = L D L^T has as many positive / negative eigenvalues as D has positive / negative entries.  The symmetric scaling
+// S A S and the symmetric fill-reducing permutation P A P^T are congruences: they leave the inertia alone, so the pivots in d_diag
+// speak of the caller's matrix.  The tiled fronts of a symmetric handle take pivot c from row c by construction (kernels_factor.hpp,
+// PIVOT = !SYM): their pivots are D.  The fronts that k_small_factor holds in LDS search the pivot block whatever the handle; where
+// the search kept the diagonal their pivots are D as well, where it moved a row k_eig_inertia_small counts the inertia of the front's
+// pivot block from the product of its factors (see there) -- the sum over the fronts is the inertia of the matrix either way.
+int32_t Solver::inertia(int64_t *n_positive, int64_t *n_negative, int64_t *n_zero) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!S.sym_mode) return ERROR_NOT_AVAILABLE;
+    DeviceScope dev_scope(device);
+    const int32_t n = S.n;
+    if (!d_eg_local) { // per pivot position: 0 in a small front, -1 in a tiled one; and the list of the small fronts
+        std::vector<int32_t> local((size_t)n, -1), small;
+        for (int32_t s = 0; s < S.nsuper; s++)
+            if (S.fsize(s) <= SMALL_F) {
+                small.push_back(s);
+                for (int32_t i = 0; i < S.npiv(s); i++) local[(size_t)S.sn_first[s] + i] = 0;
+            }
+        eg_nsmall = (int32_t)small.size();
+        HIPC(d_eg_small.upload(small), ERROR_HIP_MALLOC);
+        HIPC(d_eg_cnt.alloc(4 * ((size_t)EIG_INERTIA_WG + small.size()) + 4), ERROR_HIP_MALLOC);
+        HIPC(d_eg_local.upload(local), ERROR_HIP_MALLOC);
+    }
+    const int32_t nwg = (int32_t)std::min<int64_t>(EIG_INERTIA_WG, ((int64_t)n + 255) / 256);
+    const int64_t nslot = (int64_t)nwg + eg_nsmall;
+    int64_t *const d_sum = d_eg_cnt + 4 * ((size_t)EIG_INERTIA_WG + (size_t)eg_nsmall);
+    hipLaunchKernelGGL(k_eig_inertia, dim3(nwg), dim3(256), 0, STREAM, n, (const double *)d_diag, (const unsigned long long *)d_scalar, opt.pivot_epsilon,
+                       (const int32_t *)d_eg_local, (int64_t *)d_eg_cnt);
+    if (eg_nsmall > 0)
+        hipLaunchKernelGGL(k_eig_inertia_small, dim3((unsigned)eg_nsmall), dim3(64), 0, STREAM, (const int32_t *)d_eg_small, (const FrontDesc *)d_fd, (const double *)d_pool,
+                           (const int32_t *)d_lperm, (const double *)d_diag, (const unsigned long long *)d_scalar, opt.pivot_epsilon, d_eg_cnt + 4 * (size_t)nwg);
+    hipLaunchKernelGGL(k_eig_inertia_sum, dim3(1), dim3(256), 0, STREAM, nslot, (const int64_t *)d_eg_cnt, d_sum);
+    int64_t got[4] = {0, 0, 0, 0};
+    HIPC(hipMemcpyAsync(got, d_sum, sizeof got, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    inertia_fronts_recounted = got[3];
+    if (n_positive) *n_positive = got[0];
+    if (n_negative) *n_negative = got[1];
+    if (n_zero) *n_zero = got[2];
+    return (got[2] > 0 || n_perturbed > 0 || n_zero_pivot > 0) ? WARNING_SINGULAR_MATRIX : SUCCESSFUL_EXIT;
+}
+
+namespace {
+
+// events around the phases of a Lanczos step (0 solve, 1 SpMV, 2 orthogonalisation, 3 rotation; -1: the end of the last phase), read
+// after the step's synchronisation
+struct EigTimer {
+    EventOwner *ev;
+    hipStream_t st;
+    double *ms;
+    int tag[16];
+    int cnt = 0;
+    void mark(int t) {
+        if (cnt < 16 && hipEventRecord((hipEvent_t)ev[cnt], st) == hipSuccess) tag[cnt++] = t;
+    }
+    void flush() {
+        float e = 0.0f;
+        for (int i = 0; i + 1 < cnt; i++)
+            if (tag[i] >= 0 && hipEventElapsedTime(&e, (hipEvent_t)ev[i], (hipEvent_t)ev[i + 1]) == hipSuccess) ms[tag[i]] += e;
+        cnt = 0;
+    }
+};
+
+} // namespace
+
+// Shift-invert Lanczos with thick restart (Wu & Simon) on OP = A^{-1} M, which is symmetric in the M-inner product; A = K - sigma M is
+// what the handle factorised, so an eigenvalue theta of OP is 1 / (lambda - sigma) and the wanted pairs are those of largest |theta|.
+// One step with the basis v_0 .. v_j: p = M v_j (the stream SpMV on the staged values; M = I: nothing), w = A^{-1} p by solve() with
+// the handle's refinement, CGS2 in the M-inner product -- h = V^T (M w) by k_kry_dots / k_kry_reduce, w -= V h by k_kry_update, twice,
+// M w recomputed by SpMV each time (no second basis M V) --, beta^2 = w^T M w, v_{j+1} = w / beta (k_kry_scale).  The host reads the
+// 2 (j + 1) coefficients and beta^2 and keeps the projected matrix T: alpha_j = h_j on the diagonal, beta_j beside it, after a restart
+// the arrowhead beta s_i in row and column k.  T is diagonalised by cyclic Jacobi (krylov_host.hpp) when the basis is full and, before
+// that, at every step up to 32 vectors and every fourth beyond: pair i has converged when |beta s_{q-1, i}| <= tol |theta_i| (ARPACK's
+// rule).  A full basis restarts with the k = nev + (ncv - nev) / 2 (at most ncv - 1) Ritz vectors of largest |theta|, formed in place by
+// k_eig_rotate, and v_k = v_ncv.  beta at the rounding level of |w| before Gram-Schmidt is a (lucky) breakdown: the next vector of the
+// start sequence (k_eig_start) is M-orthogonalised against the basis and the iteration goes on with beta = 0; a basis that spans the
+// whole space ends the call.  At the end X = V Y (k_eig_rotate into the caller's array), the sign of every column is fixed, and the
+// TRUE residuals |A x - mu M x|_inf come from k_eig_residuals.
+int32_t Solver::eigs_near_shift(int32_t nev, int32_t ncv, double sigma, const double *m_values, bool mapped, const double *v0, double tol, int32_t max_steps,
+                                double *lambda, double *X, int64_t ldx, double *backward_error, int32_t *nconv_out, int32_t *steps_out, bool on_device,
+                                bool symmetric_matrix) {
+    if (!initialized) return ERROR_NEED_INITIALIZATION;
+    if (!factorized) return ERROR_NEED_FACTORIZATION;
+    if (!lambda || !X) return ERROR_NULL_POINTER;
+    if (!(S.sym_lower || symmetric_matrix) || opt.complex_pairs) return ERROR_NOT_AVAILABLE;
+    const int32_t n = S.n;
+    if (nev < 1 || nev > EIG_NEV_MAX || nev >= n || ldx < n || !std::isfinite(tol) || !std::isfinite(sigma)) return ERROR_HIPMF_INVALID_VALUE;
+    if (ncv <= 0) ncv = std::min(n, std::max(2 * nev + 8, 24));
+    if (ncv <= nev || ncv > std::min<int32_t>(n, EIG_MMAX)) return ERROR_HIPMF_INVALID_VALUE;
+    if (m_values && mapped && nnz_in < 1) return ERROR_HIPMF_INVALID_VALUE; // no map set
+    if (!(tol > 0.0)) tol = 1e-10;
+    DeviceScope dev_scope(device);
+    eigs_steps = eigs_restarts = eigs_converged = 0;
+    eigs_ms[0] = eigs_ms[1] = eigs_ms[2] = eigs_ms[3] = 0.0;
+    if (nconv_out) *nconv_out = 0;
+    if (steps_out) *steps_out = 0;
+
+    // ---- buffers ----
+    int32_t m = ncv;
+    if (eg_m < m) {
+        d_eg_V.reset(), eg_m = 0;
+        for (int32_t mm = m;; mm = std::max(nev + 2, mm / 2)) {
+            if (mm <= nev) break; // (ncv == nev + 1 did not fit)
+            if (d_eg_V.alloc(((size_t)mm + 1) * (size_t)n) == hipSuccess) {
+                eg_m = mm;
+                break;
+            }
+            (void)hipGetLastError();
+            if (mm <= nev + 2) break;
+        }
+        if (eg_m == 0) {
+            last_error = "eigs_near_shift: no device memory for the Lanczos basis";
+            return ERROR_HIP_MALLOC;
+        }
+    }
+    m = std::min(m, eg_m);
+    if (max_steps <= 0) max_steps = 20 * m;
+    const int32_t nblk = (int32_t)(((int64_t)n + KRY_TILE - 1) / KRY_TILE), g256 = (n + 255) / 256;
+    const size_t rec_h = 2 * ((size_t)EIG_MMAX + 1) + 4, rec_y = (size_t)EIG_MMAX * EIG_MMAX, rec_total = rec_h + rec_y + 4 * (size_t)EIG_NEV_MAX + 4;
+    if (!eg_small) {
+        HIPC(d_eg_vec.alloc(3 * (size_t)n), ERROR_HIP_MALLOC);
+        HIPC(d_eg_part.alloc(((size_t)EIG_MMAX + 2) * nblk + (2 * (size_t)EIG_NEV_MAX + 1) * g256), ERROR_HIP_MALLOC);
+        HIPC(d_eg_idx.alloc((size_t)EIG_NEV_MAX * g256), ERROR_HIP_MALLOC);
+        HIPC(d_eg_rec.alloc(rec_total), ERROR_HIP_MALLOC);
+        HIPC(h_eg.alloc(rec_total), ERROR_HIP_MALLOC);
+        for (int t = 0; t < 16; t++) HIPC(hipEventCreate(eg_ev[t].put()), ERROR_HIP_SYNCHRONIZE);
+        eg_small = true;
+    }
+    if (!on_device && eg_xcols < nev) {
+        HIPC(d_eg_X.alloc((size_t)n * nev), ERROR_HIP_MALLOC);
+        eg_xcols = nev;
+    }
+    const bool has_m = m_values != nullptr;
+    if (has_m) {
+        if (!d_up_vals) HIPC(d_up_vals.alloc((size_t)std::max<int64_t>(S.nnz_a, 1)), ERROR_HIP_MALLOC);
+        const int32_t c = stage_values(d_up_vals, m_values, mapped, on_device);
+        if (c != SUCCESSFUL_EXIT) return c;
+    }
+    double *const V = d_eg_V, *const d_p = d_eg_vec, *const d_w = d_eg_vec + (size_t)n, *const d_q = d_eg_vec + 2 * (size_t)n;
+    double *const d_h = d_eg_rec, *const d_nrm = d_eg_rec + 2 * ((size_t)EIG_MMAX + 1), *const d_Y = d_eg_rec + rec_h, *const d_mu = d_Y + rec_y;
+    double *const d_out = d_mu + EIG_NEV_MAX; // 2 nev maxima, then |A|, |M|; the signs behind them
+    double *const d_sign = d_out + 2 * (size_t)EIG_NEV_MAX + 4;
+    double *const h_h = h_eg, *const h_Y = h_eg + rec_h, *const h_mu = h_Y + rec_y, *const h_out = h_mu + EIG_NEV_MAX;
+    double *const d_part = d_eg_part, *const d_part2 = d_eg_part + ((size_t)EIG_MMAX + 2) * nblk;
+    double *const Xd = on_device ? X : (double *)d_eg_X;
+    const int64_t ldxd = on_device ? ldx : n;
+    const dim3 gk((unsigned)nblk), b256(256), gn((unsigned)g256);
+    const size_t nb = sizeof(double) * (size_t)n;
+    const double EPS = 2.220446049250313e-16;
+    EigTimer timer{eg_ev, STREAM, eigs_ms};
+
+    // y = M x on the staged values; M = I: x itself
+    bool timed = true;
+    auto times_m = [&](const double *x, double *y) -> const double * {
+        if (!has_m) return x;
+        if (timed) timer.mark(1);
+        hipLaunchKernelGGL(k_spmv_stream<false>, dim3(spmv_blocks), b256, 0, STREAM, d_row_blk, d_rp, d_ci, d_up_vals, d_tptr, d_tidx, d_arow, 1.0, x, (const double *)nullptr, y,
+                           (unsigned long long *)nullptr);
+        return y;
+    };
+    // one round of Gram-Schmidt of w against v_0 .. v_{nv - 1} in the M-inner product, the coefficients to hr (device)
+    auto gs_round = [&](int32_t nv, double *hr) {
+        const double *mw = times_m(d_w, d_q);
+        timer.mark(2);
+        hipLaunchKernelGGL(k_kry_dots, gk, b256, 0, STREAM, (int64_t)n, mw, (const double *)V, nv, d_part);
+        hipLaunchKernelGGL(k_kry_reduce, dim3(nv), b256, 0, STREAM, (const double *)d_part, nblk, hr);
+        hipLaunchKernelGGL(k_kry_update, gk, b256, 0, STREAM, (int64_t)n, d_w, (const double *)V, nv, (const double *)hr, d_part);
+    };
+    // d_nrm[0] = w^T M w
+    auto m_norm2 = [&]() {
+        const double *mw = times_m(d_w, d_q);
+        timer.mark(2);
+        hipLaunchKernelGGL(k_kry_dots, gk, b256, 0, STREAM, (int64_t)n, mw, (const double *)d_w, 1, d_part);
+        hipLaunchKernelGGL(k_kry_reduce, dim3(1), b256, 0, STREAM, (const double *)d_part, nblk, d_nrm);
+    };
+    // the record of a step on the host: cnt doubles from d_h, then the norm word
+    auto read_record = [&](int32_t cnt) -> int32_t {
+        timer.mark(-1);
+        if (cnt > 0) HIPC(hipMemcpyAsync(h_h, d_h, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipMemcpyAsync(h_h + 2 * ((size_t)EIG_MMAX + 1), d_nrm, sizeof(double), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+        timer.flush();
+        return SUCCESSFUL_EXIT;
+    };
+    double &h_nrm = h_h[2 * ((size_t)EIG_MMAX + 1)];
+    const auto invalid_m = [&]() {
+        last_error = "eigs_near_shift: v^T M v is not positive (M must be symmetric positive definite)";
+        return ERROR_HIPMF_INVALID_VALUE;
+    };
+    // v_dst = the vector of the start sequence number `seq`, M-orthogonalised against v_0 .. v_{nv - 1} and normalised; the norm must be
+    // positive and finite.  *ok = false: the vector lies in the span of the basis to rounding (the caller tries the next one).
+    uint32_t seq = 0;
+    auto new_direction = [&](int32_t nv, double *v_dst, bool *ok) -> int32_t {
+        *ok = false;
+        m_norm2();
+        int32_t c = read_record(0);
+        if (c != SUCCESSFUL_EXIT) return c;
+        const double before = h_nrm;
+        if (!(before > 0.0) || !std::isfinite(before)) return invalid_m();
+        if (nv > 0) {
+            gs_round(nv, d_h), gs_round(nv, d_h + nv);
+            m_norm2();
+            c = read_record(0);
+            if (c != SUCCESSFUL_EXIT) return c;
+            if (!std::isfinite(h_nrm)) return invalid_m();
+            if (!(h_nrm > 1e-8 * before)) return SUCCESSFUL_EXIT; // (half of the digits gone: not a direction of its own)
+        }
+        hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_nrm, v_dst);
+        *ok = true;
+        return SUCCESSFUL_EXIT;
+    };
+
+    const NestedSolveGuard guard(*this); // (the solves are refined as the handle is set up; the statistics of the ordinary solves stay the caller's)
+    opt.verbose = false;
+    int32_t code = SUCCESSFUL_EXIT;
+    // ---- the start vector ----
+    {
+        if (v0) HIPC(hipMemcpyAsync(d_w, v0, nb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        else hipLaunchKernelGGL(k_eig_start, gn, b256, 0, STREAM, n, seq++, d_w);
+        bool ok = false;
+        code = new_direction(0, V, &ok);
+        if (code != SUCCESSFUL_EXIT) return code;
+    }
+    std::vector<double> T((size_t)m * m, 0.0), theta, Z, Ysel;
+    std::vector<int32_t> order;
+    std::vector<char> conv;
+    int32_t j = 0, q = 0, nconv = 0;
+    double beta_last = 0.0;
+    bool done = false, spans = false;
+    while (!done) {
+        // ---- one Lanczos step ----
+        const double *vj = V + (size_t)j * n;
+        const double *rhs = times_m(vj, d_p);
+        timer.mark(0);
+        code = solve(d_w, rhs, 1, n, true);
+        if (code != SUCCESSFUL_EXIT) return code;
+        eigs_steps++;
+        const int32_t nv = j + 1;
+        gs_round(nv, d_h), gs_round(nv, d_h + nv);
+        m_norm2();
+        code = read_record(2 * nv);
+        if (code != SUCCESSFUL_EXIT) return code;
+        double hsum2 = 0.0;
+        bool finite = std::isfinite(h_nrm);
+        for (int32_t i = 0; i < nv; i++) {
+            const double hi = h_h[i] + h_h[nv + i];
+            finite = finite && std::isfinite(hi);
+            hsum2 += hi * hi;
+        }
+        if (!finite) return invalid_m();
+        const double beta2 = h_nrm, wnorm2 = hsum2 + std::max(beta2, 0.0), level = 1024.0 * EPS;
+        const bool breakdown = !(beta2 > level * level * wnorm2);
+        if (breakdown && beta2 < -level * level * wnorm2) return invalid_m();
+        T[(size_t)j * m + j] = h_h[j] + h_h[nv + j];
+        q = j + 1;
+        beta_last = breakdown ? 0.0 : sqrt(beta2);
+        if (!breakdown) {
+            hipLaunchKernelGGL(k_kry_scale, gk, b256, 0, STREAM, (int64_t)n, (const double *)d_w, (const double *)d_nrm, V + (size_t)q * n);
+        } else if (q >= n) {
+            spans = true;
+        } else { // the next vector of the start sequence, against the whole basis
+            bool ok = false;
+            for (int attempt = 0; attempt < 4 && !ok; attempt++) {
+                hipLaunchKernelGGL(k_eig_start, gn, b256, 0, STREAM, n, seq++, d_w);
+                code = new_direction(q, V + (size_t)q * n, &ok);
+                if (code != SUCCESSFUL_EXIT) return code;
+            }
+            if (!ok) spans = true; // (nothing new to be had: stop with what has been found)
+        }
+        if (q < m) T[(size_t)j * m + q] = T[(size_t)q * m + j] = beta_last;
+        if (guard.verbose) fprintf(stderr, "hipmf: eigs_near_shift: step %lld, basis %d, beta %.3e%s\n", (long long)eigs_steps, q, beta_last, breakdown ? " (breakdown)" : "");
+        const bool out_of_steps = eigs_steps >= max_steps;
+        if (!(q == m || out_of_steps || spans || q <= 32 || (q & 3) == 0)) {
+            j = q;
+            continue;
+        }
+        // ---- the Ritz pairs of the basis so far ----
+        jacobi_eigh(q, T.data(), m, theta, Z);
+        order.resize((size_t)q);
+        for (int32_t i = 0; i < q; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return std::fabs(theta[(size_t)a]) > std::fabs(theta[(size_t)b]); });
+        conv.assign((size_t)q, 0);
+        nconv = 0;
+        for (int32_t i = 0; i < q; i++) {
+            const int32_t e = order[(size_t)i];
+            conv[(size_t)e] = std::fabs(beta_last * Z[(size_t)(q - 1) * q + e]) <= tol * std::fabs(theta[(size_t)e]);
+            if (i < nev && conv[(size_t)e]) nconv++;
+        }
+        done = (q >= nev && nconv == nev) || out_of_steps || spans;
+        if (done) break;
+        if (q < m) {
+            j = q;
+            continue;
+        }
+        // ---- thick restart ----
+        const int32_t k = std::min(nev + (m - nev) / 2, m - 1);
+        for (int32_t c = 0; c < k; c++)
+            for (int32_t r = 0; r < m; r++) h_Y[(size_t)c * m + r] = Z[(size_t)r * m + order[(size_t)c]];
+        HIPC(hipMemcpyAsync(d_Y, h_Y, sizeof(double) * (size_t)m * k, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+        timer.mark(3);
+        hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)((n + 63) / 64)), b256, 0, STREAM, n, m, k, (const double *)V, (const double *)d_Y, V, (int64_t)n);
+        timer.mark(-1);
+        HIPC(hipMemcpyAsync(V + (size_t)k * n, V + (size_t)m * n, nb, hipMemcpyDeviceToDevice, STREAM), ERROR_HIP_MEMCPY);
+        HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE); // (h_Y may be rewritten)
+        timer.flush();
+        std::fill(T.begin(), T.end(), 0.0);
+        for (int32_t c = 0; c < k; c++) {
+            const int32_t e = order[(size_t)c];
+            T[(size_t)c * m + c] = theta[(size_t)e];
+            T[(size_t)c * m + k] = T[(size_t)k * m + c] = beta_last * Z[(size_t)(m - 1) * m + e];
+        }
+        eigs_restarts++;
+        j = k;
+    }
+
+    // ---- the results: the nev Ritz pairs of largest |theta| and no others -- a pair further from the shift that happens to have
+    // converged (an isolated one at the far end of the spectrum does so early) never displaces a nearer one --, the converged ones
+    // of them first, each group by distance from the shift; nconv counts the converged among these
+    const int32_t nout = std::min(nev, q);
+    std::vector<int32_t> sel;
+    for (int pass = 0; pass < 2; pass++)
+        for (int32_t i = 0; i < nout; i++)
+            if ((conv[(size_t)order[(size_t)i]] != 0) == (pass == 0)) sel.push_back(order[(size_t)i]);
+    nconv = 0;
+    for (int32_t c = 0; c < nout; c++) {
+        const int32_t e = sel[(size_t)c];
+        nconv += conv[(size_t)e] ? 1 : 0;
+        h_mu[c] = 1.0 / theta[(size_t)e];
+        lambda[c] = sigma + h_mu[c];
+        for (int32_t r = 0; r < q; r++) h_Y[(size_t)c * q + r] = Z[(size_t)r * q + e];
+    }
+    for (int32_t c = nout; c < nev; c++) { // (fewer steps than pairs asked for: the rest is empty)
+        lambda[c] = sigma;
+        if (backward_error) backward_error[c] = 1.0;
+        HIPC(hipMemsetAsync(Xd + (size_t)c * ldxd, 0, nb, STREAM), ERROR_HIP_MEMCPY);
+    }
+    HIPC(hipMemcpyAsync(d_Y, h_Y, sizeof(double) * (size_t)q * nout, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipMemcpyAsync(d_mu, h_mu, sizeof(double) * (size_t)nout, hipMemcpyHostToDevice, STREAM), ERROR_HIP_MEMCPY);
+    timer.mark(3);
+    hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)((n + 63) / 64)), b256, 0, STREAM, n, q, nout, (const double *)V, (const double *)d_Y, Xd, ldxd);
+    timer.mark(-1);
+    // |x_c|_M = 1 once more, from a compensated x_c^T M x_c (the norms of the iteration carry the rounding of plain sums over n)
+    timed = false; // (the phases of the steps and the rotations are what the counters report)
+    for (int32_t c = 0; c < nout; c++) {
+        const double *xc = Xd + (size_t)c * ldxd;
+        const double *mx = times_m(xc, d_q);
+        hipLaunchKernelGGL(k_eig_dot2, gn, b256, 0, STREAM, n, xc, (int64_t)0, mx, (int64_t)0, d_part2 + (size_t)c * g256, d_part2 + ((size_t)nout + c) * g256);
+    }
+    hipLaunchKernelGGL(k_eig_dot2_sum, dim3((unsigned)nout), dim3(64), 0, STREAM, g256, (const double *)d_part2, (const double *)(d_part2 + (size_t)nout * g256), d_sign);
+    hipLaunchKernelGGL(k_eig_scale_cols, dim3((unsigned)g256, (unsigned)nout), b256, 0, STREAM, n, Xd, ldxd, (const double *)d_sign);
+    int32_t *const d_pi = d_eg_idx;
+    hipLaunchKernelGGL(k_eig_absmax, dim3((unsigned)g256, (unsigned)nout), b256, 0, STREAM, n, (const double *)Xd, ldxd, d_part2, d_pi);
+    hipLaunchKernelGGL(k_eig_sign, dim3((unsigned)nout), dim3(64), 0, STREAM, g256, (const double *)Xd, ldxd, (const double *)d_part2, (const int32_t *)d_pi, d_sign);
+    hipLaunchKernelGGL(k_eig_flip, dim3((unsigned)g256, (unsigned)nout), b256, 0, STREAM, n, Xd, ldxd, (const double *)d_sign);
+    // |A|_inf, |M|_inf once, then the true residuals of all columns in one pass over the values
+    hipLaunchKernelGGL(k_eig_rownorm, gn, b256, 0, STREAM, n, (const int32_t *)d_rp, (const double *)d_vals, (const int32_t *)d_tptr, (const int32_t *)d_tidx, d_part2);
+    hipLaunchKernelGGL(k_eig_max, dim3(1), b256, 0, STREAM, (const double *)d_part2, g256, d_out + 2 * (size_t)EIG_NEV_MAX);
+    if (has_m) {
+        hipLaunchKernelGGL(k_eig_rownorm, gn, b256, 0, STREAM, n, (const int32_t *)d_rp, (const double *)d_up_vals, (const int32_t *)d_tptr, (const int32_t *)d_tidx, d_part2);
+        hipLaunchKernelGGL(k_eig_max, dim3(1), b256, 0, STREAM, (const double *)d_part2, g256, d_out + 2 * (size_t)EIG_NEV_MAX + 1);
+    }
+    hipLaunchKernelGGL(k_eig_residuals, gn, b256, 0, STREAM, n, (const int32_t *)d_rp, (const int32_t *)d_ci, (const double *)d_vals,
+                       has_m ? (const double *)d_up_vals : (const double *)nullptr, (const int32_t *)d_tptr, (const int32_t *)d_tidx, (const int32_t *)d_arow, (const double *)Xd, ldxd,
+                       (const double *)d_mu, nout, d_part2);
+    hipLaunchKernelGGL(k_eig_max, dim3(2 * (unsigned)nout), b256, 0, STREAM, (const double *)d_part2, g256, d_out);
+    HIPC(hipMemcpyAsync(h_out, d_out, sizeof(double) * (2 * (size_t)EIG_NEV_MAX + 2), hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    if (!on_device)
+        for (int32_t c = 0; c < nev; c++) HIPC(hipMemcpyAsync(X + (int64_t)c * ldx, Xd + (size_t)c * n, nb, hipMemcpyDeviceToHost, STREAM), ERROR_HIP_MEMCPY);
+    HIPC(hipStreamSynchronize(STREAM), ERROR_HIP_SYNCHRONIZE);
+    timer.flush();
+    HIPC(hipGetLastError(), ERROR_HIP_LAUNCH);
+    const double anorm = h_out[2 * (size_t)EIG_NEV_MAX], mnorm = has_m ? h_out[2 * (size_t)EIG_NEV_MAX + 1] : 1.0;
+    for (int32_t c = 0; c < nout && backward_error; c++) {
+        const double den = (anorm + std::fabs(h_mu[c]) * mnorm) * h_out[nout + c];
+        backward_error[c] = den > 0.0 ? h_out[c] / den : (h_out[c] > 0.0 ? 1.0 : 0.0);
+    }
+    eigs_converged = nconv;
+    if (nconv_out) *nconv_out = nconv;
+    if (steps_out) *steps_out = (int32_t)eigs_steps;
+    if (guard.verbose)
+        fprintf(stderr, "hipmf: eigs_near_shift: %d of %d pair(s) converged after %lld step(s), %lld restart(s)\n", nconv, nev, (long long)eigs_steps, (long long)eigs_restarts);
+    return nconv == nev ? SUCCESSFUL_EXIT : WARNING_NOT_CONVERGED;
 }
 
 // ---- the transposed bordered system (the loop: bordered_core above) ----

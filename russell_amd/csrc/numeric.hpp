@@ -257,10 +257,27 @@ struct SolverSensitivity {
     EventOwner sn_ev0, sn_ev1; // around the outer and scatter kernels of a call
 };
 
+// solver_hipmf_eigs_near_shift / solver_hipmf_get_inertia (kernels_eigs.hpp), allocated at the first call.  The Lanczos basis V
+// ((m + 1) x n, its own allocation: the bases of solve_updated stay as they are), three n-vectors (p = M v, w, a staging vector), the
+// staged X of a host-pointer call, the per-workgroup slots of the residual, norm and sign kernels, the small device record (the
+// coefficients of a step, Y of a rotation, mu, the norms) and its pinned mirror; for the inertia a word per pivot position (0 in a
+// small front, -1 in a tiled one), the list of the small fronts and the integer slots of the count.  M's values are staged in d_up_vals.
+struct SolverEigs {
+    DeviceArray<double> d_eg_V, d_eg_vec, d_eg_X, d_eg_part, d_eg_rec;
+    DeviceArray<int32_t> d_eg_idx, d_eg_local, d_eg_small;
+    DeviceArray<int64_t> d_eg_cnt;
+    PinnedArray<double> h_eg;
+    int32_t eg_nsmall = 0;  // small fronts of the plan (entries of d_eg_small)
+    int32_t eg_m = 0;       // basis vectors V is allocated for, less one (0: not allocated)
+    int32_t eg_xcols = 0;   // columns d_eg_X is allocated for
+    bool eg_small = false;  // the slots and the record exist
+    EventOwner eg_ev[16];   // around the phases of a step
+};
+
 // Everything a Solver holds on the device, and the counts that describe it.  Assigning a fresh instance frees it all and resets the
 // counts; members are assigned in declaration order: the transposed-solve state, device memory, pinned memory, the graph and the
 // events, the streams.
-struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise, SolverBorder, SolverSensitivity {
+struct SolverDevice : SolverTransposed, SolverPruned, SolverUpdated, SolverExtraPrecise, SolverBorder, SolverSensitivity, SolverEigs {
     // exported for the many-RHS / multi-GPU paths: the factor lives in [d_pool, d_pool + pool_doubles)
     DeviceArray<double> d_pool;
     DeviceArray<int32_t> d_lperm;
@@ -517,6 +534,24 @@ class Solver : public SolverDevice, public Tunables {
     // grad = beta grad + alpha sum_c u_c op(w_c)^T |pattern on complex entries, op = conj with conjugate_w; ldu, ldw in complex elements
     int32_t values_outer_complex(double *grad, const double *u, const double *w, int32_t ncols, int64_t ldu, int64_t ldw, double alpha, double beta,
                                  bool conjugate_w);
+    // The inertia of the factorised matrix from the signs of the pivots (Sylvester's law; kernels_eigs.hpp).  Needs the L D L^T plan
+    // (S.sym_mode; else ERROR_NOT_AVAILABLE).  The fronts one wavefront factorises in LDS (k_small_factor) search their pivot block also
+    // on a symmetric handle: where one moved a row, the inertia of its pivot block is counted from the product of its factors instead
+    // (inertia_fronts_recounted tells how many).  The symmetric scaling S A S and the symmetric permutation are congruences and leave
+    // the inertia alone.  Replaced and zero pivots are counted in n_zero and make the call return WARNING_SINGULAR_MATRIX.
+    int32_t inertia(int64_t *n_positive, int64_t *n_negative, int64_t *n_zero);
+    int64_t inertia_fronts_recounted = 0; // small fronts of the last inertia() whose pivot search had moved a row
+    // The nev eigenpairs of K x = lambda M x nearest sigma, the handle holding the factor of A = K - sigma M: thick-restart Lanczos on
+    // A^{-1} M in the M-inner product, everything of length n on the device (kernels_eigs.hpp; see numeric.cpp).  m_values: M on the
+    // handle's pattern as solve_updated takes values (nullptr: M = I); v0: start vector or nullptr; X: column-major ldx x nev;
+    // lambda, backward_error (nev each), nconv, steps: on the host.  symmetric_matrix: the interface expanded a symmetric matrix to
+    // general storage.  SUCCESSFUL_EXIT or WARNING_NOT_CONVERGED.  The factor, d_vals, the border and every statistic stay as they were.
+    int32_t eigs_near_shift(int32_t nev, int32_t ncv, double sigma, const double *m_values, bool mapped, const double *v0, double tol, int32_t max_steps,
+                            double *lambda, double *X, int64_t ldx, double *backward_error, int32_t *nconv, int32_t *steps, bool on_device,
+                            bool symmetric_matrix = false);
+    int64_t eigs_steps = 0, eigs_restarts = 0, eigs_converged = 0; // of the last eigs_near_shift: operator applications, restarts, converged pairs
+    int64_t eigs_basis_bytes() const { return eg_m > 0 ? ((int64_t)eg_m + 1) * S.n * 8 : 0; }
+    double eigs_ms[4] = {0.0, 0.0, 0.0, 0.0}; // HIP-event time of the last call's solves, SpMVs, orthogonalisation kernels, rotations
     int64_t sens_outer_columns = 0; // columns summed by the outer products of this handle, over all calls
     double sens_outer_ms = 0.0;     // HIP-event time of the outer and scatter kernels of the last such call
     int64_t updated_block_basis_bytes() const { return ub_m > 0 ? (int64_t)(2 * (int64_t)ub_m + 1) * ub_cols * S.n * 8 : 0; }
